@@ -1,9 +1,17 @@
 #!/usr/bin/env python
 """bench.py -- depth-maps/sec of PatchmatchNet inference on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without a launcher: spawns its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what ``value`` needs: set up, W warm-up steps (+ the --settle-seconds pass), K timed steps, the outputs of
+the last timed step written with --dump-outputs, the line.  Everything else on the line -- ``roofline``, ``single_stream_eager``,
+``steady_state``, ``outputs_verified``, ``value_other_input_mode`` and, at N=1, ``cpu_baseline``, ``reference_rocm``,
+``eval_end_to_end`` -- is measured only with ``--full`` (the passes below; a verified step that differs then fails the process).
+The stage-3 random draw is seeded at the start of the timed region, so the same arguments give the same outputs run after run.
+--dump-outputs DIR: ``DIR/depth.npy`` [1,1,H,W] and ``DIR/confidence.npy`` [1,H,W] (float32) of rank 0's last timed step, i.e. what
+a caller of the timed path receives; above 64 MB in all, every array is replaced by the same seeded sample of its elements.
 
 A "step" = one full ``PatchmatchNet.forward`` (FeatureNet, the learned-PatchMatch hot path, refinement, confidence -- all in
 the HIP kernels of patchmatchnet_amd/csrc) for ONE reference view with 5 source views at 1600x1200, iterations (1,2,2) -- BASELINE.json configs[1].
@@ -19,10 +27,10 @@ steps in exactly the timed mode, compared BIT FOR BIT with the same steps launch
 process exit non-zero.  (Rounds 2-4 overlapped forwards whose outputs were NOT the eager forward's, round 5 found that out and fell
 back to one hardware queue; round 6 found the cause -- a packed-fp32 instruction form that MI355X computes wrongly beside kernels that
 issue fp16 MFMAs, DESIGN_LESSONS.md lesson 46 -- and removed it from the library: overlap is back, verified.)
-``--eager`` restores the round-1 mode (one stream, kernels launched from Python); the line always carries that figure too
+``--eager`` restores the round-1 mode (one stream, kernels launched from Python); the --full line always carries that figure too
 (``single_stream_eager`` = one sample's latency).
 
-Extra objects on the line: ``roofline`` for the dominant kernel (pmn_warp_correlate; HIP events on the launch stream around
+Extra objects on the line (--full): ``roofline`` for the dominant kernel (pmn_warp_correlate; HIP events on the launch stream around
 its launches in an eager single-stream pass of the same run -- launches inside a replayed graph cannot be bracketed and
 overlapped kernels have no duration of their own; algorithmic bytes per SURVEY.md 8(d); next to the contract's HBM fraction the
 line carries the bound that actually holds, the vector-L1 / texture-addresser path: ``tap_bytes_per_step``, ``l1_achieved``,
@@ -66,6 +74,33 @@ def warp_kernel_source_hash():
         with open(os.path.join(ROOT, "patchmatchnet_amd", "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
+
+
+DRAW_SEED = 4321  # torch.manual_seed at the start of every timed loop: the stage-3 draws, and so the outputs, repeat run to run
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def hardware_queues():
+    """The hardware queues the run had: GPU_MAX_HW_QUEUES unset or set to the HIP runtime's default (4) are the same configuration."""
+    q = os.environ.get("GPU_MAX_HW_QUEUES")
+    if q is None:
+        return "runtime default (GPU_MAX_HW_QUEUES unset: 4)"
+    return "runtime default (GPU_MAX_HW_QUEUES=4)" if q.strip() == "4" else q
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as ``out_dir/<name>.npy`` in float32.  Above DUMP_LIMIT_BYTES in all, every array is replaced by
+    the same fixed, seeded sample of its flattened elements (sorted indices), so that two builds' files still compare element for
+    element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, (a.size * (DUMP_LIMIT_BYTES - 4096 * len(arrays))) // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 REFERENCE_CPU_MEASURED = {
@@ -358,7 +393,7 @@ def main():
     ap.add_argument("--width", type=int, default=1600)
     ap.add_argument("--height", type=int, default=1200)
     ap.add_argument("--views", type=int, default=5, help="number of SOURCE views (reference eval.py --num_views)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU / reference / eval.py legs")
     ap.add_argument("--in-flight", type=int, default=3,
                     help="independent samples in flight per GPU: one HIP stream + one replay slot each (1 = one stream)")
     ap.add_argument("--launch", choices=("plan", "graph"), default="plan",
@@ -369,16 +404,22 @@ def main():
     ap.add_argument("--eager", action="store_true",
                     help="issue every kernel from Python on one stream (the round-1 mode) instead of replaying HIP graphs")
     ap.add_argument("--roofline-steps", type=int, default=24,
-                    help="eager single-stream steps after the timed region that carry the HIP events of the roofline figure")
+                    help="eager single-stream steps before the timed region that carry the HIP events of the roofline figure (--full)")
     ap.add_argument("--scene", choices=("surface", "rolled"), default="surface",
                     help="surface = photo-consistent rendered scene (tests/synth.render_scene); rolled = rounds 1-2's images")
     ap.add_argument("--settle-seconds", type=float, default=1.0,
                     help="untimed replays after the W warm-up steps until the clocks / caches have settled (the timed region is still "
                          "exactly K steps); 0 = only the W warm-up steps")
     ap.add_argument("--verify-steps", type=int, default=96,
-                    help="steps of the timed mode whose outputs are compared bit for bit with eager forwards under the same seeds (0 = skip)")
+                    help="steps of the timed mode whose outputs are compared bit for bit with eager forwards under the same seeds "
+                         "(--full; 0 = skip)")
     ap.add_argument("--steady-seconds", type=float, default=2.0,
-                    help="length of the extra steady-state pass reported as `steady_state` (0 = skip)")
+                    help="length of the extra steady-state pass reported as `steady_state` (--full; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes beyond `value`: roofline / single-stream eager pass, steady state, bit-for-bit verification, "
+                         "the other input mode and (N=1) the CPU / reference / eval.py legs; a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the depth and confidence maps of the last timed step (rank 0) as DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -460,7 +501,7 @@ def main():
     main_stream = torch.cuda.current_stream(device)
     with torch.no_grad():
         launch_note = None
-        # ---- roofline pass: HIP events around the pmn_warp_correlate launches ------------------------------------------------
+        # ---- roofline pass (--full): HIP events around the pmn_warp_correlate launches -----------------------------------------
         # (Runs FIRST, before the timed region: after seconds of three overlapped forwards the part runs 5-6 % slower clocks -- the same
         # launches 1.06 ms cold, 1.13 ms behind the steady-state pass -- and the rocprofv3 summary this figure must agree with is taken
         # from a run without that load.)
@@ -471,17 +512,19 @@ def main():
         EV = 4
         R = max(args.roofline_steps, EV)
         sampled = len(range(0, R, EV))
-        for i in range(3):
-            step(i)
-        barrier()
-        ops.enable_kernel_timing()
-        t1 = time.perf_counter()
-        for i in range(R):
-            ops.pause_kernel_timing(i % EV != 0)
-            step(i)
-        torch.cuda.synchronize()
-        eager_elapsed = time.perf_counter() - t1
-        recs = ops.disable_kernel_timing()
+        recs, eager_elapsed = [], None
+        if args.full:
+            for i in range(3):
+                step(i)
+            barrier()
+            ops.enable_kernel_timing()
+            t1 = time.perf_counter()
+            for i in range(R):
+                ops.pause_kernel_timing(i % EV != 0)
+                step(i)
+            torch.cuda.synchronize()
+            eager_elapsed = time.perf_counter() - t1
+            recs = ops.disable_kernel_timing()
 
 
         region = {}  # "run": callable(steps) -> seconds, the timed loop in the mode that produced `value` (re-used by steady_state)
@@ -501,6 +544,7 @@ def main():
 
         def timed_eager():
             def run(steps):
+                torch.manual_seed(DRAW_SEED)
                 barrier()
                 t0 = time.perf_counter()
                 outs = None
@@ -508,6 +552,7 @@ def main():
                     depth, conf, _ = step(i)
                     outs = (depth, conf)
                 close_region(outs)
+                region["outs"] = outs
                 return time.perf_counter() - t0
 
             for i in range(args.warmup):
@@ -547,6 +592,7 @@ def main():
                 extra_warmup[0] = keep  # (the line reports the untimed steps before `value`'s region)
 
             def run(steps):
+                torch.manual_seed(DRAW_SEED)
                 barrier()
                 t0 = time.perf_counter()
                 outs = None
@@ -555,6 +601,7 @@ def main():
                 for st in streams:
                     main_stream.wait_stream(st)
                 close_region(outs)
+                region["outs"] = outs
                 return time.perf_counter() - t0
 
             if publish:
@@ -571,10 +618,14 @@ def main():
                 launch_note = "python, one stream (HIP-graph capture failed: %s)" % why
                 S = 1
                 elapsed = timed_eager()
+        # what the caller of the timed path received in its last step (copied now: the passes below replay the same slots)
+        last_outputs = None
+        if args.dump_outputs and rank == 0:
+            last_outputs = {"depth": region["outs"][0].float().cpu().numpy(), "confidence": region["outs"][1].float().cpu().numpy()}
 
         # ---- steady state: the same loop for ~args.steady_seconds (clocks settled, thousands of launches), reported beside `value`
         steady = None
-        if args.steady_seconds > 0:
+        if args.full and args.steady_seconds > 0:
             n_steady = max(int(args.steady_seconds / (elapsed / args.steps)), args.steps)
             n_steady = int(reduce_scalar(float(n_steady), dist.ReduceOp.MAX))  # every rank runs the same count
             steady = (n_steady, reduce_scalar(region["run"](n_steady), dist.ReduceOp.MAX))
@@ -585,7 +636,7 @@ def main():
         # seeds: the two must agree BIT FOR BIT (rounds 2-5: overlapped forwards had come out a few pixels -- now and then entirely --
         # wrong: DESIGN_LESSONS.md lessons 45-46)
         verified = None
-        if not args.eager and launch_note is None and args.verify_steps > 0 and "replay" in region:
+        if args.full and not args.eager and launch_note is None and args.verify_steps > 0 and "replay" in region:
             V = args.verify_steps
             kept = []
             for i in range(V):
@@ -612,7 +663,7 @@ def main():
         # the other input mode beside `value` (rounds 2-4's `value` had all six images copied into the slot's static buffers inside the
         # timed region; eval.py's pipeline, which recycles its upload buffers, runs that mode): the same K steps, same box, same process
         other_mode = None
-        if not args.eager and launch_note is None:
+        if args.full and not args.eager and launch_note is None:
             alt, _ = timed_in_flight(copy_inputs=not args.copy_inputs, publish=False)
             if alt is not None:
                 other_mode = reduce_scalar(alt, dist.ReduceOp.MAX)
@@ -694,7 +745,7 @@ def main():
                        "scene": "photo-consistent rendered surface (tests/synth.render_scene), one texture seed per sample"
                                 if args.scene == "surface" else "rolled noise images (rounds 1-2)",
                        "parallelism": f"ref-view shards x{world}, all-gather of depth+confidence",
-                       "hardware_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (GPU_MAX_HW_QUEUES unset: 4)"),
+                       "hardware_queues": hardware_queues(),
                        "collective_stream": "RCCL's own stream, ordered after the slot streams through the launch stream (the closing all-gather "
                                             "is issued there after main_stream.wait_stream(slot) for every slot)" if launched else None,
                        "ranks_seen": ranks_seen, "backend": dist.get_backend() if launched else "none (single process, no process group)",
@@ -708,36 +759,39 @@ def main():
                        f", {S} sample(s) in flight on {S} HIP stream(s) per GPU; images "
                        + ("copied into the slot's static buffers" if args.copy_inputs else
                           "read in place through a device table of addresses (pmn_stem_f16s_views)"))},
-            "value_other_input_mode": None if other_mode is None else {
-                "mode": "images read in place through a device table of addresses" if args.copy_inputs else
-                        "all six images copied into the slot's static buffers inside the timed region (rounds 2-4's `value`, eval.py's mode)",
-                "value": round(world * args.steps / other_mode, 4), "ms_per_step": round(other_mode / args.steps * 1e3, 4)},
-            "outputs_verified": verified,
-            "steady_state": None if steady is None else {
-                "steps": steady[0], "seconds": round(steady[1], 3), "value": round(world * steady[0] / steady[1], 2),
-                "note": "the timed region's loop repeated for ~%.0f s in the same mode (not the contract's K steps)" % args.steady_seconds},
-            "single_stream_eager": {"value": round(R / eager_elapsed, 2), "ms_per_step": round(eager_elapsed / R * 1e3, 4),
-                                    "steps": R, "note": "this rank, one sample at a time, kernels issued from Python (the "
-                                    "round-1 mode; = one sample's latency); the roofline events were recorded in this pass"},
-            "roofline": {"bound": "hbm", "kernel": "gather_corr_kernel (pmn_warp_correlate)",
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "frac_of_measured_achievable": round(achieved / 6290.0, 5),  # 6.29 TB/s measured achievable
-                         "bound_actual": "vector L1 / texture addresser (64 B/clk/CU): HBM traffic is below the algorithmic bytes, "
-                                         "the taps are re-read ~37x through L1 (DESIGN.md section 4)",
-                         "tap_bytes_per_step": int(k_taps / sampled), "l1_achieved": round(l1_achieved, 1),
-                         "l1_peak": round(L1_PEAK_GBS, 1), "l1_frac": round(l1_achieved / L1_PEAK_GBS, 4),
-                         "traffic": traffic,
-                         "traffic_unit": traffic_note,
-                         "measured_in": "eager single-stream pass of the same run (see single_stream_eager): a replayed "
-                                        "graph's launches cannot be bracketed by events",
-                         "launches": len(recs), "steps_with_events": sampled,
-                         "kernel_ms_per_step": round(k_ms / sampled, 4), "alg_bytes_per_step": int(k_bytes / sampled),
-                         "per_shape": {k: {"ms_avg": round(v[0] / v[2], 4),
-                                           "GBps": round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0}
-                                       for k, v in per.items()}},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:  # the passes beyond `value` (a plain run does not measure them, and leaves them off the line)
+            line.update({
+                "value_other_input_mode": None if other_mode is None else {
+                    "mode": "images read in place through a device table of addresses" if args.copy_inputs else
+                            "all six images copied into the slot's static buffers inside the timed region (rounds 2-4's `value`, eval.py's mode)",
+                    "value": round(world * args.steps / other_mode, 4), "ms_per_step": round(other_mode / args.steps * 1e3, 4)},
+                "outputs_verified": verified,
+                "steady_state": None if steady is None else {
+                    "steps": steady[0], "seconds": round(steady[1], 3), "value": round(world * steady[0] / steady[1], 2),
+                    "note": "the timed region's loop repeated for ~%.0f s in the same mode (not the contract's K steps)" % args.steady_seconds},
+                "single_stream_eager": {"value": round(R / eager_elapsed, 2), "ms_per_step": round(eager_elapsed / R * 1e3, 4),
+                                        "steps": R, "note": "this rank, one sample at a time, kernels issued from Python (the "
+                                        "round-1 mode; = one sample's latency); the roofline events were recorded in this pass"},
+                "roofline": {"bound": "hbm", "kernel": "gather_corr_kernel (pmn_warp_correlate)",
+                             "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5),
+                             "frac_of_measured_achievable": round(achieved / 6290.0, 5),  # 6.29 TB/s measured achievable
+                             "bound_actual": "vector L1 / texture addresser (64 B/clk/CU): HBM traffic is below the algorithmic bytes, "
+                                             "the taps are re-read ~37x through L1 (DESIGN.md section 4)",
+                             "tap_bytes_per_step": int(k_taps / sampled), "l1_achieved": round(l1_achieved, 1),
+                             "l1_peak": round(L1_PEAK_GBS, 1), "l1_frac": round(l1_achieved / L1_PEAK_GBS, 4),
+                             "traffic": traffic,
+                             "traffic_unit": traffic_note,
+                             "measured_in": "eager single-stream pass of the same run (see single_stream_eager): a replayed "
+                                            "graph's launches cannot be bracketed by events",
+                             "launches": len(recs), "steps_with_events": sampled,
+                             "kernel_ms_per_step": round(k_ms / sampled, 4), "alg_bytes_per_step": int(k_bytes / sampled),
+                             "per_shape": {k: {"ms_avg": round(v[0] / v[2], 4),
+                                               "GBps": round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0.0}
+                                           for k, v in per.items()}},
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if affinity0 is not None:
                 os.sched_setaffinity(0, affinity0)  # the baselines time the HOST: every core the process was given
             # round 4: the REAL reference timed on this box -- host cores (kind "reference") and, through PyTorch-ROCm, this GPU (the
@@ -756,10 +810,12 @@ def main():
                     ref_gpu["this_engine_over_reference"] = round(value / ref_gpu["value"], 2)
                     ref_gpu["this_engine_single_stream_over_reference"] = round((R / eager_elapsed) / ref_gpu["value"], 2)
                 line["reference_rocm"] = ref_gpu
-        if world == 1 and not args.no_cpu_baseline and not args.eager and (H, W, n_src) == (1200, 1600, 5):
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.eager and (H, W, n_src) == (1200, 1600, 5):
             samples.clear()  # (the pipeline leg brings its own inputs; give the child process the memory)
             torch.cuda.empty_cache()
             line["eval_end_to_end"] = eval_end_to_end_leg(H, W, n_src, device)
+        if last_outputs is not None:
+            dump_outputs(args.dump_outputs, last_outputs)
         print(json.dumps(line), flush=True)
     if launched:
         dist.barrier()

@@ -10,9 +10,10 @@ PMN_EXPERIMENTAL=1 timeout 1500 python -m pytest tests/test_corr_mfma.py tests/t
 echo "== smoke" | tee -a gpurun_out/pytest_gpu.log
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee -a gpurun_out/pytest_gpu.log
 echo "== bench (no cpu baseline)" | tee -a gpurun_out/pytest_gpu.log
-timeout 600 python bench.py --no-cpu-baseline 2>&1 | grep '^{' > gpurun_out/bench_quick.json; python - <<'PY'
-import json
-j=json.load(open('gpurun_out/bench_quick.json'))
+BENCH_LINE=$(timeout 600 python bench.py --full --no-cpu-baseline 2>&1 | grep '^{') python - <<'PY'
+import json, os
+j=json.loads(os.environ['BENCH_LINE'])
+print(j)
 print('value',j['value'],'steady',j['steady_state']['value'],'eager',j['single_stream_eager']['value'],'frac',j['roofline']['frac'],'traffic',j['roofline']['traffic'])
 print(j['roofline']['per_shape'])
 PY

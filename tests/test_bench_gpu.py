@@ -1,7 +1,8 @@
 """GPU tests of the measurement contract: bench.py prints ONE JSON line with the agreed keys, in the default mode (three samples
 in flight, launch-plan replay), in the eager mode, and with two ranks (control flow of the multi-GPU launch: the collective
 decision about the recording, the closing all-gather, max over ranks) -- the two ranks share cuda:0 over gloo, which is what this
-box allows; on a multi-GPU node the same code runs over RCCL."""
+box allows; on a multi-GPU node the same code runs over RCCL.  These runs pass --full (the passes beyond `value`); a plain run
+times the K steps only, and writes the outputs of its last timed step with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--width", "640", "--height", "480", "--steps", "6", "--warmup", "2", "--samples", "3", "--roofline-steps", "4", "--verify-steps", "12",
-         "--no-cpu-baseline", "--steady-seconds", "0.2", "--settle-seconds", "0.2"]
+         "--no-cpu-baseline", "--steady-seconds", "0.2", "--settle-seconds", "0.2", "--full"]
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
         "dtype", "data", "config", "roofline", "single_stream_eager", "steady_state"}
 
@@ -117,3 +118,27 @@ def test_bench_self_launches_its_ranks():
     line = _line(p.stdout)
     _check(line, 2)
     assert line["scaling"] == "weak"
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_repeatable_outputs(tmp_path):
+    """Without --full the line carries the headline figure and none of the extra passes; --dump-outputs writes the last timed step's
+    depth and confidence maps as float32, and two runs with the same arguments write the same bits (the stage-3 draw is seeded)."""
+    assert torch.cuda.is_available(), "GPU tests selected but no ROCm device is visible"
+    import numpy as np
+    plain = ["--width", "640", "--height", "480", "--steps", "5", "--warmup", "2", "--samples", "3", "--settle-seconds", "0.2"]
+    got = []
+    for k in range(2):
+        d = str(tmp_path / f"run{k}")
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + plain + ["--dump-outputs", d], capture_output=True,
+                           text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = _line(p.stdout)
+        assert line["steps"] == 5 and line["n_gpus"] == 1 and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["value"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+        assert not ({"roofline", "single_stream_eager", "steady_state", "outputs_verified", "cpu_baseline"} & set(line)), sorted(line)
+        assert sorted(os.listdir(d)) == ["confidence.npy", "depth.npy"]
+        depth, conf = np.load(os.path.join(d, "depth.npy")), np.load(os.path.join(d, "confidence.npy"))
+        assert depth.dtype == np.float32 and depth.shape == (1, 1, 480, 640) and conf.dtype == np.float32 and conf.shape == (1, 480, 640)
+        assert np.isfinite(depth).all() and np.isfinite(conf).all() and depth.max() > 0
+        got.append((depth, conf))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
