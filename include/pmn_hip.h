@@ -10,6 +10,7 @@
  *   - all tensor arguments are DEVICE pointers to contiguous float32 buffers owned (and pre-allocated) by the
  *     caller; the library never allocates, never synchronises, and launches on `stream` (a hipStream_t; pass the
  *     caller's current stream, NULL = default stream);
+ *     (exception: pmn_view_scores, the COLMAP import's view selection, takes float64 / int32 / int64 buffers, as declared);
  *   - arguments named *_host are small HOST arrays (neighbour tables) copied into the kernel-argument segment;
  *   - returns PMN_OK (0) or a negative PMN_ERR_* code; nothing is launched when an argument check fails;
  *   - entry points never block: each one only ENQUEUES kernels (no hip*Synchronize, no hipMalloc / hipFree, no hipMemcpy /
@@ -37,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PMN_ABI_VERSION 22
+#define PMN_ABI_VERSION 23
 #define PMN_MLP_FLOATS 340
 #define PMN_MAX_DEPTH 64
 #define PMN_MAX_NEIGHBORS 17
@@ -342,6 +343,19 @@ const char *pmn_plan_kernel_name(const void *plan, int index);
 int pmn_plan_launch(const void *plan, void *stream);
 int pmn_plan_destroy(void *plan);
 
+/* ABI 23.  View selection of the COLMAP import (reference colmap_input.py:336-366): the full N x N float64 score matrix of every
+ * image pair, score[i][j] = score[j][i] = sum over the observations of image min(i,j), in that image's order, of the points also
+ * observed by image max(i,j), of exp(-(theta - theta0)^2 / (2 sigma^2)) (theta = the triangulation angle in degrees, sigma = sigma1
+ * for theta <= theta0, else sigma2); score[i][i] = 0.  Every entry is written (no memset needed).  Inputs, all DEVICE and contiguous:
+ *   cam_centers [N][3] float64 (-R^T t), xyz [P][3] float64 (points indexed densely 0..P-1);
+ *   obs_ptr [N+1] int64 / obs_pt [n_obs] int32: per image its observations in the image's own order, untriangulated entries dropped,
+ *     duplicates kept (CSR; obs_ptr[N] == n_obs);
+ *   trk_ptr [P+1] int64 / trk_img [n_trk] int32: per point the DISTINCT images observing it, ascending (CSR; trk_ptr[P] == n_trk).
+ * Each score is a sequential float64 sum in that order: the same bits on every run; IEEE operations without contraction, so a point
+ * at a camera centre (or an acos argument beyond +-1) gives NaN as numpy does.  One launch of N x ceil(N / 4096) one-wave workgroups. */
+int pmn_view_scores(const double *cam_centers, const double *xyz, const long long *obs_ptr, const int *obs_pt,
+                    const long long *trk_ptr, const int *trk_img, int N, int P, long long n_obs, long long n_trk,
+                    double theta0, double sigma1, double sigma2, double *score, void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ from typing import Optional
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "libpmn_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 MLP_FLOATS = 340
 MAX_DEPTH = 64
 MAX_NEIGHBORS = 17
@@ -66,6 +66,7 @@ SIGNATURES = {
     "pmn_plan_kernel_name": [_hp, _i],
     "pmn_plan_launch": [_hp, _s],
     "pmn_plan_destroy": [_hp],
+    "pmn_view_scores": [_fp] * 6 + [_i, _i, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_double] * 3 + [_fp, _s],
 }
 
 # libpmn_hip_experimental.so only (include/pmn_hip_experimental.h; `make -C patchmatchnet_amd/csrc EXPERIMENTAL=1`)

@@ -932,3 +932,48 @@ class PointPacker:
         if any(x < 0 for x in c):
             raise PmnError("pack_points: the record buffer is too small for this scan")
         return c
+
+
+def view_scores(cam_centers: torch.Tensor, xyz: torch.Tensor, obs_ptr: torch.Tensor, obs_pt: torch.Tensor, trk_ptr: torch.Tensor,
+                trk_img: torch.Tensor, theta0: float, sigma1: float, sigma2: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pmn_view_scores: the N x N float64 view-selection scores of the COLMAP import (reference colmap_input.py:336-366).
+
+    cam_centers [N,3] float64, xyz [P,3] float64; per image its observations as CSR (obs_ptr [N+1] int64, obs_pt int32 dense point
+    indices in the image's order, untriangulated entries dropped, duplicates kept); per point its distinct observing images in
+    ascending order as CSR (trk_ptr [P+1] int64, trk_img int32).  patchmatchnet_amd/colmap.py builds them.  Returns score [N,N]
+    float64 (or fills ``out``) on the current stream; every entry is written, the diagonal is 0."""
+    specs = ((cam_centers, "cam_centers", torch.float64), (xyz, "xyz", torch.float64), (obs_ptr, "obs_ptr", torch.int64),
+             (obs_pt, "obs_pt", torch.int32), (trk_ptr, "trk_ptr", torch.int64), (trk_img, "trk_img", torch.int32))
+    for t, name, dtype in specs:
+        if not isinstance(t, torch.Tensor):
+            raise PmnError(f"{name}: expected a torch.Tensor")
+        if not t.is_cuda:
+            raise PmnError(f"{name}: tensor is on {t.device}; patchmatchnet_amd runs only on a ROCm GPU (no CPU fallback)")
+        if t.dtype != dtype:
+            raise PmnError(f"{name}: expected {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise PmnError(f"{name}: tensor must be contiguous")
+        if t.device != cam_centers.device:
+            raise PmnError(f"{name}: every input must be on {cam_centers.device}")
+    if cam_centers.dim() != 2 or cam_centers.shape[1] != 3 or cam_centers.shape[0] < 1:
+        raise PmnError("view_scores: cam_centers must be [N,3] with N >= 1")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise PmnError("view_scores: xyz must be [P,3]")
+    N, P = int(cam_centers.shape[0]), int(xyz.shape[0])
+    if obs_ptr.shape != (N + 1,) or trk_ptr.shape != (P + 1,) or obs_pt.dim() != 1 or trk_img.dim() != 1:
+        raise PmnError("view_scores: obs_ptr must be [N+1], trk_ptr [P+1], obs_pt and trk_img 1-D")
+    if N >= 2 ** 31 or P >= 2 ** 31:
+        raise PmnError("view_scores: more than 2^31 - 1 images or points")
+    if out is None:
+        out = torch.empty((N, N), dtype=torch.float64, device=cam_centers.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.shape == (N, N)
+              and out.device == cam_centers.device):
+        raise PmnError("view_scores: out must be a contiguous float64 [N,N] tensor on the inputs' device")
+    with torch.cuda.device(cam_centers.device):
+        check(_lib.lib().pmn_view_scores(cam_centers.data_ptr(), _ptr(xyz) if P else None, obs_ptr.data_ptr(),
+                                         obs_pt.data_ptr() if obs_pt.numel() else None, trk_ptr.data_ptr(),
+                                         trk_img.data_ptr() if trk_img.numel() else None, N, P, int(obs_pt.numel()),
+                                         int(trk_img.numel()), float(theta0), float(sigma1), float(sigma2), out.data_ptr(),
+                                         _stream(cam_centers)),
+              "pmn_view_scores")
+    return out
