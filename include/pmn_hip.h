@@ -10,7 +10,8 @@
  *   - all tensor arguments are DEVICE pointers to contiguous float32 buffers owned (and pre-allocated) by the
  *     caller; the library never allocates, never synchronises, and launches on `stream` (a hipStream_t; pass the
  *     caller's current stream, NULL = default stream);
- *     (exception: pmn_view_scores, the COLMAP import's view selection, takes float64 / int32 / int64 buffers, as declared);
+ *     (exceptions: pmn_view_scores, the COLMAP import's view selection, takes float64 / int32 / int64 buffers, and pmn_depth_metrics
+ *     writes float64 rows, as declared);
  *   - arguments named *_host are small HOST arrays (neighbour tables) copied into the kernel-argument segment;
  *   - returns PMN_OK (0) or a negative PMN_ERR_* code; nothing is launched when an argument check fails;
  *   - entry points never block: each one only ENQUEUES kernels (no hip*Synchronize, no hipMalloc / hipFree, no hipMemcpy /
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PMN_ABI_VERSION 23
+#define PMN_ABI_VERSION 24
 #define PMN_MLP_FLOATS 340
 #define PMN_MAX_DEPTH 64
 #define PMN_MAX_NEIGHBORS 17
@@ -356,6 +357,45 @@ int pmn_plan_destroy(void *plan);
 int pmn_view_scores(const double *cam_centers, const double *xyz, const long long *obs_ptr, const int *obs_pt,
                     const long long *trk_ptr, const int *trk_img, int N, int P, long long n_obs, long long n_trk,
                     double theta0, double sigma1, double sigma2, double *score, void *stream);
+
+/* ABI 24.  Ground-truth depth metrics of validation (train.py --mode test; reference train.py:127-181, utils.py:170-221,
+ * models/net.py:321-342), for one batch: one row of RAW float64 sums and exact counts per sample, from which the host forms the
+ * reference's loss, depth-error-stage-i and threshold-{t}mm-error (patchmatchnet_amd/validate.py).
+ *   depth_gt [B][H][W] float32, depth_min [B] float32: the valid pixels of stage 0 are depth_gt >= depth_min[b] (IEEE: NaN is not valid);
+ *     stage s reads the nearest down-sampling gt[y << s][x << s] and its mask, as F.interpolate(scale_factor=2^-s, mode="nearest");
+ *   maps_host: HOST array of DEVICE pointers, stage-major: stage s contributes iters_host[s] maps (1..PMN_METRICS_MAX_ITERS) of
+ *     [B][H >> s][W >> s] float32 each, in iteration order -- depth_patchmatch of the forward, stage 0 = the refined map;
+ *   hw_host: HOST int[2 * stages], each stage's map height and width; anything but floor(H / 2^s) x floor(W / 2^s), or an empty stage,
+ *     is PMN_ERR_SHAPE (the model's maps of an image whose sides are not multiples of 8 are not down-samplings of its ground truth);
+ *   thresholds_host: HOST float[n_thresholds], n_thresholds <= PMN_METRICS_MAX_THRESHOLDS (the reference uses 1, 2, 4, 8).
+ * Row of sample b (rows [B][PMN_METRICS_ROW] float64; entries of absent stages / iterations / thresholds are 0):
+ *   [PMN_METRICS_COUNT + s]                           valid pixels of stage s
+ *   [PMN_METRICS_ABS + s]                             sum |d - gt| over them, d = the LAST map of stage s
+ *   [PMN_METRICS_THR + t]                             count of |d - gt| > thresholds[t] at stage 0 (last map)
+ *   [PMN_METRICS_SL1 + s * PMN_METRICS_MAX_ITERS + k] sum smooth-L1(d - gt), beta = 1, of iteration k of stage s
+ * Per element fp32 as torch computes it (z = |d - gt|; z < 1 ? 0.5 * z * z : z - 0.5), a NaN estimate is not above any threshold but
+ * makes the sums NaN, the sums are fp64.  scratch: DEVICE float64 of at least PMN_METRICS_SCRATCH(B, H, W) elements (per-workgroup
+ * partial rows; the caller owns it, nothing needs zeroing).  Two launches: the partial rows, then their sum in workgroup order --
+ * deterministic, the same bits on every run and stream. */
+#define PMN_METRICS_MAX_STAGES 4
+#define PMN_METRICS_MAX_ITERS 5
+#define PMN_METRICS_MAX_THRESHOLDS 8
+#define PMN_METRICS_COUNT 0
+#define PMN_METRICS_ABS 4
+#define PMN_METRICS_THR 8
+#define PMN_METRICS_SL1 16
+#define PMN_METRICS_ROW 36
+#define PMN_METRICS_PIXELS_PER_BLOCK 4096
+#define PMN_METRICS_MAX_BLOCKS 128
+/* workgroups per sample: ceil(H * W / PMN_METRICS_PIXELS_PER_BLOCK), at most PMN_METRICS_MAX_BLOCKS */
+#define PMN_METRICS_BLOCKS(H, W)                                                                                                     \
+    ((int)((((long long)(H) * (W) + PMN_METRICS_PIXELS_PER_BLOCK - 1) / PMN_METRICS_PIXELS_PER_BLOCK) > PMN_METRICS_MAX_BLOCKS        \
+               ? PMN_METRICS_MAX_BLOCKS                                                                                               \
+               : (((long long)(H) * (W) + PMN_METRICS_PIXELS_PER_BLOCK - 1) / PMN_METRICS_PIXELS_PER_BLOCK)))
+#define PMN_METRICS_SCRATCH(B, H, W) ((long long)(B) * PMN_METRICS_BLOCKS(H, W) * PMN_METRICS_ROW)
+int pmn_depth_metrics(const float *depth_gt, const float *depth_min, const float *const *maps_host, const int *iters_host,
+                      const int *hw_host, int stages, const float *thresholds_host, int n_thresholds, int B, int H, int W,
+                      double *scratch, long long scratch_doubles, double *rows, void *stream);
 
 #ifdef __cplusplus
 }

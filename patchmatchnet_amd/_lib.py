@@ -13,7 +13,7 @@ from typing import Optional
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "libpmn_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 MLP_FLOATS = 340
 MAX_DEPTH = 64
 MAX_NEIGHBORS = 17
@@ -67,7 +67,22 @@ SIGNATURES = {
     "pmn_plan_launch": [_hp, _s],
     "pmn_plan_destroy": [_hp],
     "pmn_view_scores": [_fp] * 6 + [_i, _i, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_double] * 3 + [_fp, _s],
+    "pmn_depth_metrics": [_fp, _fp, _hp, _hp, _hp, _i, _hp, _i, _i, _i, _i, _fp, ctypes.c_longlong, _fp, _s],
 }
+
+# pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)
+METRICS_MAX_STAGES = 4
+METRICS_MAX_ITERS = 5
+METRICS_MAX_THRESHOLDS = 8
+METRICS_COUNT, METRICS_ABS, METRICS_THR, METRICS_SL1 = 0, 4, 8, 16
+METRICS_ROW = 36
+METRICS_PIXELS_PER_BLOCK = 4096
+METRICS_MAX_BLOCKS = 128
+
+
+def metrics_scratch(B: int, H: int, W: int) -> int:
+    """PMN_METRICS_SCRATCH(B, H, W): float64 elements of pmn_depth_metrics' per-workgroup partial rows."""
+    return B * min(METRICS_MAX_BLOCKS, -(-H * W // METRICS_PIXELS_PER_BLOCK)) * METRICS_ROW
 
 # libpmn_hip_experimental.so only (include/pmn_hip_experimental.h; `make -C patchmatchnet_amd/csrc EXPERIMENTAL=1`)
 EXPERIMENTAL_SIGNATURES = {"pmn_set_tuning": [_i, _i],

@@ -348,6 +348,52 @@ class PlannedForward(GraphedForward):
             _lib.check(_lib.lib().pmn_plan_launch(handle.plan, torch.cuda.current_stream(dev).cuda_stream), "pmn_plan_launch")
 
 
+class PlannedValidationForward(PlannedForward):
+    """PlannedForward whose recorded run ends with the ground-truth metrics of its maps (train.py --mode test --hip_graph 1): ONE
+    pmn_plan_launch covers the forward and pmn_depth_metrics over its depth_patchmatch maps.
+
+    ``PlannedValidationForward(model, thresholds)(images, intrinsics, extrinsics, depth_min, depth_max, depth_gt)`` -> (depth,
+    confidence, rows [B, _lib.METRICS_ROW] float64): static outputs, overwritten by the next call of the same signature.  The ground
+    truth [B,1,H,W] and depth_min are copied into static buffers of their own (one pair per ground-truth shape, kept as long as this
+    object, since the plans of that shape hold their addresses).  Sides that are not multiples of 8 are refused: the forward would run
+    eagerly (PlannedForward) and its stage maps are not down-samplings of the ground truth anyway (ops.depth_metrics)."""
+
+    def __init__(self, model, thresholds: Sequence[float], max_graphs: int = 8) -> None:
+        super().__init__(model, max_graphs=max_graphs)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        self._truth: Dict[Tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._current: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+
+    def __call__(self, images: List[torch.Tensor], intrinsics: torch.Tensor, extrinsics: torch.Tensor,  # type: ignore[override]
+                 depth_min: torch.Tensor, depth_max: torch.Tensor, depth_gt: torch.Tensor):
+        h, w = images[0].shape[-2:]
+        if h % 8 or w % 8:
+            raise PmnError(f"PlannedValidationForward: {h}x{w} images -- the stage maps are down-samplings of the ground truth only "
+                           "when height and width are multiples of 8")
+        key = (tuple(depth_gt.shape), depth_gt.device)
+        bufs = self._truth.get(key)
+        if bufs is None:
+            bufs = self._truth[key] = (torch.empty(tuple(depth_gt.shape), dtype=torch.float32, device=depth_gt.device),
+                                       torch.empty(tuple(depth_min.shape), dtype=torch.float32, device=depth_gt.device))
+        bufs[0].copy_(depth_gt, non_blocking=True)
+        bufs[1].copy_(depth_min, non_blocking=True)
+        self._current = bufs
+        return super().__call__(images, intrinsics, extrinsics, depth_min, depth_max)
+
+    def _record(self, run, dev):
+        from . import ops
+        depth_gt, depth_min = self._current
+        held = {}
+
+        def run_scored():
+            depth, confidence, maps = run()
+            held["rows"] = ops.depth_metrics(depth_gt, depth_min, maps, self.thresholds)  # the recording pass's rows: pool memory
+            return depth, confidence, maps
+
+        handle, (depth, confidence) = super()._record(run_scored, dev)
+        return handle, (depth, confidence, held["rows"])
+
+
 class _Plan:
     """Owns one pmn_plan and the torch memory pool its recorded addresses live in."""
 

@@ -13,15 +13,18 @@ from typing import Dict, List, Tuple
 import numpy as np
 from torch.utils.data import Dataset
 
-from .data_io import image_shape, read_cam_file, read_image, read_image_u8, read_pair_file
+from .data_io import image_shape, read_cam_file, read_image, read_image_u8, read_map, read_pair_file
 
 
 class MVSDataset(Dataset):
     def __init__(self, data_path: str, num_views: int = 10, max_dim: int = -1, scan_list: str = "",
                  num_light_idx: int = -1, cam_folder: str = "cams", pair_path: str = "pair.txt",
-                 image_folder: str = "images", image_extension: str = ".jpg") -> None:
+                 image_folder: str = "images", image_extension: str = ".jpg", depth_folder: str = "depth_gt",
+                 load_depth_gt: bool = False) -> None:
         super().__init__()
         self.data_path, self.num_views, self.max_dim = data_path, num_views, max_dim
+        # load_depth_gt (train.py --mode test, off for eval.py): samples gain the reference view's ground truth and mask
+        self.depth_folder, self.load_depth_gt = depth_folder, load_depth_gt
         self.cam_folder, self.image_folder, self.image_extension = cam_folder, image_folder, image_extension
         self.load_images = True  # False: samples carry cameras and image SHAPES only (eval.py's encode-once path)
         self.uint8_images = False  # True: images that need no down-scaling come as uint8 [3,H,W]; the consumer divides by 255
@@ -77,6 +80,13 @@ class MVSDataset(Dataset):
             out.setdefault((scan, light), []).append(i)
         return out
 
+    def depth_gt_path(self, scan: str, vid: int) -> str:
+        return os.path.join(self.data_path, scan, self.depth_folder, "{:0>8}.pfm".format(vid))
+
+    def missing_depth_gt(self) -> List[Tuple[str, int]]:
+        """(scan, reference view) of every sample without a ground-truth file, in sample order."""
+        return [(scan, ref) for scan, _, ref, _ in self.metas if not os.path.isfile(self.depth_gt_path(scan, ref))]
+
     def views_of(self, indices: List[int]) -> List[int]:
         """Every view id the given samples read (reference + the source views actually used), sorted."""
         ids = set()
@@ -116,10 +126,23 @@ class MVSDataset(Dataset):
             extrinsics.append(E)
             if i == 0:
                 depth_min, depth_max = depth_params[0], depth_params[1]
-        return {"images": images, "intrinsics": np.stack(intrinsics), "extrinsics": np.stack(extrinsics),
-                "depth_min": depth_min, "depth_max": depth_max, "ref_view": view_ids[0],
-                "view_ids": np.asarray(view_ids, np.int64), "scan": scan, "light": light,
-                "filename": os.path.join(scan, "{}", "{:0>8}".format(view_ids[0]) + "{}")}
+        sample = {"images": images, "intrinsics": np.stack(intrinsics), "extrinsics": np.stack(extrinsics),
+                  "depth_min": depth_min, "depth_max": depth_max, "ref_view": view_ids[0],
+                  "view_ids": np.asarray(view_ids, np.int64), "scan": scan, "light": light,
+                  "filename": os.path.join(scan, "{}", "{:0>8}".format(view_ids[0]) + "{}")}
+        if self.load_depth_gt:
+            sample["depth_gt"], sample["mask"] = self.read_depth_gt(scan, view_ids[0], depth_min)
+        return sample
+
+    def read_depth_gt(self, scan: str, vid: int, depth_min) -> Tuple[np.ndarray, np.ndarray]:
+        """Ground truth of a reference view as the reference reads it (datasets/mvs.py:88-97): ``read_map(path, max_dim)`` as
+        [1,H,W] float32 and ``mask = depth_gt >= depth_min`` [1,H,W] bool (depth_min: the float32 the camera file parses to); the
+        reference's empty arrays when the file does not exist."""
+        path = self.depth_gt_path(scan, vid)
+        if not os.path.isfile(path):
+            return np.empty(0), np.empty(0)
+        depth_gt = np.ascontiguousarray(read_map(path, self.max_dim).transpose([2, 0, 1]), np.float32)
+        return depth_gt, depth_gt >= depth_min
 
 
 class MVSViewDataset(Dataset):

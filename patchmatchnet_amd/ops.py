@@ -977,3 +977,78 @@ def view_scores(cam_centers: torch.Tensor, xyz: torch.Tensor, obs_ptr: torch.Ten
                                          _stream(cam_centers)),
               "pmn_view_scores")
     return out
+
+
+def depth_metrics(depth_gt: torch.Tensor, depth_min: torch.Tensor, depth_patchmatch, thresholds: Sequence[float] = (1.0, 2.0, 4.0, 8.0),
+                  out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pmn_depth_metrics: per sample one row of raw float64 sums and exact counts against the ground truth (train.py --mode test;
+    reference train.py:127-181).  Row layout: include/pmn_hip.h (PMN_METRICS_*; _lib.METRICS_*); patchmatchnet_amd/validate.py turns
+    rows into the reference's scalars.
+
+    depth_gt [B,H,W] or [B,1,H,W] float32, depth_min [B] float32; depth_patchmatch = the forward's {stage: [maps]} (or a list in stage
+    order): stage 0 the refined [B,1,H,W], stage s its iterations at [B,1,H>>s,W>>s].  Returns rows [B, _lib.METRICS_ROW] float64 (or
+    fills ``out``) on the current stream, without a synchronisation; ``scratch`` (float64, at least _lib.metrics_scratch(B,H,W)) is
+    allocated when not given."""
+    _dev(depth_gt, "depth_gt")
+    _dev(depth_min, "depth_min")
+    if depth_gt.dim() == 4 and depth_gt.shape[1] == 1:
+        depth_gt = depth_gt.view(depth_gt.shape[0], depth_gt.shape[2], depth_gt.shape[3])
+    if depth_gt.dim() != 3:
+        raise PmnError(f"depth_metrics: depth_gt must be [B,H,W] or [B,1,H,W], got {tuple(depth_gt.shape)}")
+    B, H, W = (int(x) for x in depth_gt.shape)
+    if tuple(depth_min.shape) != (B,):
+        raise PmnError(f"depth_metrics: depth_min must be [{B}], got {tuple(depth_min.shape)}")
+    stages = [depth_patchmatch[s] for s in sorted(depth_patchmatch)] if isinstance(depth_patchmatch, dict) else list(depth_patchmatch)
+    if isinstance(depth_patchmatch, dict) and sorted(depth_patchmatch) != list(range(len(stages))):
+        raise PmnError(f"depth_metrics: depth_patchmatch must hold stages 0..n-1, got {sorted(depth_patchmatch)}")
+    if not 1 <= len(stages) <= _lib.METRICS_MAX_STAGES:
+        raise PmnError(f"depth_metrics: 1 to {_lib.METRICS_MAX_STAGES} stages, got {len(stages)}")
+    thresholds = [float(t) for t in thresholds]
+    if len(thresholds) > _lib.METRICS_MAX_THRESHOLDS:
+        raise PmnError(f"depth_metrics: at most {_lib.METRICS_MAX_THRESHOLDS} thresholds, got {len(thresholds)}")
+    maps, iters, hw = [], [], []
+    for s, ms in enumerate(stages):
+        ms = list(ms)
+        if not 1 <= len(ms) <= _lib.METRICS_MAX_ITERS:
+            raise PmnError(f"depth_metrics: stage {s} has {len(ms)} maps; 1 to {_lib.METRICS_MAX_ITERS} are supported")
+        shape = None
+        for k, m in enumerate(ms):
+            _dev(m, f"depth_patchmatch[{s}][{k}]")
+            if m.device != depth_gt.device:
+                raise PmnError(f"depth_patchmatch[{s}][{k}]: on {m.device}, the ground truth on {depth_gt.device}")
+            sh = tuple(m.shape)
+            if len(sh) == 4 and sh[1] == 1:
+                sh = (sh[0], sh[2], sh[3])
+            if len(sh) != 3 or sh[0] != B or (shape is not None and sh != shape):
+                raise PmnError(f"depth_metrics: depth_patchmatch[{s}][{k}] is {tuple(m.shape)}; expected [{B},1,h,w] like the stage's "
+                               "other maps")
+            shape = sh
+            maps.append(m.data_ptr())
+        if shape[1:] != (H >> s, W >> s) or min(shape[1:]) < 1:
+            raise PmnError(f"depth_metrics: the stage-{s} maps are {shape[1]}x{shape[2]}, the nearest down-sampling of the {H}x{W} "
+                           f"ground truth is {H >> s}x{W >> s} (the model's stage maps match it only when H and W are multiples of "
+                           f"{1 << (len(stages) - 1)})")
+        iters.append(len(ms))
+        hw += [shape[1], shape[2]]
+    if out is None:
+        out = torch.empty((B, _lib.METRICS_ROW), dtype=torch.float64, device=depth_gt.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, _lib.METRICS_ROW)
+              and out.device == depth_gt.device):
+        raise PmnError(f"depth_metrics: out must be a contiguous float64 [{B},{_lib.METRICS_ROW}] tensor on the ground truth's device")
+    need = _lib.metrics_scratch(B, H, W)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float64, device=depth_gt.device)
+    elif not (scratch.is_cuda and scratch.dtype == torch.float64 and scratch.is_contiguous() and scratch.numel() >= need
+              and scratch.device == depth_gt.device):
+        raise PmnError(f"depth_metrics: scratch must be a contiguous float64 tensor of at least {need} elements on the same device")
+    maps_h = (ctypes.c_void_p * len(maps))(*maps)
+    iters_h = (ctypes.c_int * len(iters))(*iters)
+    hw_h = (ctypes.c_int * len(hw))(*hw)
+    thr_h = (ctypes.c_float * max(len(thresholds), 1))(*thresholds)
+    with torch.cuda.device(depth_gt.device):
+        check(_lib.lib().pmn_depth_metrics(depth_gt.data_ptr(), depth_min.data_ptr(), ctypes.cast(maps_h, ctypes.c_void_p),
+                                           ctypes.cast(iters_h, ctypes.c_void_p), ctypes.cast(hw_h, ctypes.c_void_p), len(stages),
+                                           ctypes.cast(thr_h, ctypes.c_void_p), len(thresholds), B, H, W, scratch.data_ptr(),
+                                           int(scratch.numel()), out.data_ptr(), _stream(depth_gt)),
+              "pmn_depth_metrics")
+    return out
