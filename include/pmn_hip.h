@@ -10,8 +10,9 @@
  *   - all tensor arguments are DEVICE pointers to contiguous float32 buffers owned (and pre-allocated) by the
  *     caller; the library never allocates, never synchronises, and launches on `stream` (a hipStream_t; pass the
  *     caller's current stream, NULL = default stream);
- *     (exceptions: pmn_view_scores, the COLMAP import's view selection, takes float64 / int32 / int64 buffers, and pmn_depth_metrics
- *     writes float64 rows, as declared);
+ *     (exceptions: pmn_view_scores, the COLMAP import's view selection, takes float64 / int32 / int64 buffers, pmn_depth_metrics
+ *     writes float64 rows, and the point-cloud searches pmn_nn_distance / pmn_reduce_round take int64 keys, int32 / uint8 / uint32
+ *     state and write float64 distances, as declared);
  *   - arguments named *_host are small HOST arrays (neighbour tables) copied into the kernel-argument segment;
  *   - returns PMN_OK (0) or a negative PMN_ERR_* code; nothing is launched when an argument check fails;
  *   - entry points never block: each one only ENQUEUES kernels (no hip*Synchronize, no hipMalloc / hipFree, no hipMemcpy /
@@ -39,7 +40,7 @@
 extern "C" {
 #endif
 
-#define PMN_ABI_VERSION 24
+#define PMN_ABI_VERSION 25
 #define PMN_MLP_FLOATS 340
 #define PMN_MAX_DEPTH 64
 #define PMN_MAX_NEIGHBORS 17
@@ -396,6 +397,45 @@ int pmn_view_scores(const double *cam_centers, const double *xyz, const long lon
 int pmn_depth_metrics(const float *depth_gt, const float *depth_min, const float *const *maps_host, const int *iters_host,
                       const int *hw_host, int stages, const float *thresholds_host, int n_thresholds, int B, int H, int W,
                       double *scratch, long long scratch_doubles, double *rows, void *stream);
+
+/* ABI 25.  The two searches of the DTU point-cloud score (reference evaluations/dtu/MaxDistCP.m and reducePts_haa.m, MATLAB KD-trees on
+ * the CPU; patchmatchnet_amd/pointcloud.py and eval_dtu.py are the callers).  Both read a UNIFORM GRID OVER SORTED POINTS that the caller
+ * builds (pointcloud.build_grid):
+ *   origin_host HOST double[3], cell > 0, dims_host HOST int[3] (1 .. 2^30 each, product < 2^62, else PMN_ERR_SHAPE);
+ *   a point's cell along an axis is floor((double(p) - origin) / cell), 0 <= cell index < dims, its key
+ *   (cz * dims[1] + cy) * dims[0] + cx;  xyz [n][3] float32 and keys [n] int64 hold the points and their keys in ASCENDING KEY ORDER.
+ *   There is no cell table: x is the fastest axis of the key, so a row of cells is one contiguous range of the sorted points, found by
+ *   binary search over the keys, and the memory of a grid does not depend on its extent.
+ * Every distance is sqrt(dx*dx + dy*dy + dz*dz) of the float32 coordinates widened to float64, products and sums in float64 in x, y, z
+ * order, no fused multiply-add; "nearest" and "within dst" are decided on that value.  Non-finite coordinates are the caller's error
+ * (the Python layer counts and rejects them).  n, n_to, n_from: 1 .. 2^31 - 65.
+ *
+ * pmn_nn_distance: for each of the n_from query points ([n_from][3] float32, any position, inside the grid or not) the distance to the
+ * nearest of the n_to grid points, capped: dist[q] = min(d, max_dist) (float64 [n_from], indexed as `query`).  index, if not NULL
+ * (int32 [n_from]), receives the position IN THE SORTED ORDER of a nearest point, -1 where the result is the cap (tests use it).
+ * order, if not NULL (int32 [n_from], a permutation), is the sequence in which queries are taken: pass the queries' own cell order so
+ * that the lanes of a wave walk the same cells (any order gives the same output).  The search visits the query's cell, then shells of
+ * growing Chebyshev radius, and ends when the best distance is no larger than the distance to the nearest face of the next shell or the
+ * shell lies beyond max_dist.  The kernel knows nothing of DTU: MaxDistCP.m's 60-unit blocks are applied by the caller, and where the
+ * MATLAB (which searches only the to-points of the block grown by MaxDist and does not clamp) returns some value >= MaxDist for a point
+ * with no neighbour within MaxDist, this returns MaxDist.  Every consumer keeps only distances < 20, so no score can differ.
+ * One launch of ceil(n_from / 64) one-wave workgroups.
+ *
+ * pmn_reduce_round: one round of the parallel form of reducePts_haa.m (visit the points in a given order; a point still kept removes
+ * every point within dst, distance <= dst, and stays: the greedy maximal independent set of that order).  rank [n] int32: the position
+ * of each SORTED point in the visiting order (a permutation of 0..n-1).  state [n] uint8, zeroed by the caller before the first round:
+ * 0 undecided, 1 kept, 2 removed.  In a round every undecided point scans its neighbours within dst: it becomes removed if one of lower
+ * rank is kept, kept if every one of lower rank is removed, and otherwise stays undecided.  state is updated IN PLACE and only ever
+ * leaves 0: a decision rests on neighbours' final states alone, so reading a neighbour before or after it was decided in the same round
+ * changes when a point is decided, never what it becomes.  The number of points still undecided after the round is ADDED to *counter
+ * (uint32, zeroed by the caller; one atomicAdd per wave).  The caller launches rounds until a round adds zero; the fixed point is the
+ * sequential greedy set of the order, the same bits on every run.  Identical points (distance 0) are neighbours like any others.
+ * dst >= 0; dst / cell above 1024 is PMN_ERR_SHAPE (cells of about 2 dst keep the candidate lists short). */
+int pmn_nn_distance(const float *to_xyz, const long long *to_keys, long long n_to, const double *origin_host, double cell,
+                    const int *dims_host, const float *query, const int *order, long long n_from, double max_dist, double *dist,
+                    int *index, void *stream);
+int pmn_reduce_round(const float *xyz, const long long *keys, long long n, const double *origin_host, double cell,
+                     const int *dims_host, double dst, const int *rank, unsigned char *state, unsigned int *counter, void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ from typing import Optional
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "libpmn_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 MLP_FLOATS = 340
 MAX_DEPTH = 64
 MAX_NEIGHBORS = 17
@@ -68,6 +68,9 @@ SIGNATURES = {
     "pmn_plan_destroy": [_hp],
     "pmn_view_scores": [_fp] * 6 + [_i, _i, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_double] * 3 + [_fp, _s],
     "pmn_depth_metrics": [_fp, _fp, _hp, _hp, _hp, _i, _hp, _i, _i, _i, _i, _fp, ctypes.c_longlong, _fp, _s],
+    "pmn_nn_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, ctypes.c_double, _fp, _ip,
+                        _s],
+    "pmn_reduce_round": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, ctypes.c_double, _ip, _ip, _ip, _s],
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)

@@ -1,0 +1,361 @@
+"""DTU accuracy / completeness of a fused point cloud on the device (reference evaluations/dtu/BaseEvalMain_web.m,
+PointCompareMain.m, MaxDistCP.m, reducePts_haa.m, ComputeStat_web.m -- MATLAB with CPU KD-trees).
+
+The two searches are HIP kernels (csrc/pointcloud.hip): pmn_reduce_round, the greedy 0.2-unit reduction of the method's cloud, and
+pmn_nn_distance, the nearest-neighbour distance in both directions.  Both read a uniform grid over sorted points; building it is
+plumbing and uses torch on the device (cell coordinates -> 63-bit key -> torch.sort), as are the masks and the statistics (a gather
+from the ObsMask volume, a dot product, boolean selects, one sort for the median, float64 sums: a few elementwise launches per scan).
+There is no CPU path: the searches refuse host tensors.
+
+Semantics: every distance is sqrt(dx*dx + dy*dy + dz*dz) of the float32 PLY coordinates widened to float64; the visiting
+order of the reduction is an explicit, seeded permutation (the MATLAB draws an unseeded randperm), and for a given order the result is
+the sequential greedy set exactly; nn_distance returns min(d, max_dist) where MaxDistCP.m returns some value >= MaxDist (the one stated
+deviation: every consumer keeps only distances < 20).
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import time
+from typing import Dict, NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import PmnError, check
+
+# defaults chosen from the sweep recorded in DESIGN.md 13
+NN_CELL = 2.0          # cell of the nearest-neighbour grids, in scene units (DTU: millimetres)
+REDUCE_CELL_RATIO = 2  # cell of the reduction's grid = REDUCE_CELL_RATIO * dst
+ROUNDS_PER_READ = 4    # rounds of the reduction enqueued between two reads of the undecided counters
+
+
+# ---- files --------------------------------------------------------------------------------------------------------------------
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply_vertices(path: str) -> np.ndarray:
+    """The ``vertex`` element of a PLY as [n,3] float32 (x, y, z).  binary_little_endian, binary_big_endian or ascii; other scalar
+    vertex properties (colours, normals) are skipped; elements after ``vertex`` (faces) are ignored.  Reads what fusion.write_ply
+    writes and DTU's Points/stl/stl%03d_total.ply.  ValueError (naming the file) for a list property inside ``vertex``, a missing
+    x / y / z, or an element before ``vertex`` (its size would have to be parsed to find the vertices)."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, count, props, element, before = None, None, [], None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: PLY header has no end_header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                element = tok[1]
+                if element == "vertex":
+                    count = int(tok[2])
+                elif count is None:
+                    before.append(element)
+            elif tok[0] == "property" and element == "vertex":
+                if tok[1] == "list":
+                    raise ValueError(f"{path}: list property {tok[-1]!r} inside the vertex element is not supported")
+                if tok[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: unknown property type {tok[1]!r}")
+                props.append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == "end_header":
+                break
+        if count is None:
+            raise ValueError(f"{path}: no vertex element")
+        if before:
+            raise ValueError(f"{path}: element {before[0]!r} precedes vertex")
+        names = [p[0] for p in props]
+        for axis in "xyz":
+            if axis not in names:
+                raise ValueError(f"{path}: the vertex element has no property {axis!r}")
+        if fmt == "ascii":
+            cols = [names.index(a) for a in "xyz"]
+            rows = np.loadtxt(f, dtype=np.float64, max_rows=count, usecols=cols, ndmin=2) if count else np.zeros((0, 3))
+            if len(rows) != count:
+                raise ValueError(f"{path}: {len(rows)} vertices where the header says {count}")
+            return np.ascontiguousarray(rows, np.float32)
+        if fmt not in ("binary_little_endian", "binary_big_endian"):
+            raise ValueError(f"{path}: unknown PLY format {fmt!r}")
+        end = "<" if fmt == "binary_little_endian" else ">"
+        rec = np.fromfile(f, dtype=np.dtype([(n, end + t) for n, t in props]), count=count)
+        if len(rec) != count:
+            raise ValueError(f"{path}: {len(rec)} vertices where the header says {count}")
+    return np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32)
+
+
+def _load_fields(path: str, fields) -> Dict[str, np.ndarray]:
+    if not os.path.isfile(path):
+        raise FileNotFoundError(path)
+    if path.endswith(".npz"):
+        with np.load(path) as z:
+            missing = [k for k in fields if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: no field {missing[0]!r}")
+            return {k: z[k] for k in fields}
+    try:
+        import scipy.io
+    except ImportError as e:
+        raise PmnError(f"{path}: reading .mat files needs scipy (scipy.io.loadmat); convert the file to .npz with the same field "
+                       f"names ({', '.join(fields)}) to do without it") from e
+    m = scipy.io.loadmat(path, variable_names=list(fields))
+    missing = [k for k in fields if k not in m]
+    if missing:
+        raise ValueError(f"{path}: no field {missing[0]!r}")
+    return {k: m[k] for k in fields}
+
+
+def load_obs_mask(path: str) -> Tuple[np.ndarray, np.ndarray, float]:
+    """ObsMask/ObsMask<scan>_10.mat (or an .npz with the same field names) -> (ObsMask bool [s1,s2,s3], BB float64 [2,3], Res)."""
+    m = _load_fields(path, ("ObsMask", "BB", "Res"))
+    obs = np.asarray(m["ObsMask"]).astype(bool)
+    bb = np.asarray(m["BB"], np.float64)
+    if obs.ndim != 3 or bb.shape != (2, 3):
+        raise ValueError(f"{path}: ObsMask must be 3-D and BB 2x3, got {obs.shape} and {bb.shape}")
+    return obs, bb, float(np.asarray(m["Res"], np.float64).reshape(-1)[0])
+
+
+def load_plane(path: str) -> np.ndarray:
+    """ObsMask/Plane<scan>.mat (or .npz): P, the 4 plane coefficients, float64 [4]."""
+    p = np.asarray(_load_fields(path, ("P",))["P"], np.float64).reshape(-1)
+    if p.shape != (4,):
+        raise ValueError(f"{path}: P must have 4 entries, got {p.shape}")
+    return p
+
+
+# ---- grid -----------------------------------------------------------------------------------------------------------------------
+
+class Grid(NamedTuple):
+    """Uniform grid over sorted points (layout: include/pmn_hip.h, ABI 25)."""
+    xyz: torch.Tensor     # [n,3] float32, ascending key order
+    keys: torch.Tensor    # [n] int64
+    perm: torch.Tensor    # [n] int64: xyz == points[perm]
+    origin: Tuple[float, float, float]
+    cell: float
+    dims: Tuple[int, int, int]
+
+
+def _points(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise PmnError(f"{name}: expected a torch.Tensor")
+    if not t.is_cuda:
+        raise PmnError(f"{name}: tensor is on {t.device}; patchmatchnet_amd runs only on a ROCm GPU (no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise PmnError(f"{name}: expected float32, got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+        raise PmnError(f"{name}: expected a contiguous [n,3] tensor, got {tuple(t.shape)}")
+    if t.shape[0] < 1 or t.shape[0] >= 2 ** 31 - 64:
+        raise PmnError(f"{name}: between 1 and 2^31 - 65 points, got {t.shape[0]}")
+    bad = int((~torch.isfinite(t)).any(1).sum())
+    if bad:
+        raise PmnError(f"{name}: {bad} points have non-finite coordinates")
+    return t
+
+
+def _cells(points: torch.Tensor, origin, cell: float) -> torch.Tensor:
+    """floor((double(p) - origin) / cell), int64 [n,3]: the expression of the kernels (csrc/pointcloud.hip pc_cell)."""
+    o = torch.tensor(origin, dtype=torch.float64, device=points.device)
+    return torch.floor((points.double() - o) / cell).clamp_(-2.0 ** 30, 2.0 ** 30).long()
+
+
+def build_grid(points: torch.Tensor, cell: float, origin=None) -> Grid:
+    """Sorts ``points`` ([n,3] float32 on the device) into the cells of a uniform grid of side ``cell`` whose corner is ``origin``
+    (default: the per-axis minimum of the points; a given origin must not exceed it)."""
+    points = _points(points, "points")
+    cell = float(cell)
+    if not (cell > 0.0 and np.isfinite(cell)):
+        raise PmnError(f"build_grid: cell must be positive and finite, got {cell}")
+    lo = points.min(0).values.double().cpu().numpy()
+    origin = lo if origin is None else np.asarray(origin, np.float64).reshape(3)
+    if not np.isfinite(origin).all() or (origin > lo).any():
+        raise PmnError(f"build_grid: origin {origin.tolist()} must be finite and not above the points' minimum {lo.tolist()}")
+    c = _cells(points, origin.tolist(), cell)
+    dims = (c.max(0).values + 1).cpu().tolist()
+    if max(dims) > 2 ** 30 or dims[0] * dims[1] * dims[2] >= 2 ** 62:
+        raise PmnError(f"build_grid: a grid of {dims} cells does not fit a 63-bit key (PMN_ERR_SHAPE); use a larger cell")
+    keys = (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
+    keys, perm = torch.sort(keys)
+    return Grid(points[perm].contiguous(), keys, perm, tuple(float(v) for v in origin), cell, tuple(int(d) for d in dims))
+
+
+def _grid_args(g: Grid):
+    return (g.xyz.data_ptr(), g.keys.data_ptr(), int(g.xyz.shape[0]), (ctypes.c_double * 3)(*g.origin), float(g.cell),
+            (ctypes.c_int * 3)(*g.dims))
+
+
+def _stream(t: torch.Tensor) -> int:
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def nn_distance(query: torch.Tensor, grid: Grid, max_dist: float, return_index: bool = False):
+    """pmn_nn_distance: float64 [n] distance from every query point to the nearest point of ``grid``, capped at ``max_dist``.
+    ``return_index``: also int64 [n], the index into the points ``grid`` was built from (-1 where the result is the cap)."""
+    query = _points(query, "query")
+    if query.device != grid.xyz.device:
+        raise PmnError(f"nn_distance: query is on {query.device}, the grid on {grid.xyz.device}")
+    if not (max_dist > 0.0 and np.isfinite(max_dist)):
+        raise PmnError(f"nn_distance: max_dist must be positive and finite, got {max_dist}")
+    n = int(query.shape[0])
+    # queries are taken in the order of their own cells: the lanes of a wave then walk the same cells
+    qc = _cells(query, grid.origin, grid.cell).clamp_(-1, max(grid.dims))
+    side = max(grid.dims) + 2
+    order = torch.argsort(((qc[:, 2] + 1) * side + (qc[:, 1] + 1)) * side + (qc[:, 0] + 1)).int()
+    dist = torch.empty(n, dtype=torch.float64, device=query.device)
+    index = torch.empty(n, dtype=torch.int32, device=query.device) if return_index else None
+    with torch.cuda.device(query.device):
+        check(_lib.lib().pmn_nn_distance(*_grid_args(grid), query.data_ptr(), order.data_ptr(), n, float(max_dist), dist.data_ptr(),
+                                         index.data_ptr() if return_index else None, _stream(query)), "pmn_nn_distance")
+    if not return_index:
+        return dist
+    idx = index.long()
+    return dist, torch.where(idx >= 0, grid.perm[idx.clamp_min(0)], idx)
+
+
+def reduce_points(points: torch.Tensor, dst: float, order=None, seed: int = 0, cell: Optional[float] = None,
+                  return_rounds: bool = False):
+    """reducePts_haa.m on the device: bool [n], the greedy maximal set of points no two of which are within ``dst`` (<=) of each
+    other, for the visiting order ``order`` (a permutation of 0..n-1, tensor or array; default: numpy's default_rng(seed)
+    permutation, drawn on the host).  The result is the sequential greedy set of that order, bit for bit, on every run.
+    ``cell``: the grid's cell (default REDUCE_CELL_RATIO * dst)."""
+    points = _points(points, "points")
+    n = int(points.shape[0])
+    dst = float(dst)
+    if not (dst >= 0.0 and np.isfinite(dst)):
+        raise PmnError(f"reduce_points: dst must be finite and >= 0, got {dst}")
+    if order is None:
+        order = np.random.default_rng(seed).permutation(n)
+    order = torch.as_tensor(np.asarray(order.cpu()) if isinstance(order, torch.Tensor) else np.asarray(order)).long().to(points.device)
+    if order.shape != (n,) or int(order.min()) != 0 or int(order.max()) != n - 1 or int(torch.unique(order).numel()) != n:
+        raise PmnError(f"reduce_points: order must be a permutation of 0..{n - 1}")
+    if cell is None:
+        cell = REDUCE_CELL_RATIO * dst if dst > 0 else 1.0
+    grid = build_grid(points, cell)
+    rank = torch.empty(n, dtype=torch.int32, device=points.device)
+    rank[order] = torch.arange(n, dtype=torch.int32, device=points.device)
+    rank = rank[grid.perm].contiguous()
+    state = torch.zeros(n, dtype=torch.uint8, device=points.device)
+    L = _lib.lib()
+    args = _grid_args(grid)
+    rounds = 0
+    with torch.cuda.device(points.device):
+        while True:
+            counters = torch.zeros(ROUNDS_PER_READ, dtype=torch.int32, device=points.device)
+            for k in range(ROUNDS_PER_READ):
+                check(L.pmn_reduce_round(*args, dst, rank.data_ptr(), state.data_ptr(), counters[k:].data_ptr(), _stream(points)),
+                      "pmn_reduce_round")
+            left = counters.cpu().tolist()
+            if 0 in left:
+                rounds += left.index(0) + 1
+                break
+            rounds += ROUNDS_PER_READ
+    keep = torch.empty(n, dtype=torch.bool, device=points.device)
+    keep[grid.perm] = state == 1
+    return (keep, rounds) if return_rounds else keep
+
+
+# ---- masks and statistics (PointCompareMain.m:32-53, ComputeStat_web.m:52-68) -----------------------------------------------------------
+
+def matlab_round(x: torch.Tensor) -> torch.Tensor:
+    """MATLAB round: halves away from zero (torch.round rounds halves to even)."""
+    t = torch.trunc(x)
+    return t + torch.sign(x) * ((x - t).abs() >= 0.5)
+
+
+def data_in_mask(xyz: torch.Tensor, obs_mask: torch.Tensor, bb: np.ndarray, res: float) -> torch.Tensor:
+    """Qv = round((Qdata - BB(1,:)) / Res + 1), 1-based, inside size(ObsMask) and ObsMask(Qv) set; float64 from the float32 points."""
+    lo = torch.tensor(np.asarray(bb, np.float64)[0], dtype=torch.float64, device=xyz.device)
+    qv = matlab_round((xyz.double() - lo) / float(res) + 1.0)
+    shape = torch.tensor(tuple(obs_mask.shape), dtype=torch.float64, device=xyz.device)
+    inside = ((qv > 0) & (qv <= shape)).all(1)
+    iv = (qv.clamp(1.0, 2.0 ** 40).long() - 1).minimum(torch.tensor(tuple(obs_mask.shape), device=xyz.device) - 1)
+    return inside & (obs_mask[iv[:, 0], iv[:, 1], iv[:, 2]] != 0)
+
+
+def above_plane(xyz: torch.Tensor, plane: np.ndarray) -> torch.Tensor:
+    """P' * [Qstl; 1] > 0 in float64."""
+    p = [float(v) for v in np.asarray(plane, np.float64).reshape(4)]
+    q = xyz.double()
+    return q[:, 0] * p[0] + q[:, 1] * p[1] + q[:, 2] * p[2] + p[3] > 0
+
+
+def in_blocks(xyz: torch.Tensor, bb: np.ndarray, search_dist: float) -> torch.Tensor:
+    """True for the points inside one of MaxDistCP.m's blocks [Low, Low + MaxDist), Low = BB(1,:) + k * MaxDist, k = 0 ..
+    floor((BB(2,:) - BB(1,:)) / MaxDist) per axis, with the bounds computed as the MATLAB computes them."""
+    bb = np.asarray(bb, np.float64)
+    q = xyz.double()
+    out = torch.ones(len(q), dtype=torch.bool, device=xyz.device)
+    for a in range(3):
+        k = np.arange(int(np.floor((bb[1, a] - bb[0, a]) / search_dist)) + 1, dtype=np.float64)
+        low = torch.tensor(bb[0, a] + k * search_dist, dtype=torch.float64, device=xyz.device)
+        high = low + search_dist
+        out &= ((q[:, a, None] >= low) & (q[:, a, None] < high)).any(1)
+    return out
+
+
+def _stats(d: torch.Tensor, prefix: str) -> Dict[str, float]:
+    n = int(d.numel())
+    nan = float("nan")
+    out = {f"{prefix}_n": n, f"{prefix}_mean": nan, f"{prefix}_median": nan, f"{prefix}_var": nan}
+    if n:
+        s = torch.sort(d).values
+        out[f"{prefix}_mean"] = float(d.mean())
+        out[f"{prefix}_median"] = float((s[(n - 1) // 2] + s[n // 2]) / 2)  # numpy / MATLAB median, not torch.median
+    if n > 1:
+        out[f"{prefix}_var"] = float(d.var(unbiased=True))
+    return out
+
+
+def dtu_score_scan(data_xyz: torch.Tensor, stl_xyz: torch.Tensor, obs_mask, bb, res: float, plane, dst: float = 0.2,
+                   max_dist: float = 20.0, search_dist: float = 60.0, seed: int = 0, nn_cell: Optional[float] = None) -> Dict:
+    """PointCompareMain.m + the statistics of BaseEvalMain_web.m / ComputeStat_web.m for one scan.  data_xyz / stl_xyz: [n,3] float32
+    on the device (the vertices of the method's PLY and of stl%03d_total.ply); obs_mask, bb, res, plane: load_obs_mask / load_plane.
+    ``max_dist``: the outlier threshold of the statistics (20); ``search_dist``: MaxDistCP's block size and cap (60).
+    Returns n_data_in, n_data_reduced, reduce_rounds, acc_n/mean/median/var, comp_n/mean/median/var and seconds per phase."""
+    data_xyz = _points(data_xyz, "data_xyz")
+    stl_xyz = _points(stl_xyz, "stl_xyz")
+    dev = data_xyz.device
+    nn_cell = NN_CELL if nn_cell is None else float(nn_cell)
+    obs = torch.as_tensor(np.ascontiguousarray(np.asarray(obs_mask), dtype=np.uint8)).to(dev)
+    if obs.dim() != 3:
+        raise PmnError(f"dtu_score_scan: ObsMask must be 3-D, got {tuple(obs.shape)}")
+
+    def clock():
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    t0 = clock()
+    keep, rounds = reduce_points(data_xyz, dst, seed=seed, return_rounds=True)
+    qd = data_xyz[keep].contiguous()
+    t1 = clock()
+
+    def blocked(frm, to):  # MaxDistCP.m: a from-point in no block keeps MaxDist
+        d = nn_distance(frm, build_grid(to, nn_cell), search_dist)
+        return torch.where(in_blocks(frm, bb, search_dist), d, torch.full_like(d, search_dist))
+
+    d_data = blocked(qd, stl_xyz)
+    t2 = clock()
+    d_stl = blocked(stl_xyz, qd)
+    t3 = clock()
+    acc = d_data[data_in_mask(qd, obs, bb, res)]
+    comp = d_stl[above_plane(stl_xyz, plane)]
+    out = {"n_data_in": int(data_xyz.shape[0]), "n_data_reduced": int(qd.shape[0]), "reduce_rounds": rounds}
+    out.update(_stats(acc[acc < max_dist], "acc"))
+    out.update(_stats(comp[comp < max_dist], "comp"))
+    t4 = clock()
+    out["seconds"] = {"reduce": t1 - t0, "data_to_stl": t2 - t1, "stl_to_data": t3 - t2, "statistics": t4 - t3}
+    return out
+
+
+def totals(per_scan) -> Dict[str, float]:
+    """BaseEvalMain_web.m:98-99: mean over the scans of the per-scan means; overall = (acc + comp) / 2."""
+    acc = float(np.mean([s["acc_mean"] for s in per_scan])) if per_scan else float("nan")
+    comp = float(np.mean([s["comp_mean"] for s in per_scan])) if per_scan else float("nan")
+    return {"acc": acc, "comp": comp, "overall": (acc + comp) / 2}
