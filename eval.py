@@ -778,12 +778,14 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
     with torch.cuda.device(device), torch.cuda.stream(stream):
         stream.wait_event(job["ready"])
         capacity = sum(sizes[ref][0] * sizes[ref][1] for ref, _ in my_pairs)
+        with_normals = bool(getattr(args, "normals", 0))
+        rec_size = 27 if with_normals else 15  # --normals 1: x y z nx ny nz red green blue (fusion.PLY_VERTEX_NORMALS)
         # (15 bytes per pixel of every reference view of the scan: 1.4 GB for 49 views of 1600x1200, 9 GB for 300 views of 1920x1080.
         #  A buffer up to --fuse_buffer_mb stays with the worker for the next scan; a larger one is released when its scan is done.)
         packer = state.get("packer")
-        if packer is None or packer.capacity < capacity or packer.view_counts.numel() < len(my_pairs):
+        if packer is None or packer.capacity < capacity or packer.view_counts.numel() < len(my_pairs) or packer.normals != with_normals:
             state.pop("packer", None)
-            packer = state["packer"] = ops.PointPacker(max(capacity, 1), device, max_views=max(len(my_pairs), 64))
+            packer = state["packer"] = ops.PointPacker(max(capacity, 1), device, max_views=max(len(my_pairs), 64), normals=with_normals)
         packer.reset()
         hmax = max([sizes[ref][0] * sizes[ref][1] for ref, _ in my_pairs] or [1])
         mring = state.get("mask_ring")
@@ -807,7 +809,9 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
         masks_dev = []
         for ref, m in fusion.fuse_views_packed(job["buf"], job["slot_of"], job["cams"], images, my_pairs, args.geo_pixel_thres,
                                                args.geo_depth_thres, args.geo_mask_thres, args.photo_thres, packer,
-                                               sizes=sizes if job["mixed"] else None):
+                                               sizes=sizes if job["mixed"] else None, normals=with_normals,
+                                               normals_radius=getattr(args, "normals_radius", 2),
+                                               normals_depth_thres=getattr(args, "normals_depth_thres", 0.01)):
             masks_dev.append((ref, m))
             images.pop(ref, None)
         t_enqueued = time.time()
@@ -838,12 +842,12 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
         feeder.start()
         ply = os.path.join(args.output_folder, scan, "fused.ply")
         target = ply if world == 1 else ply + ".part{}.tmp".format(rank)
-        header = fusion.ply_header(total) if world == 1 else b""
+        header = fusion.ply_header(total, with_normals) if world == 1 else b""
         fd = os.open(target, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
         try:
             if header:
                 os.pwrite(fd, header, 0)
-            body = fusion.download_to_file(packer.records, 15 * total, fd, len(header), bring, io_pool, stream)
+            body = fusion.download_to_file(packer.records, rec_size * total, fd, len(header), bring, io_pool, stream)
             t_chunks = time.time()
             for f in body:
                 f.result()  # re-raises a writer's exception
@@ -857,7 +861,7 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
         finally:
             feeder.join()
             os.close(fd)
-    if 15 * capacity > (getattr(args, "fuse_buffer_mb", 4096) << 20):
+    if rec_size * capacity > (getattr(args, "fuse_buffer_mb", 4096) << 20):
         state.pop("packer", None)  # (the tensors go back to the caching allocator once the last chunk has been downloaded: above)
     for ref, _ in my_pairs:
         photo, geo, final = fractions[ref]
@@ -878,9 +882,9 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
                 if time.time() > deadline:
                     raise P.PmnError("{}: the point lists of the other ranks never arrived within --fuse_timeout ({})".format(scan, parts))
                 time.sleep(0.005)
-            n_points = sum(os.path.getsize(p) for p in parts) // 15
+            n_points = sum(os.path.getsize(p) for p in parts) // rec_size  # (every rank runs with the same --normals)
             with open(ply, "wb") as f:
-                f.write(fusion.ply_header(n_points))
+                f.write(fusion.ply_header(n_points, with_normals))
                 for p in parts:
                     with open(p, "rb") as g:
                         while True:
@@ -949,6 +953,13 @@ def build_parser():
     p.add_argument("--fuse_buffer_mb", type=int, default=4096,
                    help="the fusion stage's device record buffer (15 B per pixel of a scan's reference views) is kept between scans up to "
                         "this size; a larger one is released after its scan")
+    p.add_argument("--normals", type=int, default=0, choices=(0, 1),
+                   help="--output_type both|fusion: 1 writes an ORIENTED fused.ply (x y z nx ny nz red green blue, 27 B per point): "
+                        "per reference view a surface-normal map from its estimated depth map (pmn_depth_normals), rotated to "
+                        "the world frame; the points, masks and maps are those of a run without it")
+    p.add_argument("--normals_radius", type=int, default=2, choices=(1, 2, 3), help="--normals 1: window radius of the plane fit")
+    p.add_argument("--normals_depth_thres", type=float, default=0.01,
+                   help="--normals 1: relative depth difference up to which a neighbour counts as the same surface")
     p.add_argument("--fuse_timeout", type=float, default=600.0,
                    help="several ranks: seconds rank 0 waits for the other ranks' point lists of a scan before it gives up")
     p.add_argument("--fuse_threads", type=int, default=-1,

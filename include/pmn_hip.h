@@ -307,6 +307,31 @@ int pmn_pack_points(const unsigned char *final_mask, const float *xyz, const voi
                     unsigned char *records, long long capacity_points, long long *cursor, int *view_count, long long *scratch,
                     void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  pmn_pack_points with the normal columns of an oriented
+ * cloud: normals_chw [3][H][W] is the view's camera-frame normal map (pmn_depth_normals), rotation the camera-to-world rotation,
+ * DEVICE float32, row-major with rotation_stride (>= 3) floats between rows -- 3 for a packed 3x3, 4 for the upper-left block of
+ * inverse(E_ref) inside pmn_fuse_view's mats (mats + 18).  Records are 27 bytes: x y z nx ny nz little-endian float32, red green blue
+ * uint8; the world normal is rotation . normal in float32 (products summed left to right, not re-normalised; a zero normal stays
+ * zero).  `records` has room for capacity_points 27-byte records.  Everything else -- which pixels, their order, the cursor,
+ * *view_count = -1 when the view does not fit, the scratch size, three launches -- is pmn_pack_points (the count and the scan are
+ * the same kernels). */
+int pmn_pack_points_normals(const unsigned char *final_mask, const float *xyz, const float *normals_chw, const float *rotation,
+                            int rotation_stride, const void *image_hwc, int image_is_float, int H, int W, unsigned char *records,
+                            long long capacity_points, long long *cursor, int *view_count, long long *scratch, void *stream);
+
+/* Added under ABI 25 (purely additive).  Surface normals of a depth map in the camera frame of its image (the
+ * reference writes no normal maps).  depth [H][W], any H, W >= 1; intrinsics_host HOST float[9] = K row-major (fx, skew, cx, fy, cy
+ * are read; all nine must be finite); pixel (x, y) has the ray inverse(K) (x, y, 1)^T with integer pixel coordinates.
+ * normals_out is PLANAR [3][H][W] (the channel order of COLMAP's .bin body).  Per pixel p: the pixels q of the (2 radius + 1)^2 window
+ * that are inside the image, valid (finite, > 0) and satisfy fabsf(z_q - z_p) <= rel_thres * z_p (float32, one rounding each side)
+ * are accepted; 1 / z_q - 1 / z_p = (z_p - z_q) / (z_p z_q) is fitted by a dx + b dy + c over them (unweighted least squares, the
+ * normal equations' integer determinant and adjugate exact); m = (fx a, skew a + fy b, 1 / z_p + c + a (cx - x_p) + b (cy - y_p)),
+ * n = -m / |m|: unit length, facing the camera (n . ray < 0).  n = (0, 0, 0) where p is invalid, where the determinant is 0 (fewer
+ * than three non-collinear accepted pixels) or where |m| is zero or not finite.  IEEE divisions and square root, no contraction.
+ * radius outside 1..3: PMN_ERR_SHAPE; rel_thres not finite or <= 0, a non-finite intrinsic: PMN_ERR_ARG.  One launch. */
+int pmn_depth_normals(const float *depth, int H, int W, const float *intrinsics_host, int radius, float rel_thres,
+                      float *normals_out, void *stream);
+
 /* ABI 20.  Refinement's input normalisation (reference models/net.py:104-106): out = (depth - depth_min[b]) / (depth_max[b] -
  * depth_min[b]) over n floats per batch element, IEEE subtraction and correctly rounded division = the bits of the torch expression.
  * With it a whole forward consists of launches of this library only, which is what makes it recordable as a launch plan. */

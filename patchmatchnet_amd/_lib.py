@@ -57,6 +57,8 @@ SIGNATURES = {
     "pmn_differentiable_warping": [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _s],
     "pmn_fuse_view": [_fp, ctypes.c_longlong, _i, _hp, _hp, _i, _fp, _i, _i, _f, _f, _i, _f, _fp, _fp, _fp, _ip, _s],
     "pmn_pack_points": [_fp, _fp, _fp, _i, _i, _i, _fp, ctypes.c_longlong, _fp, _ip, _fp, _s],
+    "pmn_pack_points_normals": [_fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _fp, ctypes.c_longlong, _fp, _ip, _fp, _s],
+    "pmn_depth_normals": [_fp, _i, _i, _hp, _i, _f, _fp, _s],
     "pmn_normalize_depth": [_fp, _fp, _fp, _i, _i, _fp, _s],
     "pmn_check_f16_domain": [_fp, ctypes.c_longlong, _ip, _s],
     "pmn_plan_create": [ctypes.POINTER(ctypes.c_void_p)],

@@ -362,12 +362,25 @@ def rotation_matrix_to_quaternion(rot: np.ndarray) -> List[float]:
     return [q[0], q[1], q[2], q[3]]
 
 
-def export_workspace(input_folder: str, results_folder: str = "", output_folder: str = "") -> None:
+def export_workspace(input_folder: str, results_folder: str = "", output_folder: str = "", normal_maps: bool = False,
+                     device: str = "cuda:0", normals_radius: int = 2, normals_depth_thres: float = 0.01) -> None:
     """MVSNet-layout input (cams/, images/, pair.txt) + eval.py results (depth_est/, confidence/ as .pfm or .bin) -> a COLMAP dense
     workspace: images/, stereo/{depth,confidence}_maps/<image>.geometric.bin, stereo/patch-match.cfg, stereo/fusion.cfg, and a
-    PINHOLE text model with no points in sparse/.  Views are listed in ascending id order."""
+    PINHOLE text model with no points in sparse/.  Views are listed in ascending id order.
+
+    ``normal_maps``: additionally stereo/normal_maps/<image>.geometric.bin for every image -- COLMAP's stereo_fusion opens one per
+    image of fusion.cfg -- computed on ``device`` from the exported depth map (ops.depth_normals) with the cam
+    file's intrinsics scaled to the map's size as eval.py scales them.  Needs a ROCm device (checked before anything is written);
+    without the flag the export is host-only and stereo/normal_maps/ stays empty, as the reference leaves it."""
     from PIL import Image as PilImage
     from .data_io import read_cam_file, read_map, read_pair_file, save_bin
+    if normal_maps:
+        import torch
+        from ._lib import PmnError
+        if torch.device(device).type != "cuda" or not torch.cuda.is_available():
+            raise PmnError(f"--normal_maps needs a ROCm GPU (pmn_depth_normals has no CPU fallback): device {device!r} is not one, "
+                           "or none is visible; nothing was written")
+        from . import ops
     results_folder = results_folder or input_folder
     output_folder = output_folder or input_folder
     for what, d in (("input", input_folder), ("results", results_folder), ("output", output_folder)):
@@ -391,6 +404,17 @@ def export_workspace(input_folder: str, results_folder: str = "", output_folder:
                 shutil.copyfile(src, dst)
             else:
                 save_bin(dst, np.ascontiguousarray(read_map(src)))
+            if normal_maps and kind == "depth_maps":
+                depth = np.ascontiguousarray(read_map(src), np.float32)
+                depth = depth.reshape(depth.shape[0], depth.shape[1])
+                with PilImage.open(os.path.join(input_folder, "images", image_file)) as im:
+                    w0, h0 = im.width, im.height
+                K, _, _ = read_cam_file(os.path.join(input_folder, "cams", stem + "_cam.txt"))
+                K[0] *= depth.shape[1] / w0  # eval.py's _scan_cameras: the intrinsics at the MAP's size
+                K[1] *= depth.shape[0] / h0
+                nrm = ops.depth_normals(torch.from_numpy(depth).to(device), K, normals_radius, normals_depth_thres)
+                save_bin(os.path.join(output_folder, "stereo", "normal_maps", image_file + ".geometric.bin"),
+                         np.ascontiguousarray(nrm.permute(1, 2, 0).cpu().numpy()))
 
     cameras, images = [], []
     for cam_file in sorted(os.listdir(os.path.join(input_folder, "cams"))):

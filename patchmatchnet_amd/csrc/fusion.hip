@@ -163,6 +163,8 @@ extern "C" int pmn_fuse_view(const float* maps, long long slot_stride, int ref_s
 // Three launches per view on the caller's stream: per-block counts (1024 pixels per block), an exclusive scan of the block counts
 // that also advances the cursor, and the pack.  Colours: the decoded image bytes (uint8 [H,W,3]), or for a resized float image in
 // [0,1] the reference's (color * 255).astype(uint8) = truncation of the float32 product.
+// pmn_pack_points_normals is the same three launches with 27-byte records: the pack kernel is instantiated
+// with and without the normal columns, the count and the scan are shared, so the point set and order are the same by construction.
 #define PMN_PACK_PIX 4                        // consecutive pixels per thread
 #define PMN_PACK_BLOCK (256 * PMN_PACK_PIX)   // pixels per workgroup
 
@@ -231,10 +233,17 @@ __global__ __launch_bounds__(1024) void pack_scan_kernel(long long* __restrict__
     }
 }
 
+// NORMALS (pmn_pack_points_normals): 27-byte records x y z nx ny nz red green blue; the world normal is rot (row-major, rows
+// rot_stride floats apart) times the pixel's camera-frame normal of the planar map normals [3][n], float32 products summed left to
+// right; a zero normal stays exactly zero (0 * r + 0 * r + 0 * r).
+template <bool NORMALS>
 __global__ __launch_bounds__(256) void pack_write_kernel(const unsigned char* __restrict__ mask, const float* __restrict__ xyz,
                                                          const void* __restrict__ image, int image_is_float, long long n,
-                                                         const long long* __restrict__ blocks, unsigned char* __restrict__ records) {
+                                                         const long long* __restrict__ blocks, unsigned char* __restrict__ records,
+                                                         const float* __restrict__ normals, const float* __restrict__ rot,
+                                                         int rot_stride) {
 #pragma clang fp contract(off)
+    constexpr int REC = NORMALS ? 27 : 15, COLOUR = NORMALS ? 6 : 3;
     __shared__ int part[4];
     if (blocks[0] < 0) return;  // overflow reported by the scan
     bool keep[PMN_PACK_PIX];
@@ -257,10 +266,18 @@ __global__ __launch_bounds__(256) void pack_write_kernel(const unsigned char* __
     for (int j = 0; j < PMN_PACK_PIX; ++j) {
         if (!keep[j]) continue;
         const long long p = p0 + j;
-        unsigned int word[4];
+        unsigned int word[COLOUR + 1];
         word[0] = __float_as_uint(xyz[3 * p + 0]);
         word[1] = __float_as_uint(xyz[3 * p + 1]);
         word[2] = __float_as_uint(xyz[3 * p + 2]);
+        if (NORMALS) {
+            const float cx = normals[p], cy = normals[n + p], cz = normals[2 * n + p];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float* r3 = rot + k * rot_stride;
+                word[3 + k] = __float_as_uint((r3[0] * cx + r3[1] * cy) + r3[2] * cz);
+            }
+        }
         unsigned int cr, cg, cb;
         if (image_is_float) {
             const float* im = static_cast<const float*>(image) + 3 * p;
@@ -273,17 +290,17 @@ __global__ __launch_bounds__(256) void pack_write_kernel(const unsigned char* __
             cg = im[1];
             cb = im[2];
         }
-        word[3] = cr | (cg << 8) | (cb << 16);
-        unsigned char* o = records + r * 15;
+        word[COLOUR] = cr | (cg << 8) | (cb << 16);
+        unsigned char* o = records + r * REC;
 #pragma unroll
-        for (int i = 0; i < 15; ++i) o[i] = (unsigned char)(word[i >> 2] >> (8 * (i & 3)));
+        for (int i = 0; i < REC; ++i) o[i] = (unsigned char)(word[i >> 2] >> (8 * (i & 3)));
         ++r;
     }
 }
 
-extern "C" int pmn_pack_points(const unsigned char* final_mask, const float* xyz, const void* image_hwc, int image_is_float, int H,
-                               int W, unsigned char* records, long long capacity_points, long long* cursor, int* view_count,
-                               long long* scratch, void* stream) {
+static int pack_points(const unsigned char* final_mask, const float* xyz, const void* image_hwc, int image_is_float, int H, int W,
+                       unsigned char* records, long long capacity_points, long long* cursor, int* view_count, long long* scratch,
+                       const float* normals, const float* rot, int rot_stride, void* stream) {
     if (!final_mask || !xyz || !image_hwc || !records || !cursor || !view_count || !scratch) return PMN_ERR_ARG;
     if (H < 1 || W < 1 || capacity_points < 0) return PMN_ERR_ARG;
     const long long n = (long long)H * W;
@@ -294,8 +311,28 @@ extern "C" int pmn_pack_points(const unsigned char* final_mask, const float* xyz
     PMN_CHECK_LAUNCH();
     PMN_LAUNCH(pack_scan_kernel, dim3(1), dim3(1024), 0, st, scratch, (int)nb, cursor, capacity_points, view_count);
     PMN_CHECK_LAUNCH();
-    PMN_LAUNCH(pack_write_kernel, dim3((unsigned)nb), dim3(256), 0, st, final_mask, xyz, image_hwc, image_is_float, n,
-                       (const long long*)scratch, records);
+    if (normals)
+        PMN_LAUNCH(pack_write_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, final_mask, xyz, image_hwc, image_is_float, n,
+                   (const long long*)scratch, records, normals, rot, rot_stride);
+    else
+        PMN_LAUNCH(pack_write_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, final_mask, xyz, image_hwc, image_is_float, n,
+                   (const long long*)scratch, records, normals, rot, rot_stride);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
+}
+
+extern "C" int pmn_pack_points(const unsigned char* final_mask, const float* xyz, const void* image_hwc, int image_is_float, int H,
+                               int W, unsigned char* records, long long capacity_points, long long* cursor, int* view_count,
+                               long long* scratch, void* stream) {
+    return pack_points(final_mask, xyz, image_hwc, image_is_float, H, W, records, capacity_points, cursor, view_count, scratch,
+                       nullptr, nullptr, 0, stream);
+}
+
+extern "C" int pmn_pack_points_normals(const unsigned char* final_mask, const float* xyz, const float* normals_chw,
+                                       const float* rotation, int rotation_stride, const void* image_hwc, int image_is_float, int H,
+                                       int W, unsigned char* records, long long capacity_points, long long* cursor, int* view_count,
+                                       long long* scratch, void* stream) {
+    if (!normals_chw || !rotation || rotation_stride < 3) return PMN_ERR_ARG;
+    return pack_points(final_mask, xyz, image_hwc, image_is_float, H, W, records, capacity_points, cursor, view_count, scratch,
+                       normals_chw, rotation, rotation_stride, stream);
 }

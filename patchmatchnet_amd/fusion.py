@@ -131,31 +131,47 @@ def fuse_scan(views: Dict[int, Dict], pairs: List[Tuple[int, List[int]]], geo_pi
 
 
 PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+# the vertex of an ORIENTED cloud (eval.py --normals 1): the property order MeshLab, Open3D and COLMAP's own
+# fused.ply use, so Poisson meshers read the normals without a conversion
+PLY_VERTEX_NORMALS = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                               ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 
 
-def ply_records(vertices: np.ndarray, colors: np.ndarray) -> np.ndarray:
-    """The 15-byte vertex records of the PLY body (two strided byte copies: positions, colours)."""
+def ply_records(vertices: np.ndarray, colors: np.ndarray, normals: Optional[np.ndarray] = None) -> np.ndarray:
+    """The 15-byte vertex records of the PLY body (two strided byte copies: positions, colours); with ``normals`` [n,3] the 27-byte
+    records x y z nx ny nz red green blue."""
     n = len(vertices)
-    rec = np.empty(n, dtype=PLY_VERTEX)
+    if normals is None:
+        rec = np.empty(n, dtype=PLY_VERTEX)
+        if n:
+            raw = rec.view(np.uint8).reshape(n, 15)
+            raw[:, :12] = np.ascontiguousarray(vertices, "<f4").view(np.uint8).reshape(n, 12)
+            raw[:, 12:] = np.asarray(colors, np.uint8)
+        return rec
+    if len(normals) != n:
+        raise ValueError("ply_records: one normal per vertex")
+    rec = np.empty(n, dtype=PLY_VERTEX_NORMALS)
     if n:
-        raw = rec.view(np.uint8).reshape(n, 15)
+        raw = rec.view(np.uint8).reshape(n, 27)
         raw[:, :12] = np.ascontiguousarray(vertices, "<f4").view(np.uint8).reshape(n, 12)
-        raw[:, 12:] = np.asarray(colors, np.uint8)
+        raw[:, 12:24] = np.ascontiguousarray(normals, "<f4").view(np.uint8).reshape(n, 12)
+        raw[:, 24:] = np.asarray(colors, np.uint8)
     return rec
 
 
-def ply_header(n: int) -> bytes:
+def ply_header(n: int, normals: bool = False) -> bytes:
+    extra = "property float nx\nproperty float ny\nproperty float nz\n" if normals else ""
     return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-            "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % n).encode("ascii")
+            "property float z\n%sproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % (n, extra)).encode("ascii")
 
 
-def write_ply(filename: str, vertices: np.ndarray, colors: np.ndarray) -> None:
+def write_ply(filename: str, vertices: np.ndarray, colors: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
     """Binary little-endian PLY with x,y,z float32 + red,green,blue uint8 per vertex (what plyfile writes at reference
-    eval.py:283-297)."""
-    rec = ply_records(vertices, colors)
+    eval.py:283-297); with ``normals`` the oriented vertex x,y,z,nx,ny,nz,red,green,blue."""
+    rec = ply_records(vertices, colors, normals)
     os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
     with open(filename, "wb") as f:
-        f.write(ply_header(len(rec)))
+        f.write(ply_header(len(rec), normals is not None))
         rec.tofile(f)
 
 
@@ -176,13 +192,17 @@ def write_ply_records(filename: str, chunks, header: bool = True) -> int:
 
 def fuse_views_packed(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[int, Dict], images: Dict[int, torch.Tensor],
                       pairs: List[Tuple[int, List[int]]], geo_pixel_thres: float, geo_depth_thres: float, geo_mask_thres: int,
-                      photo_thres: float, packer: "ops.PointPacker", sizes: Optional[Dict[int, Tuple[int, int]]] = None):
+                      photo_thres: float, packer: "ops.PointPacker", sizes: Optional[Dict[int, Tuple[int, int]]] = None,
+                      normals: bool = False, normals_radius: int = 2, normals_depth_thres: float = 0.01):
     """The device half of ``fuse_views`` and nothing else: per reference view of ``pairs`` one pmn_fuse_view launch and one
     pmn_pack_points (three small launches) on the CURRENT stream -- the kept points become PLY vertex records appended to
     ``packer.records`` in pair-file / row-major order (reference eval.py:270-297), nothing synchronises, nothing leaves the device.
     ``images[ref]``: the reference view's image ON THE DEVICE, [H,W,3] uint8 (the decoded bytes) or float32 in [0,1].
     A generator: yields (ref, masks) per view -- masks = the [3,H,W] uint8 device tensor (photo, geo, final) -- so that the caller
-    can queue its download behind the launches.  After the last view ``packer.counts()`` holds every view's number of points."""
+    can queue its download behind the launches.  After the last view ``packer.counts()`` holds every view's number of points.
+    ``normals`` (with a ``PointPacker(normals=True)``): one more launch per view, pmn_depth_normals on the view's ESTIMATED depth map
+    in ``maps`` (not the averaged depth) with its intrinsics; the records carry inverse(E_ref)[:3,:3] . normal.
+    The masks and the points are those of a call without normals."""
     if not maps.is_cuda:
         raise PmnError("fusion runs on a ROCm GPU only (pmn_fuse_view); there is no CPU fallback")
     slot_sizes = None
@@ -196,7 +216,17 @@ def fuse_views_packed(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[in
         mats = torch.from_numpy(block).to(maps.device)
         m, xyz, _, _ = ops.fuse_view(maps, slot_of[ref], [slot_of[s] for s in srcs], mats, geo_pixel_thres, geo_depth_thres,
                                      geo_mask_thres, photo_thres, sizes=slot_sizes)
-        packer.append(m[2], xyz, images[ref])
+        if normals:
+            sl = slot_of[ref]
+            if slot_sizes is None:
+                depth = maps[sl, 0]
+            else:
+                h, w = slot_sizes[sl]
+                depth = maps[sl, :h * w].view(h, w)
+            nrm = ops.depth_normals(depth, cams[ref]["intrinsics"], normals_radius, normals_depth_thres)
+            packer.append(m[2], xyz, images[ref], nrm, mats[18:34].view(4, 4))  # the block camera_block put there: inverse(E_ref)
+        else:
+            packer.append(m[2], xyz, images[ref])
         yield ref, m
 
 

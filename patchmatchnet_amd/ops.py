@@ -880,6 +880,41 @@ def fuse_view(maps: torch.Tensor, ref_slot: int, src_slots: Sequence[int], mats:
     return masks, xyz, davg, gsum
 
 
+def depth_normals(depth: torch.Tensor, intrinsics, radius: int = 2, rel_thres: float = 0.01) -> torch.Tensor:
+    """pmn_depth_normals: camera-frame surface normals of depth maps, unit length and facing the camera, zero
+    where there is no valid depth or no plane to fit.  depth [H,W] with intrinsics [3,3] -> [3,H,W] (planar: the body of COLMAP's
+    normal-map .bin); depth [B,H,W] with intrinsics [B,3,3] -> [B,3,H,W], one launch per map.  ``intrinsics`` (numpy or tensor, at
+    the MAP's size) is read on the host; ``radius`` 1..3 is the window radius, ``rel_thres`` the relative depth difference up to which
+    a neighbour counts as the same surface (--geo_depth_thres's test)."""
+    _dev(depth, "depth")
+    if depth.dim() not in (2, 3) or depth.numel() == 0:
+        raise PmnError("depth_normals: depth must be [H,W] or [B,H,W], H, W >= 1")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 3:
+        raise PmnError("depth_normals: radius must be 1, 2 or 3")
+    with np.errstate(over="ignore"):
+        rel_thres = float(np.float32(rel_thres))  # the kernel's value: 1e-60 is 0 there, 1e60 is inf
+    if not (np.isfinite(rel_thres) and rel_thres > 0.0):
+        raise PmnError("depth_normals: rel_thres must be a positive finite float32")
+    K = np.ascontiguousarray((intrinsics.detach().cpu().numpy() if isinstance(intrinsics, torch.Tensor) else np.asarray(intrinsics)),
+                             np.float32)
+    batched = depth.dim() == 3
+    B = depth.shape[0] if batched else 1
+    if tuple(K.shape) != ((B, 3, 3) if batched else (3, 3)):
+        raise PmnError("depth_normals: intrinsics must be [3,3] for a [H,W] map, [B,3,3] for [B,H,W] maps")
+    if not np.isfinite(K).all():
+        raise PmnError("depth_normals: intrinsics must be finite")
+    K = K.reshape(B, 9)
+    H, W = depth.shape[-2:]
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        for b in range(B):
+            k, k_p = _host_f32(K[b], 9, "intrinsics")
+            check(_lib.lib().pmn_depth_normals((depth[b] if batched else depth).data_ptr(), H, W, k_p, int(radius), rel_thres,
+                                               out[b].data_ptr(), _stream(depth)), "pmn_depth_normals")
+            del k
+    return out if batched else out[0]
+
+
 class PointPacker:
     """pmn_pack_points: the PLY vertex records of a scan's fused reference views, packed on the device view after view into ONE
     record buffer (reference eval.py:270-297).  ``capacity`` = room in points (a view can keep at most H*W).
@@ -888,11 +923,18 @@ class PointPacker:
         for every reference view:  packer.append(masks[2], xyz, image_hwc)        # three launches on the current stream
         counts = packer.counts()                                                   # synchronises the current stream
         body = packer.records[:15 * sum(counts)]                                   # device uint8: the PLY body in pair-file order
+
+    ``normals=True`` (pmn_pack_points_normals): 27-byte records x y z nx ny nz red green blue; ``append`` then also takes the view's
+    camera-frame normal map [3,H,W] (``depth_normals``) and its camera-to-world rotation, a device float32 [3,3] or the [4,4]
+    inverse(E_ref) whose upper-left block it is (a view into pmn_fuse_view's ``mats`` will do: nothing is copied).  Same points in the
+    same order; ``record_size`` is the stride of ``records``.
     """
 
-    def __init__(self, capacity: int, device, max_views: int = 1024) -> None:
+    def __init__(self, capacity: int, device, max_views: int = 1024, normals: bool = False) -> None:
         self.capacity = int(capacity)
-        self.records = torch.empty((15 * self.capacity,), dtype=torch.uint8, device=device)
+        self.normals = bool(normals)
+        self.record_size = 27 if self.normals else 15  # x y z [nx ny nz] red green blue
+        self.records = torch.empty((self.record_size * self.capacity,), dtype=torch.uint8, device=device)
         self.cursor = torch.zeros((1,), dtype=torch.int64, device=device)
         self.view_counts = torch.zeros((max_views,), dtype=torch.int32, device=device)
         self.scratch = None
@@ -902,8 +944,12 @@ class PointPacker:
         self.cursor.zero_()
         self.n = 0
 
-    def append(self, final_mask: torch.Tensor, xyz: torch.Tensor, image_hwc: torch.Tensor) -> None:
+    def append(self, final_mask: torch.Tensor, xyz: torch.Tensor, image_hwc: torch.Tensor,
+               normals_chw: Optional[torch.Tensor] = None, rotation: Optional[torch.Tensor] = None) -> None:
         _dev(xyz, "xyz")
+        if self.normals != (normals_chw is not None) or self.normals != (rotation is not None):
+            raise PmnError("pack_points: a packer built with normals=True takes normals_chw and rotation with every view, "
+                           "one built without takes neither")
         for t, name in ((final_mask, "final_mask"), (image_hwc, "image_hwc")):
             if not isinstance(t, torch.Tensor) or t.device != self.records.device:
                 raise PmnError(f"pack_points: {name} must be a tensor on {self.records.device} (no CPU fallback)")
@@ -919,6 +965,22 @@ class PointPacker:
         nb = (H * W + 1023) // 1024
         if self.scratch is None or self.scratch.numel() < nb:
             self.scratch = torch.empty((nb,), dtype=torch.int64, device=self.records.device)
+        if self.normals:
+            for t, name in ((normals_chw, "normals_chw"), (rotation, "rotation")):
+                if not isinstance(t, torch.Tensor) or t.device != self.records.device or t.dtype != torch.float32:
+                    raise PmnError(f"pack_points: {name} must be a float32 tensor on {self.records.device} (no CPU fallback)")
+            if tuple(normals_chw.shape) != (3, H, W) or not normals_chw.is_contiguous():
+                raise PmnError("pack_points: normals_chw must be contiguous float32 [3,H,W]")
+            if tuple(rotation.shape) not in ((3, 3), (4, 4)) or rotation.stride(1) != 1 or rotation.stride(0) < 3:
+                raise PmnError("pack_points: rotation must be float32 [3,3] or [4,4] with unit column stride")
+            with torch.cuda.device(self.records.device):
+                check(_lib.lib().pmn_pack_points_normals(final_mask.data_ptr(), xyz.data_ptr(), normals_chw.data_ptr(),
+                                                         rotation.data_ptr(), int(rotation.stride(0)), image_hwc.data_ptr(),
+                                                         1 if image_hwc.dtype == torch.float32 else 0, H, W, self.records.data_ptr(),
+                                                         self.capacity, self.cursor.data_ptr(), self.view_counts[self.n:].data_ptr(),
+                                                         self.scratch.data_ptr(), _stream(self.records)), "pmn_pack_points_normals")
+            self.n += 1
+            return
         with torch.cuda.device(self.records.device):
             check(_lib.lib().pmn_pack_points(final_mask.data_ptr(), xyz.data_ptr(), image_hwc.data_ptr(),
                                              1 if image_hwc.dtype == torch.float32 else 0, H, W, self.records.data_ptr(),
