@@ -45,6 +45,7 @@ extern "C" {
 #define PMN_MAX_DEPTH 64
 #define PMN_MAX_NEIGHBORS 17
 #define PMN_MAX_FUSE_SRC 32
+#define PMN_TSDF_MAX_VIEWS 16 /* views of one pmn_tsdf_integrate launch */
 
 #define PMN_OK 0
 #define PMN_ERR_ARG (-1)     /* null pointer / size out of range */
@@ -461,6 +462,49 @@ int pmn_nn_distance(const float *to_xyz, const long long *to_keys, long long n_t
                     int *index, void *stream);
 int pmn_reduce_round(const float *xyz, const long long *keys, long long n, const double *origin_host, double cell,
                      const int *dims_host, double dst, const int *rank, unsigned char *state, unsigned int *counter, void *stream);
+
+/* Added under ABI 25 (purely additive: three tests of the existing suite pin the number).  A surface mesh from the depth maps (the reference has no mesher; tests/tsdf_ref.py is the numpy form).
+ *
+ * The volume is a dense lattice of dims_host = {nx, ny, nz} samples (HOST int[3]; nz <= 65535, nx * ny * nz < 2^31, else PMN_ERR_SHAPE),
+ * x fastest, sample (i, j, k) at origin_host[c] + (float)index * voxel per coordinate (HOST float[3], world units).  Planes, all DEVICE
+ * float32 [nz][ny][nx] owned and initialised by the caller: tsdf (1), weight (0) and -- both or neither -- rgb [3][nz][ny][nx] and
+ * cweight (0).
+ *
+ * pmn_tsdf_integrate folds n_views (1 .. PMN_TSDF_MAX_VIEWS) depth maps into the volume in ONE launch.  The views are addressed as
+ * pmn_fuse_view addresses them: maps + slots_host[v] * slot_stride is the depth map [h_v][w_v] of view v, hw_host = HOST int[2 n_views]
+ * (height, width; h * w <= slot_stride).  masks_host / images_host: NULL, or HOST arrays of n_views DEVICE pointers (entries may be NULL)
+ * to a uint8 mask [h][w] (pmn_fuse_view's final mask: zero = ignore the pixel) and a uint8 image [h][w][3].  cams_host: HOST
+ * float[21 n_views] = K row-major at the MAP's size, then the upper 3 x 4 of the world-to-camera extrinsic row-major; all finite.
+ * Per sample p and per view, in view order, float32, no contraction, IEEE division:
+ *   pc_r = ((R_r0 p.x + R_r1 p.y) + R_r2 p.z) + t_r; skip if pc.z <= 0.  q_r = (K_r0 pc.x + K_r1 pc.y) + K_r2 pc.z.
+ *   fx = floorf(q.x / q.z + 0.5f), fy likewise; skip unless 0 <= fx < w and 0 <= fy < h (as floats; NaN is outside); nearest pixel.
+ *   d = depth[fy][fx]; skip unless 0 < d < inf and the mask byte is non-zero.  sdf = d - pc.z; skip if sdf < -trunc.
+ *   obs = fminf(1, sdf / trunc); tsdf = (tsdf * weight + obs) / (weight + 1); weight += 1; with colour planes, an image and
+ *   sdf <= trunc: rgb_c = (rgb_c * cweight + (float)byte_c) / (cweight + 1); cweight += 1.
+ * A batch of V views leaves exactly the bits of V single-view calls.  voxel, trunc > 0 and finite, else PMN_ERR_ARG.
+ *
+ * pmn_mt_count / pmn_mt_emit: the iso-surface tsdf = 0 by marching tetrahedra on the Kuhn split (six tetrahedra {0, a, a|b, 7} per cell,
+ * (a, b) in lexicographic order over the axis bits 1, 2, 4), indexed and closed wherever the volume is observed.  A cell is live iff its
+ * eight corners have weight >= min_weight; an edge lo -> hi (lo a subset of hi) belongs to the sample at lo with class hi ^ lo (1..7) and
+ * carries a vertex iff tsdf < 0 differs at its ends and a live cell contains it.  pmn_mt_count writes vertex_mask [nz][ny][nx] (bit
+ * class - 1 = the sample owns a vertex on its edge of that class) and cell_triangles [nz][ny][nx] (0..12, indexed by the cell's corner 0;
+ * a sample on the last plane of an axis owns no cell and gets 0).  The caller scans both (INCLUSIVE int32 prefix sums of
+ * popcount(vertex_mask) and of cell_triangles, x fastest; the totals must fit int32) and allocates the outputs.  pmn_mt_emit writes
+ * vertices [Nv][3] (p_lo + t (p_hi - p_lo) per coordinate, t = v_lo / (v_lo - v_hi)), colors [Nv][3] uint8 or NULL (needs the colour
+ * planes; floorf(c + 0.5f) of the interpolated colour; an end with cweight 0 takes the other end's, both 0 give 128), normals [Nv][3] or
+ * NULL (the central differences tsdf[s + e] - tsdf[s - e] of both ends interpolated with t, normalised; zero where one of the twelve
+ * neighbours is outside the lattice or below min_weight) and faces [Nt][3] int32, wound so that the normal points from tsdf < 0 to
+ * tsdf > 0.  Order: vertices by owning sample then class; triangles by cell, tetrahedron, triangle.  One launch each. */
+int pmn_tsdf_integrate(float *tsdf, float *weight, float *rgb, float *cweight, const int *dims_host, const float *origin_host,
+                       float voxel, float trunc, const float *maps, long long slot_stride, const int *slots_host,
+                       const int *hw_host, const void *const *masks_host, const void *const *images_host, const float *cams_host,
+                       int n_views, void *stream);
+int pmn_mt_count(const float *tsdf, const float *weight, const int *dims_host, float min_weight, unsigned char *vertex_mask,
+                 unsigned char *cell_triangles, void *stream);
+int pmn_mt_emit(const float *tsdf, const float *weight, const float *rgb, const float *cweight, const int *dims_host,
+                const float *origin_host, float voxel, float min_weight, const unsigned char *vertex_mask,
+                const unsigned char *cell_triangles, const int *vertex_scan, const int *triangle_scan, float *vertices,
+                unsigned char *colors, float *normals, int *faces, void *stream);
 
 #ifdef __cplusplus
 }

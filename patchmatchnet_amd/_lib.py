@@ -18,6 +18,7 @@ MLP_FLOATS = 340
 MAX_DEPTH = 64
 MAX_NEIGHBORS = 17
 MAX_FUSE_SRC = 32
+TSDF_MAX_VIEWS = 16
 
 _fp = ctypes.c_void_p  # device float* (passed as integer address)
 _ip = ctypes.c_void_p
@@ -73,6 +74,9 @@ SIGNATURES = {
     "pmn_nn_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, ctypes.c_double, _fp, _ip,
                         _s],
     "pmn_reduce_round": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, ctypes.c_double, _ip, _ip, _ip, _s],
+    "pmn_tsdf_integrate": [_fp] * 4 + [_hp, _hp, _f, _f, _fp, ctypes.c_longlong] + [_hp] * 5 + [_i, _s],
+    "pmn_mt_count": [_fp, _fp, _hp, _f, _ip, _ip, _s],
+    "pmn_mt_emit": [_fp] * 4 + [_hp, _hp, _f, _f] + [_ip] * 4 + [_fp, _ip, _fp, _ip, _s],
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)

@@ -915,6 +915,136 @@ def depth_normals(depth: torch.Tensor, intrinsics, radius: int = 2, rel_thres: f
     return out if batched else out[0]
 
 
+
+def _volume_planes(tsdf, weight, rgb, cweight, what):
+    _dev(tsdf, "tsdf")
+    _dev(weight, "weight")
+    if tsdf.dim() != 3 or tsdf.numel() == 0 or weight.shape != tsdf.shape or weight.device != tsdf.device:
+        raise PmnError(f"{what}: tsdf and weight must be [nz,ny,nx] planes of one volume on one device")
+    if (rgb is None) != (cweight is None):
+        raise PmnError(f"{what}: rgb and cweight come together or not at all")
+    if rgb is not None:
+        _dev(rgb, "rgb")
+        _dev(cweight, "cweight")
+        if tuple(rgb.shape) != (3,) + tuple(tsdf.shape) or cweight.shape != tsdf.shape or rgb.device != tsdf.device or \
+                cweight.device != tsdf.device:
+            raise PmnError(f"{what}: rgb must be [3,nz,ny,nx] and cweight [nz,ny,nx] on the volume's device")
+    nz, ny, nx = tsdf.shape
+    if nz > 65535 or tsdf.numel() > 2 ** 31 - 1:
+        raise PmnError(f"{what}: a volume holds at most 2^31 - 1 samples and 65535 planes")
+    return _host_i32(np.asarray([nx, ny, nz]), 3, "dims")
+
+
+def _positive_f32(v, what):
+    with np.errstate(over="ignore"):
+        v = float(np.float32(v))
+    if not (np.isfinite(v) and v > 0.0):
+        raise PmnError(f"{what} must be a positive finite float32")
+    return v
+
+
+def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, rgb: Optional[torch.Tensor], cweight: Optional[torch.Tensor], origin,
+                   voxel: float, trunc: float, maps: torch.Tensor, slots: Sequence[int], sizes: Sequence[Tuple[int, int]], cams,
+                   masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                   images: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+    """pmn_tsdf_integrate: folds the depth maps of len(slots) views (1 .. _lib.TSDF_MAX_VIEWS) into the volume IN PLACE, one launch
+    (DESIGN.md section 15).  tsdf / weight [nz,ny,nx] (initially 1 / 0), rgb [3,nz,ny,nx] + cweight or None + None; ``origin`` 3
+    floats and ``voxel`` place sample (i,j,k) at origin + (i,j,k) * voxel.  maps [S,F] float32 slots (or any [S,...] buffer whose slot
+    starts with the depth map, e.g. eval.py's [V,2,H,W]); view n is slot ``slots[n]``, ``sizes[n] = (h, w)``, ``cams[n]`` = 21 floats
+    (K row-major at map size, then the upper 3x4 of the world-to-camera extrinsic; numpy, read on the host), ``masks[n]`` a uint8
+    [h,w] tensor or None, ``images[n]`` a uint8 [h,w,3] tensor or None."""
+    dims, dims_p = _volume_planes(tsdf, weight, rgb, cweight, "tsdf_integrate")
+    _dev(maps, "maps")
+    if maps.dim() < 2 or maps.device != tsdf.device:
+        raise PmnError("tsdf_integrate: maps must be [S,...] slots on the volume's device")
+    S, stride = maps.shape[0], maps[0].numel()
+    V = len(slots)
+    if not 1 <= V <= _lib.TSDF_MAX_VIEWS:
+        raise PmnError(f"tsdf_integrate: 1 .. {_lib.TSDF_MAX_VIEWS} views per launch, got {V}")
+    if len(sizes) != V or any(not 0 <= int(s) < S for s in slots) or any(h < 1 or w < 1 or h * w > stride for h, w in sizes):
+        raise PmnError("tsdf_integrate: a slot is out of range or a view's depth map does not fit its slot")
+    cam = np.ascontiguousarray(np.asarray(cams, np.float32).reshape(-1))
+    if cam.size != 21 * V or not np.isfinite(cam).all():
+        raise PmnError("tsdf_integrate: cams must hold 21 finite floats per view (K, then the upper 3x4 of the extrinsic)")
+    org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
+    if not np.isfinite(org).all():
+        raise PmnError("tsdf_integrate: origin must be finite")
+    voxel, trunc = _positive_f32(voxel, "tsdf_integrate: voxel"), _positive_f32(trunc, "tsdf_integrate: trunc")
+
+    def table(items, shape_of, name):
+        if items is None:
+            return None, None
+        if len(items) != V:
+            raise PmnError(f"tsdf_integrate: {name} must have one entry (a tensor or None) per view")
+        arr = (ctypes.c_void_p * V)()
+        for n, t in enumerate(items):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != tsdf.device or t.dtype != torch.uint8 or \
+                    not t.is_contiguous() or tuple(t.shape) != shape_of(*sizes[n]):
+                raise PmnError(f"tsdf_integrate: {name}[{n}] must be a contiguous uint8 tensor {shape_of(*sizes[n])} on the volume's "
+                               f"device (no CPU fallback)")
+            arr[n] = t.data_ptr()
+        return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+    m_arr, m_p = table(masks, lambda h, w: (h, w), "masks")
+    i_arr, i_p = table(images, lambda h, w: (h, w, 3), "images")
+    sl, sl_p = _host_i32(np.asarray(list(slots)), V, "slots")
+    hw, hw_p = _host_i32(np.asarray([x for s in sizes for x in s]), 2 * V, "sizes")
+    with torch.cuda.device(tsdf.device):
+        check(_lib.lib().pmn_tsdf_integrate(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), dims_p, org_p, voxel, trunc,
+                                            maps.data_ptr(), int(stride), sl_p, hw_p, m_p, i_p, cam.ctypes.data_as(ctypes.c_void_p), V,
+                                            _stream(tsdf)), "pmn_tsdf_integrate")
+    del dims, org, m_arr, i_arr, sl, hw
+
+
+def _popcount_u8(m: torch.Tensor) -> torch.Tensor:
+    m = m - ((m >> 1) & 0x55)
+    m = (m & 0x33) + ((m >> 2) & 0x33)
+    return (m + (m >> 4)) & 0x0F
+
+
+def mt_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, min_weight: float = 1.0,
+               rgb: Optional[torch.Tensor] = None, cweight: Optional[torch.Tensor] = None, normals: bool = True):
+    """pmn_mt_count + scan + pmn_mt_emit: the iso-surface tsdf = 0 of a volume by marching tetrahedra.
+    Returns (vertices [Nv,3] float32, faces [Nt,3] int32, colors [Nv,3] uint8 or None (with rgb / cweight), normals [Nv,3] float32
+    or None), on the volume's device; vertices ordered by owning sample then edge class, faces by cell, tetrahedron, triangle.  The two
+    scans are torch.cumsum on the device; ONE host read (the two totals, to size the outputs) is the only synchronisation."""
+    dims, dims_p = _volume_planes(tsdf, weight, rgb, cweight, "mt_extract")
+    org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
+    if not np.isfinite(org).all():
+        raise PmnError("mt_extract: origin must be finite")
+    voxel = _positive_f32(voxel, "mt_extract: voxel")
+    min_weight = float(np.float32(min_weight))
+    if not np.isfinite(min_weight):
+        raise PmnError("mt_extract: min_weight must be finite")
+    dev = tsdf.device
+    vmask = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
+    ntri = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L = _lib.lib()
+        check(L.pmn_mt_count(tsdf.data_ptr(), weight.data_ptr(), dims_p, min_weight, vmask.data_ptr(), ntri.data_ptr(), _stream(tsdf)),
+              "pmn_mt_count")
+        vcount = _popcount_u8(vmask)
+        totals = torch.stack((vcount.sum(dtype=torch.int64), ntri.sum(dtype=torch.int64))).tolist()  # the feature's one host read
+        nv, nt = int(totals[0]), int(totals[1])
+        if nv > 2 ** 31 - 1 or nt > 2 ** 31 - 1:
+            raise PmnError(f"mt_extract: {nv} vertices / {nt} triangles do not fit int32 indices; use a larger voxel")
+        vscan = torch.cumsum(vcount.reshape(-1), 0, dtype=torch.int32)
+        tscan = torch.cumsum(ntri.reshape(-1), 0, dtype=torch.int32)
+        del vcount
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        colors = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if rgb is not None else None
+        nrm = torch.empty((nv, 3), dtype=torch.float32, device=dev) if normals else None
+        if nv:
+            check(L.pmn_mt_emit(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), dims_p, org_p, voxel, min_weight,
+                                vmask.data_ptr(), ntri.data_ptr(), vscan.data_ptr(), tscan.data_ptr(), vertices.data_ptr(),
+                                _ptr(colors), _ptr(nrm), faces.data_ptr(), _stream(tsdf)), "pmn_mt_emit")
+    del dims, org
+    return vertices, faces, colors, nrm
+
+
 class PointPacker:
     """pmn_pack_points: the PLY vertex records of a scan's fused reference views, packed on the device view after view into ONE
     record buffer (reference eval.py:270-297).  ``capacity`` = room in points (a view can keep at most H*W).

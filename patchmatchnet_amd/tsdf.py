@@ -1,0 +1,206 @@
+"""A surface mesh from a scan's depth maps: a dense truncated-signed-distance volume integrated on the device
+(pmn_tsdf_integrate), its iso-surface by marching tetrahedra (pmn_mt_count / pmn_mt_emit), the grid heuristics of mesh.py and the PLY
+mesh files.  There is no CPU path: the volume refuses a host device."""
+from __future__ import annotations
+
+import os
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, fusion, ops
+from ._lib import PmnError
+
+MAX_VOXELS = 2 ** 29  # mesh.py --max_voxels: 24 B per sample with colour = 12.9 GB
+
+
+class TsdfVolume:
+    """nx x ny x nz samples, sample (i,j,k) at origin + (i,j,k) * voxel (world units); planes tsdf (1), weight (0) and, with
+    ``color``, rgb and cweight (0), all float32 on ``device``."""
+
+    def __init__(self, origin, voxel: float, dims: Sequence[int], trunc: float, device, color: bool = True) -> None:
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise PmnError(f"TsdfVolume: device {device} is not a ROCm GPU (no CPU fallback)")
+        nx, ny, nz = (int(d) for d in dims)
+        if min(nx, ny, nz) < 2 or nz > 65535 or nx * ny * nz > 2 ** 31 - 1:
+            raise PmnError(f"TsdfVolume: dims {nx} x {ny} x {nz} must be >= 2 per axis, nz <= 65535, fewer than 2^31 samples")
+        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
+        self.voxel, self.trunc, self.dims, self.device = float(np.float32(voxel)), float(np.float32(trunc)), (nx, ny, nz), device
+        if not (np.isfinite(self.origin).all() and np.isfinite(self.voxel) and self.voxel > 0 and np.isfinite(self.trunc) and self.trunc > 0):
+            raise PmnError("TsdfVolume: origin must be finite, voxel and trunc positive and finite")
+        self.tsdf = torch.ones((nz, ny, nx), dtype=torch.float32, device=device)
+        self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device)
+        self.rgb = torch.zeros((3, nz, ny, nx), dtype=torch.float32, device=device) if color else None
+        self.cweight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device) if color else None
+
+    def integrate(self, maps: torch.Tensor, slots: Sequence[int], sizes: Sequence[Tuple[int, int]], cams, masks=None, images=None,
+                  batch: int = 8) -> None:
+        """Folds the views in, ``batch`` per launch, in the given order (see ops.tsdf_integrate for the arguments; any batch size
+        leaves the same bits)."""
+        if not 1 <= int(batch) <= _lib.TSDF_MAX_VIEWS:
+            raise PmnError(f"TsdfVolume.integrate: batch must be 1 .. {_lib.TSDF_MAX_VIEWS}")
+        cams = np.asarray(cams, np.float32).reshape(len(slots), 21)
+        for a in range(0, len(slots), int(batch)):
+            b = min(a + int(batch), len(slots))
+            ops.tsdf_integrate(self.tsdf, self.weight, self.rgb, self.cweight, self.origin, self.voxel, self.trunc, maps, slots[a:b],
+                               sizes[a:b], cams[a:b], None if masks is None else masks[a:b],
+                               None if images is None or self.rgb is None else images[a:b])
+
+    def extract(self, min_weight: float = 1.0, normals: bool = True):
+        """(vertices [Nv,3] float32, faces [Nt,3] int32, colors [Nv,3] uint8 | None, normals [Nv,3] float32 | None) on the device."""
+        return ops.mt_extract(self.tsdf, self.weight, self.origin, self.voxel, min_weight, self.rgb, self.cweight, normals)
+
+
+def camera21(K, E) -> np.ndarray:
+    """The 21 floats pmn_tsdf_integrate reads per view: K row-major (at the MAP's size), then the upper 3x4 of the extrinsic."""
+    return np.concatenate((np.asarray(K, np.float32).reshape(9), np.asarray(E, np.float32)[:3, :4].reshape(12)))
+
+
+def backproject(depth: torch.Tensor, mask: Optional[torch.Tensor], K, E, stride: int = 1):
+    """World points [n,3] (float32, on the device) and depth / fx [n] of the valid (finite, > 0, mask != 0) pixels of one view, every
+    ``stride``-th pixel per axis: the evidence choose_grid sizes the volume from (elementwise torch: plumbing, not a kernel)."""
+    h, w = depth.shape
+    d = depth[::stride, ::stride]
+    ok = torch.isfinite(d) & (d > 0)
+    if mask is not None:
+        ok &= mask[::stride, ::stride] != 0
+    v, u = torch.meshgrid(torch.arange(0, h, stride, device=depth.device, dtype=torch.float32),
+                          torch.arange(0, w, stride, device=depth.device, dtype=torch.float32), indexing="ij")
+    K64, E64 = np.asarray(K, np.float64), np.asarray(E, np.float64)
+    Kinv = torch.from_numpy(np.linalg.inv(K64)).to(depth.device, torch.float32)
+    Einv = torch.from_numpy(np.linalg.inv(E64)).to(depth.device, torch.float32)
+    z = d[ok]
+    pix = torch.stack((u[ok], v[ok], torch.ones_like(z)), 1)
+    cam = (pix @ Kinv.T) * z[:, None]
+    return cam @ Einv[:3, :3].T + Einv[:3, 3], z / float(K64[0, 0])
+
+
+def choose_grid(points: torch.Tensor, footprint: Optional[torch.Tensor] = None, voxel: Optional[float] = None,
+                trunc: Optional[float] = None, bounds: Optional[Sequence[float]] = None, max_voxels: int = MAX_VOXELS):
+    """Bounds and voxel size for a scan -> (origin float32[3], voxel, trunc, (nx, ny, nz), note).  ``points`` [n,3] are the
+    back-projected masked pixels, ``footprint`` [n] their depth / fx.  voxel defaults to 2 x the median footprint (a sample is then
+    seen by several pixels' worth of evidence), trunc to 4 x voxel, the box to the 1st..99th percentile of the points per axis grown by
+    trunc on every side (``bounds`` = xmin ymin zmin xmax ymax zmax is taken as given).  If the lattice would exceed ``max_voxels``
+    samples the voxel grows (trunc with it, when trunc was not given) and ``note`` says so; it is None otherwise.  Works on any device
+    (a sort per axis)."""
+    if voxel is None:
+        if footprint is None or footprint.numel() == 0:
+            raise PmnError("choose_grid: no valid pixel to size the voxel from")
+        voxel = 2.0 * float(footprint.float().median())
+    voxel = float(voxel)
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise PmnError("choose_grid: voxel must be positive and finite")
+    auto_trunc = trunc is None
+    trunc = 4.0 * voxel if auto_trunc else float(trunc)
+    if not (np.isfinite(trunc) and trunc > 0):
+        raise PmnError("choose_grid: trunc must be positive and finite")
+    if bounds is None:
+        if points is None or points.numel() == 0:
+            raise PmnError("choose_grid: no valid pixel to bound the volume with")
+        srt = torch.sort(points.float(), 0).values
+        n = srt.shape[0]
+        lo = srt[int(np.floor(0.01 * (n - 1)))].tolist()
+        hi = srt[int(np.ceil(0.99 * (n - 1)))].tolist()
+        grow = True
+    else:
+        if len(bounds) != 6 or not np.isfinite(np.asarray(bounds, float)).all() or any(bounds[c + 3] <= bounds[c] for c in range(3)):
+            raise PmnError("choose_grid: bounds must be xmin ymin zmin xmax ymax zmax with max > min")
+        lo, hi, grow = list(bounds[:3]), list(bounds[3:]), False
+    note = None
+    while True:
+        g = trunc if grow else 0.0
+        dims = tuple(max(int(np.ceil((hi[c] - lo[c] + 2 * g) / voxel)) + 1, 2) for c in range(3))
+        if dims[0] * dims[1] * dims[2] <= max_voxels and dims[2] <= 65535:
+            break
+        factor = max((dims[0] * dims[1] * dims[2] / float(max_voxels)) ** (1.0 / 3.0), 1.01)
+        voxel *= factor
+        if auto_trunc:
+            trunc = 4.0 * voxel
+        note = "the grid would exceed --max_voxels %d: voxel enlarged to %.6g%s" % (max_voxels, voxel,
+                                                                                  " (trunc %.6g)" % trunc if auto_trunc else "")
+    g = trunc if grow else 0.0
+    origin = np.asarray([lo[c] - g for c in range(3)], np.float32)
+    return origin, voxel, trunc, dims, note
+
+
+# ---- files ---------------------------------------------------------------------------------------------------------------------
+
+PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])  # property list uchar int vertex_indices: 13 bytes
+
+
+def mesh_header(nv: int, nf: int, colors: bool, normals: bool) -> bytes:
+    h = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % nv
+    if normals:
+        h += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors:
+        h += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    return (h + "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % nf).encode("ascii")
+
+
+def _vertex_dtype(colors: bool, normals: bool) -> np.dtype:
+    if colors:
+        return fusion.PLY_VERTEX_NORMALS if normals else fusion.PLY_VERTEX
+    names = ("x", "y", "z", "nx", "ny", "nz") if normals else ("x", "y", "z")
+    return np.dtype([(n, "<f4") for n in names])
+
+
+def write_ply_mesh(path: str, vertices, faces, colors=None, normals=None) -> None:
+    """Binary little-endian PLY: the vertex element of fusion.write_ply (x y z [nx ny nz] [red green blue]) followed by
+    ``element face`` with ``property list uchar int vertex_indices`` (13 bytes per triangle).  Arrays or tensors."""
+    host = lambda a: None if a is None else (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+    vertices, faces, colors, normals = host(vertices), host(faces), host(colors), host(normals)
+    n = len(vertices)
+    if faces.ndim != 2 or faces.shape[1] != 3 or (len(faces) and (faces.min() < 0 or faces.max() >= n)):
+        raise ValueError("write_ply_mesh: faces must be [m,3] indices into the vertices")
+    if colors is not None:
+        rec = fusion.ply_records(vertices, colors, normals)
+    else:
+        rec = np.empty(n, _vertex_dtype(False, normals is not None))
+        raw = rec.view(np.uint8).reshape(n, rec.dtype.itemsize)
+        raw[:, :12] = np.ascontiguousarray(vertices, "<f4").view(np.uint8).reshape(n, 12)
+        if normals is not None:
+            raw[:, 12:24] = np.ascontiguousarray(normals, "<f4").view(np.uint8).reshape(n, 12)
+    frec = np.empty(len(faces), PLY_FACE)
+    frec["n"] = 3
+    frec["v"] = faces
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(mesh_header(n, len(faces), colors is not None, normals is not None))
+        rec.tofile(f)
+        frec.tofile(f)
+
+
+def read_ply_mesh(path: str):
+    """(vertices [n,3] float32, faces [m,3] int32, colors [n,3] uint8 | None, normals [n,3] float32 | None) of a file
+    write_ply_mesh wrote; ValueError (naming the file) for anything else."""
+    with open(path, "rb") as f:
+        lines = []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: PLY header has no end_header")
+            lines.append(line.decode("ascii", "replace").strip())
+            if lines[-1] == "end_header":
+                break
+        if lines[:2] != ["ply", "format binary_little_endian 1.0"] or not lines[2].startswith("element vertex "):
+            raise ValueError(f"{path}: not a binary little-endian PLY mesh")
+        nv = int(lines[2].split()[2])
+        at = [n for n, ln in enumerate(lines) if ln.startswith("element face ")]
+        if len(at) != 1 or lines[at[0] + 1:] != ["property list uchar int vertex_indices", "end_header"]:
+            raise ValueError(f"{path}: expected one face element with 'property list uchar int vertex_indices'")
+        nf = int(lines[at[0]].split()[2])
+        props = [ln.split()[1:] for ln in lines[3:at[0]]]
+        names = tuple(p[1] for p in props)
+        colors, normals = names[-3:] == ("red", "green", "blue"), names[3:6] == ("nx", "ny", "nz")
+        dt = _vertex_dtype(colors, normals)
+        if names != dt.names:
+            raise ValueError(f"{path}: vertex properties {names} are not a mesh this library writes")
+        rec = np.fromfile(f, dt, nv)
+        frec = np.fromfile(f, PLY_FACE, nf)
+        if len(rec) != nv or len(frec) != nf or (nf and (frec["n"] != 3).any()):
+            raise ValueError(f"{path}: truncated, or a face that is not a triangle")
+    col = lambda *k: np.stack([rec[n] for n in k], 1) if nv else np.zeros((0, 3), rec.dtype[k[0]])
+    return (col("x", "y", "z"), np.ascontiguousarray(frec["v"]), col("red", "green", "blue") if colors else None,
+            col("nx", "ny", "nz") if normals else None)
