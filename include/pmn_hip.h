@@ -46,6 +46,9 @@ extern "C" {
 #define PMN_MAX_NEIGHBORS 17
 #define PMN_MAX_FUSE_SRC 32
 #define PMN_TSDF_MAX_VIEWS 16 /* views of one pmn_tsdf_integrate launch */
+#define PMN_RASTER_MAX_DIM 16384 /* largest height / width of a rendered view: the guard band of pmn_raster_triangles in pixels */
+#define PMN_RASTER_MAX_BOX 64    /* pixels of a triangle's bounding box up to which one thread draws it (max_box = 0) */
+#define PMN_SPLAT_MAX_RADIUS 32  /* largest footprint radius of pmn_splat_points in pixels */
 
 #define PMN_OK 0
 #define PMN_ERR_ARG (-1)     /* null pointer / size out of range */
@@ -505,6 +508,52 @@ int pmn_mt_emit(const float *tsdf, const float *weight, const float *rgb, const 
                 const float *origin_host, float voxel, float min_weight, const unsigned char *vertex_mask,
                 const unsigned char *cell_triangles, const int *vertex_scan, const int *triangle_scan, float *vertices,
                 unsigned char *colors, float *normals, int *faces, void *stream);
+
+/* Added under ABI 25 (purely additive, as above).  A mesh or a cloud drawn into one camera (the reference has no
+ * renderer; tests/render_ref.py is the numpy form).  cam_host: HOST float[21] = K row-major at the OUTPUT's size, then the upper 3 x 4 of
+ * the world-to-camera extrinsic row-major (tsdf.camera21), all finite.  1 <= h, w <= PMN_RASTER_MAX_DIM, else PMN_ERR_SHAPE.
+ *
+ * keys: DEVICE uint64 [h][w], set to all ones by the caller; key = (uint64)float_bits(depth) << 32 | primitive index, updated with one
+ * 64-bit atomic min per covered pixel: the nearest depth wins and, among equal depths, the lowest index -- independent of the order of
+ * the primitives, of the launch shape and of the run.  Several calls may draw into the same keys (the indices are then the caller's to
+ * tell apart).  counters: DEVICE int32[4], zeroed by the caller before EVERY call: [0] primitives with a vertex whose camera-frame
+ * position is not finite or has z <= 0 (or, for a triangle, a vertex index outside [0, n_vertices)), [1] primitives with a vertex
+ * outside the guard band, [2] zero-area triangles, [3] triangles handed to the wave-per-triangle kernel.  Primitives counted in
+ * [0]..[2] are NOT DRAWN; there is no near-plane clipping.
+ *
+ * Projection of a world point p, float32, no contraction, IEEE division:
+ *   pc_r = ((R_r0 p.x + R_r1 p.y) + R_r2 p.z) + t_r;  q_r = (K_r0 pc.x + K_r1 pc.y) + K_r2 pc.z;  u = q.x / q.z;  v = q.y / q.z
+ *   X = rintf(u * 256.0f), Y = rintf(v * 256.0f) (half to even); guard band |X|, |Y| <= 2^22 (16384 px): coordinate differences stay
+ *   within 2^23 and the 64-bit edge functions within 2^47.  Pixel centres are at integer coordinates: P = (256 px, 256 py).
+ * pmn_raster_triangles (vertices [n_vertices][3] float32 world, faces [n_faces][3] int32), all coverage arithmetic in integers:
+ *   orient(a, b, c) = (b.X - a.X)(c.Y - a.Y) - (b.Y - a.Y)(c.X - a.X);  w0 = orient(v1, v2, P), w1 = orient(v2, v0, P),
+ *   w2 = orient(v0, v1, P), area = orient(v0, v1, v2), s = sign(area) (both windings are drawn, area = 0 is dropped).  Edge i (v1->v2,
+ *   v2->v0, v0->v1) with (dx, dy) = s (end - start) is top-left iff dy < 0 or (dy = 0 and dx > 0); P is covered iff for every i
+ *   s w_i > 0, or s w_i = 0 and edge i is top-left.  Depth: b_i = (float)(s w_i) / (float)(s area), c_i = b_i / pc_i.z,
+ *   depth = 1.0f / ((c0 + c1) + c2); written only if 0 < depth < inf.
+ *   A triangle whose bounding box (clipped to the image) holds at most max_box pixels (0 = PMN_RASTER_MAX_BOX) is drawn by one thread;
+ *   a larger one is appended to worklist (DEVICE int32 [n_faces], contents undefined afterwards) and drawn by waves of a second
+ *   kernel (eight per triangle, a lane per pixel).  Two launches, nothing is read back.
+ * pmn_splat_points (points [n_points][3], n_points < 2^31: the index plane is int32): depth = pc.z, index = the point's.  Footprint: the nearest pixel
+ *   ((X + 128) >> 8, (Y + 128) >> 8) always and, with r > 0, every pixel with (256 px - X)^2 + (256 py - Y)^2 <= Rq^2,
+ *   Rq = (int)rintf(r * 256.0f); r = radius_px (0 .. PMN_SPLAT_MAX_RADIUS) or, with radius_world > 0 (then radius_px must be 0),
+ *   fminf((radius_world * K_00) / pc.z, PMN_SPLAT_MAX_RADIUS).  A cloud sparser than its footprint is see-through.  One launch.
+ * pmn_raster_resolve, one thread per pixel: depth [h][w] float32 (0 where the key is untouched), index [h][w] int32 (-1), and, if not
+ *   NULL, rgb [h][w][3] uint8 (0) and normal [h][w][3] float32 camera frame (0).  faces = NULL (n_faces = 0): the primitives were points
+ *   and vertices are the points.  colors [n_vertices][3] uint8 or NULL (then 128), normals [n_vertices][3] float32 world or NULL.  For a
+ *   triangle the winner's c_i are recomputed from the same integers and an attribute a is ((c0 a0 + c1 a1) + c2 a2) * depth
+ *   (perspective-correct), the camera-frame position p likewise from the pc_i; vertex normals are interpolated in the world frame and
+ *   then rotated, n_r = (R_r0 n.x + R_r1 n.y) + R_r2 n.z; without vertex normals n = (pc1 - pc0) x (pc2 - pc0).  A point takes its own
+ *   colour, normal and pc.  n = n / sqrtf((n.x n.x + n.y n.y) + n.z n.z) (0 if that length is 0 or not finite), negated if
+ *   d = (n.x p.x + n.y p.y) + n.z p.z > 0 (COLMAP's convention: the normal faces the camera).  With shade != 0 and a non-zero normal the
+ *   colour is multiplied by |d| / |p| (head-light Lambert); bytes are floorf(c + 0.5f) clamped to 0..255, as pmn_mt_emit rounds. */
+int pmn_raster_triangles(const float *vertices, int n_vertices, const int *faces, int n_faces, const float *cam_host, int h, int w,
+                         long long max_box, unsigned long long *keys, int *counters, int *worklist, void *stream);
+int pmn_splat_points(const float *points, long long n_points, const float *cam_host, int h, int w, float radius_px, float radius_world,
+                     unsigned long long *keys, int *counters, void *stream);
+int pmn_raster_resolve(const unsigned long long *keys, int h, int w, const float *cam_host, const float *vertices, long long n_vertices,
+                       const int *faces, long long n_faces, const unsigned char *colors, const float *normals, int shade, float *depth,
+                       int *index, unsigned char *rgb, float *normal, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1045,6 +1045,117 @@ def mt_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, m
     return vertices, faces, colors, nrm
 
 
+# ---- rendering ---------------------------------------------------------------------------------------------
+
+def _raster_common(keys: torch.Tensor, counters: torch.Tensor, cam, what: str):
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda:
+        raise PmnError(f"{what}: keys must be a tensor on a ROCm GPU (no CPU fallback)")
+    if keys.dtype != torch.int64 or keys.dim() != 2 or not keys.is_contiguous() or keys.numel() == 0:
+        raise PmnError(f"{what}: keys must be a contiguous [h,w] int64 tensor (the uint64 keys' bits)")
+    h, w = keys.shape
+    if h > _lib.RASTER_MAX_DIM or w > _lib.RASTER_MAX_DIM:
+        raise PmnError(f"{what}: a view is at most {_lib.RASTER_MAX_DIM} pixels per side")
+    if not isinstance(counters, torch.Tensor) or counters.device != keys.device or counters.dtype != torch.int32 or \
+            counters.numel() != 4 or not counters.is_contiguous():
+        raise PmnError(f"{what}: counters must be 4 int32 on the keys' device")
+    cam = np.ascontiguousarray(np.asarray(cam, np.float32).reshape(-1))
+    if cam.size != 21 or not np.isfinite(cam).all():
+        raise PmnError(f"{what}: cam must hold 21 finite floats (K, then the upper 3x4 of the extrinsic)")
+    return h, w, cam
+
+
+def _raster_array(t, dtype, keys, name, what, rows=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != keys.device or t.dtype != dtype or t.dim() != 2 or \
+            t.shape[1] != 3 or not t.is_contiguous() or t.shape[0] < 1 or (rows is not None and t.shape[0] != rows):
+        raise PmnError(f"{what}: {name} must be a contiguous [{'n' if rows is None else rows},3] {dtype} tensor on the keys' device "
+                       f"(no CPU fallback)")
+    return t
+
+
+def raster_triangles(vertices: torch.Tensor, faces: torch.Tensor, cam, keys: torch.Tensor, counters: torch.Tensor,
+                     worklist: torch.Tensor, max_box: int = 0) -> None:
+    """pmn_raster_triangles: draws the mesh (vertices [Nv,3] float32 world, faces [Nt,3] int32) into ``keys`` ([h,w] int64 holding
+    the uint64 z-buffer keys, filled with -1 = all ones by the caller) through the camera ``cam`` (tsdf.camera21 at the view's size).
+    ``counters`` int32[4], zeroed by the caller: not drawn because behind the camera / not finite, outside the guard band, zero area;
+    [3] = triangles drawn by the wave-per-triangle kernel.  ``worklist`` int32 [>= Nt] scratch.  ``max_box``: bounding-box pixels up
+    to which one thread draws a triangle (0 = the library's default).  Two launches, no host read."""
+    h, w, cam = _raster_common(keys, counters, cam, "raster_triangles")
+    _raster_array(vertices, torch.float32, keys, "vertices", "raster_triangles")
+    _raster_array(faces, torch.int32, keys, "faces", "raster_triangles")
+    if vertices.shape[0] > 2 ** 31 - 1 or faces.shape[0] > 2 ** 31 - 1:
+        raise PmnError("raster_triangles: at most 2^31 - 1 vertices and faces")
+    if not isinstance(worklist, torch.Tensor) or worklist.device != keys.device or worklist.dtype != torch.int32 or \
+            not worklist.is_contiguous() or worklist.numel() < faces.shape[0]:
+        raise PmnError("raster_triangles: worklist must hold one int32 per face on the keys' device")
+    if int(max_box) < 0:
+        raise PmnError("raster_triangles: max_box must be >= 0")
+    with torch.cuda.device(keys.device):
+        check(_lib.lib().pmn_raster_triangles(vertices.data_ptr(), vertices.shape[0], faces.data_ptr(), faces.shape[0],
+                                              cam.ctypes.data_as(ctypes.c_void_p), h, w, int(max_box), keys.data_ptr(),
+                                              counters.data_ptr(), worklist.data_ptr(), _stream(keys)), "pmn_raster_triangles")
+
+
+def splat_points(points: torch.Tensor, cam, keys: torch.Tensor, counters: torch.Tensor, radius_px: float = 0.0,
+                 radius_world: float = 0.0) -> None:
+    """pmn_splat_points: draws the cloud (points [N,3] float32 world) into ``keys`` (see raster_triangles).  Footprint: the nearest
+    pixel, and with ``radius_px`` (0 .. _lib.SPLAT_MAX_RADIUS) or ``radius_world`` (a disc of radius_world * fx / z pixels, clamped to
+    the same maximum) every pixel whose centre lies in the disc.  One launch."""
+    h, w, cam = _raster_common(keys, counters, cam, "splat_points")
+    _raster_array(points, torch.float32, keys, "points", "splat_points")
+    if points.shape[0] > 2 ** 31 - 1:
+        raise PmnError("splat_points: at most 2^31 - 1 points (the index plane is int32)")
+    with np.errstate(over="ignore"):
+        radius_px, radius_world = float(np.float32(radius_px)), float(np.float32(radius_world))
+    if not (0.0 <= radius_px <= _lib.SPLAT_MAX_RADIUS) or not (np.isfinite(radius_world) and radius_world >= 0.0) or \
+            (radius_px > 0.0 and radius_world > 0.0):
+        raise PmnError(f"splat_points: radius_px must be 0 .. {_lib.SPLAT_MAX_RADIUS}, radius_world >= 0 and finite, and only one "
+                       f"of them non-zero")
+    with torch.cuda.device(keys.device):
+        check(_lib.lib().pmn_splat_points(points.data_ptr(), points.shape[0], cam.ctypes.data_as(ctypes.c_void_p), h, w, radius_px,
+                                          radius_world, keys.data_ptr(), counters.data_ptr(), _stream(keys)), "pmn_splat_points")
+
+
+def raster_resolve(keys: torch.Tensor, cam, vertices: torch.Tensor, faces: Optional[torch.Tensor], depth: torch.Tensor,
+                   index: torch.Tensor, colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                   shade: bool = False, rgb: Optional[torch.Tensor] = None, normal: Optional[torch.Tensor] = None) -> None:
+    """pmn_raster_resolve: turns the keys into depth [h,w] float32 (0 = nothing drawn), index [h,w] int32 (-1) and, if given, rgb
+    [h,w,3] uint8 and normal [h,w,3] float32 (camera frame, facing the camera).  ``faces`` None: the primitives were points.
+    ``colors`` [Nv,3] uint8 / ``normals`` [Nv,3] float32 (world) are per vertex or per point."""
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dtype != torch.int64 or keys.dim() != 2 or \
+            not keys.is_contiguous() or keys.numel() == 0:
+        raise PmnError("raster_resolve: keys must be a contiguous [h,w] int64 tensor on a ROCm GPU (no CPU fallback)")
+    h, w = keys.shape
+    cam = np.ascontiguousarray(np.asarray(cam, np.float32).reshape(-1))
+    if cam.size != 21 or not np.isfinite(cam).all():
+        raise PmnError("raster_resolve: cam must hold 21 finite floats (K, then the upper 3x4 of the extrinsic)")
+    _raster_array(vertices, torch.float32, keys, "vertices", "raster_resolve")
+    nv = vertices.shape[0]
+    if faces is not None:
+        _raster_array(faces, torch.int32, keys, "faces", "raster_resolve")
+    if colors is not None:
+        _raster_array(colors, torch.uint8, keys, "colors", "raster_resolve", nv)
+    if normals is not None:
+        _raster_array(normals, torch.float32, keys, "normals", "raster_resolve", nv)
+
+    def plane(t, dtype, shape, name):
+        if not isinstance(t, torch.Tensor) or t.device != keys.device or t.dtype != dtype or tuple(t.shape) != shape or \
+                not t.is_contiguous():
+            raise PmnError(f"raster_resolve: {name} must be a contiguous {shape} {dtype} tensor on the keys' device")
+        return t
+
+    plane(depth, torch.float32, (h, w), "depth")
+    plane(index, torch.int32, (h, w), "index")
+    if rgb is not None:
+        plane(rgb, torch.uint8, (h, w, 3), "rgb")
+    if normal is not None:
+        plane(normal, torch.float32, (h, w, 3), "normal")
+    with torch.cuda.device(keys.device):
+        check(_lib.lib().pmn_raster_resolve(keys.data_ptr(), h, w, cam.ctypes.data_as(ctypes.c_void_p), vertices.data_ptr(), nv,
+                                            _ptr(faces), 0 if faces is None else faces.shape[0], _ptr(colors), _ptr(normals),
+                                            1 if shade else 0, depth.data_ptr(), index.data_ptr(), _ptr(rgb), _ptr(normal),
+                                            _stream(keys)), "pmn_raster_resolve")
+
+
 class PointPacker:
     """pmn_pack_points: the PLY vertex records of a scan's fused reference views, packed on the device view after view into ONE
     record buffer (reference eval.py:270-297).  ``capacity`` = room in points (a view can keep at most H*W).
