@@ -555,6 +555,58 @@ int pmn_raster_resolve(const unsigned long long *keys, int h, int w, const float
                        const int *faces, long long n_faces, const unsigned char *colors, const float *normals, int shade, float *depth,
                        int *index, unsigned char *rgb, float *normal, void *stream);
 
+/* Added under ABI 25 (purely additive, as above).  The registration, downsample and crop behind the Tanks and Temples F-score (DESIGN.md
+ * section 17; patchmatchnet_amd/registration.py and eval_tnt.py are the callers, tests/tnt_ref.py is the numpy form).  Float64 throughout,
+ * products and sums in the written order, no fused multiply-add.  A pose is pose_host = HOST double[12], row-major 3 x 4 [R | t], finite;
+ * the posed point is p'_r = R_r0 * x + R_r1 * y + R_r2 * z + t_r, evaluated from left to right on the float32 coordinates widened to
+ * float64.  n: 1 .. 2^31 - 65.
+ *
+ * pmn_icp_accumulate: one ICP iteration's search and reduction in one pass.  The first six arguments are pmn_nn_distance's grid (the
+ * TARGET cloud).  For each of the n source points (src [n][3] float32; order as pmn_nn_distance's, NULL = identity) the nearest target
+ * point q of the query p' is found exactly as pmn_nn_distance finds it -- same shell walk, same comparisons; p' is NOT rounded to
+ * float32 -- and a pair whose distance is at or beyond max_dist is no match.  With a = p' - centre and b = (double)q - centre
+ * (centre_host = HOST double[3], finite) sums [PMN_ICP_SUMS] float64 receives over the matched pairs: [0] their number, [1..3] the sum of
+ * a, [4..6] of b, [7..15] of a_i * b_j (row-major, each product rounded once), [16] of |q - p'|^2 = dx * dx + dy * dy + dz * dz.
+ * Every sum is EXACT up to its last step: a term is scaled by a power of two derived on the host from the grid's extent, centre and
+ * max_dist (which bound every term of a matched pair), cut into PMN_ICP_LIMBS signed 32-bit digits and added in 64-bit INTEGERS -- a
+ * wave by a butterfly, a workgroup (one wave, PMN_ICP_BLOCK_POINTS points) into its row of scratch, a second launch over the rows --
+ * and, the carries propagated, the integer total is rounded to float64 ONCE (to nearest, ties to even).  Integer addition is
+ * associative, so sums does not depend on the schedule, on the run, on the launch shape, on the grid's cell or on order, bit for bit;
+ * there are no atomics.  Its error is below half an ulp of the sum + n * 2^-155 * (bound of the sum's terms).  No match at all
+ * gives seventeen zeros.  scratch: DEVICE, PMN_ICP_SCRATCH(n) 8-byte words (scratch_doubles states its size, else PMN_ERR_ARG),
+ * contents undefined before and after.  PMN_ERR_SHAPE if a bound's exponent leaves +-800.  Two launches.
+ *
+ * pmn_voxel_mean: the mean of every run of a sorted grid.  xyz [n][3] float32 and, if not NULL, attr [n][channels] float32
+ * (1 .. PMN_VOXEL_MAX_CHANNELS columns: colours, normals), both in ascending key order; starts [m + 1] int64 = the first index of every
+ * run of equal keys, then n (strictly increasing, starts[0] = 0: the caller's to get right).  Per run and column: the float64 sum of the
+ * run's values divided by its length in float64, rounded to float32 once, into out_xyz [m][3] / out_attr [m][channels].  A run of at most
+ * PMN_VOXEL_LONG_RUN points is summed by one lane in index order, starting from 0.0.  A longer run is summed by a wave: lane l adds
+ * the points l, l + 64, ... of the run in index order to 0.0, and the 64 values meet in the butterfly x_l += x_(l ^ 32), then ^ 16, 8,
+ * 4, 2, 1 -- a fixed tree (tnt_ref.voxel_mean restates it).  One launch.
+ *
+ * pmn_crop_prism: mask [n] uint8 = 1 for the points inside a polygon extruded along a coordinate axis (the toolbox's crop volume).
+ * polygon: DEVICE double [k][2], 3 <= k <= PMN_CROP_MAX_VERTICES (else PMN_ERR_SHAPE), the vertices in cyclic order, given in the two
+ * axes other than axis in ascending order ((y, z) for axis 0, (x, z) for 1, (x, y) for 2).  pose_host, if not NULL, is applied first.
+ * With c the coordinate along axis and (px, py) the other two, a point is inside iff axis_min <= c && c <= axis_max and `inside` is set
+ * after   for i in 0..k-1, j = i - 1 (cyclically):  if ((yi > py) != (yj > py) && px < (xj - xi) * (py - yi) / (yj - yi) + xi)
+ * inside = !inside   (even-odd rule; float64, that order of operations).  One launch. */
+#define PMN_ICP_SUMS 17
+#define PMN_ICP_LIMBS 5
+#define PMN_ICP_BLOCK_POINTS 256
+#define PMN_ICP_BLOCKS(n) (((long long)(n) + PMN_ICP_BLOCK_POINTS - 1) / PMN_ICP_BLOCK_POINTS)
+#define PMN_ICP_SCRATCH(n) (PMN_ICP_BLOCKS(n) * PMN_ICP_SUMS * PMN_ICP_LIMBS)
+#define PMN_VOXEL_LONG_RUN 256
+#define PMN_VOXEL_MAX_CHANNELS 8
+#define PMN_CROP_MAX_VERTICES 4096
+int pmn_icp_accumulate(const float *to_xyz, const long long *to_keys, long long n_to, const double *origin_host, double cell,
+                       const int *dims_host, const float *src, const int *order, long long n, const double *pose_host,
+                       const double *centre_host, double max_dist, double *scratch, long long scratch_doubles, double *sums,
+                       void *stream);
+int pmn_voxel_mean(const float *xyz, const float *attr, int channels, long long n, const long long *starts, long long m, float *out_xyz,
+                   float *out_attr, void *stream);
+int pmn_crop_prism(const float *xyz, long long n, const double *polygon, int k, int axis, double axis_min, double axis_max,
+                   const double *pose_host, unsigned char *mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,12 @@ TSDF_MAX_VIEWS = 16
 RASTER_MAX_DIM = 16384
 RASTER_MAX_BOX = 64
 SPLAT_MAX_RADIUS = 32
+ICP_SUMS = 17
+ICP_LIMBS = 5
+ICP_BLOCK_POINTS = 256
+VOXEL_LONG_RUN = 256
+VOXEL_MAX_CHANNELS = 8
+CROP_MAX_VERTICES = 4096
 
 _fp = ctypes.c_void_p  # device float* (passed as integer address)
 _ip = ctypes.c_void_p
@@ -83,6 +89,10 @@ SIGNATURES = {
     "pmn_raster_triangles": [_fp, _i, _ip, _i, _hp, _i, _i, ctypes.c_longlong, _ip, _ip, _ip, _s],
     "pmn_splat_points": [_fp, ctypes.c_longlong, _hp, _i, _i, _f, _f, _ip, _ip, _s],
     "pmn_raster_resolve": [_ip, _i, _i, _hp, _fp, ctypes.c_longlong, _ip, ctypes.c_longlong, _ip, _fp, _i, _fp, _ip, _ip, _fp, _s],
+    "pmn_icp_accumulate": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, _hp, _hp, ctypes.c_double,
+                           _fp, ctypes.c_longlong, _fp, _s],
+    "pmn_voxel_mean": [_fp, _fp, _i, ctypes.c_longlong, _ip, ctypes.c_longlong, _fp, _fp, _s],
+    "pmn_crop_prism": [_fp, ctypes.c_longlong, _fp, _i, _i, ctypes.c_double, ctypes.c_double, _hp, _ip, _s],
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)
@@ -98,6 +108,11 @@ METRICS_MAX_BLOCKS = 128
 def metrics_scratch(B: int, H: int, W: int) -> int:
     """PMN_METRICS_SCRATCH(B, H, W): float64 elements of pmn_depth_metrics' per-workgroup partial rows."""
     return B * min(METRICS_MAX_BLOCKS, -(-H * W // METRICS_PIXELS_PER_BLOCK)) * METRICS_ROW
+
+def icp_scratch(n: int) -> int:
+    """PMN_ICP_SCRATCH(n): 8-byte words of pmn_icp_accumulate's per-workgroup digit sums."""
+    return -(-n // ICP_BLOCK_POINTS) * ICP_SUMS * ICP_LIMBS
+
 
 # libpmn_hip_experimental.so only (include/pmn_hip_experimental.h; `make -C patchmatchnet_amd/csrc EXPERIMENTAL=1`)
 EXPERIMENTAL_SIGNATURES = {"pmn_set_tuning": [_i, _i],
