@@ -46,6 +46,7 @@ extern "C" {
 #define PMN_MAX_NEIGHBORS 17
 #define PMN_MAX_FUSE_SRC 32
 #define PMN_TSDF_MAX_VIEWS 16 /* views of one pmn_tsdf_integrate launch */
+#define PMN_TSDF_MARK_SPAN 8 /* blocks per axis one pixel of pmn_tsdf_mark_blocks may mark; a larger box is counted, not marked */
 #define PMN_RASTER_MAX_DIM 16384 /* largest height / width of a rendered view: the guard band of pmn_raster_triangles in pixels */
 #define PMN_RASTER_MAX_BOX 64    /* pixels of a triangle's bounding box up to which one thread draws it (max_box = 0) */
 #define PMN_SPLAT_MAX_RADIUS 32  /* largest footprint radius of pmn_splat_points in pixels */
@@ -508,6 +509,50 @@ int pmn_mt_emit(const float *tsdf, const float *weight, const float *rgb, const 
                 const float *origin_host, float voxel, float min_weight, const unsigned char *vertex_mask,
                 const unsigned char *cell_triangles, const int *vertex_scan, const int *triangle_scan, float *vertices,
                 unsigned char *colors, float *normals, int *faces, void *stream);
+
+/* Added under ABI 25 (purely additive, as above).  The same volume stored in blocks: a scene whose dense lattice
+ * would not fit keeps its natural voxel.  dims_host = {nx, ny, nz} is the VIRTUAL lattice, defined as above (2 <= n < 2^19 per axis, so
+ * (float)index is exact); it is cut into blocks of 8 x 8 x 8 samples, nb = ceil(n / 8) per axis, nbx * nby * nbz <= 2^28, else
+ * PMN_ERR_SHAPE.  All arrays are the caller's:
+ *   table  DEVICE int32 [nbz][nby][nbx]  the block's slot in the pool, or -1
+ *   blocks DEVICE int32 [n_blocks]       the linear block index ((bz * nby + by) * nbx + bx) of every slot, ascending;
+ *                                        1 <= n_blocks, n_blocks * 512 < 2^31, else PMN_ERR_SHAPE
+ *   pool   DEVICE float32 tsdf [n_blocks][8][8][8] (initially 1), weight (0) and -- both or neither -- rgb [3][n_blocks][8][8][8] and
+ *          cweight (0); x fastest inside a block
+ * A sample of a border block with an index >= n is outside the lattice: never integrated, never meshed.  A sample outside the lattice or
+ * in a block without a slot reads as tsdf 1, weight 0, cweight 0.
+ *
+ * pmn_tsdf_mark_blocks sets flags (DEVICE uint8 [nbz][nby][nbx], zeroed by the caller once; several calls accumulate) to 1 for every
+ * block that may hold a sample which pmn_tsdf_integrate would map to a valid pixel (finite depth > 0, mask byte non-zero) with
+ * |sdf| <= trunc: per pixel (u, v) of depth d the section of the pyramid through (u +- 0.5, v +- 0.5) between the camera depths
+ * max(d - trunc, 0) and d + trunc is taken to the world, its axis-aligned box grown by one voxel and clipped to the lattice, and every
+ * block the box touches is flagged.  inv_cams_host: HOST float[21 n_views] = K^-1 row-major, then the upper 3 x 4 of the
+ * CAMERA-TO-WORLD matrix E^-1 row-major, inverted by the caller in float64; all finite.  The other view arguments are
+ * pmn_tsdf_integrate's.  A box that touches more than PMN_TSDF_MARK_SPAN blocks on an axis, or has no finite position, is not marked:
+ * it adds 1 to *overflow (DEVICE int32, zeroed by the caller), which the caller reads together with the flags.  The flags are a
+ * superset of the band; the caller dilates them by one block in all 26 directions before it builds table, blocks and pool, which makes
+ * the mesh below the dense one bit for bit (the argument is in DESIGN.md section 18).
+ *
+ * pmn_tsdf_integrate_blocks is pmn_tsdf_integrate on the samples of the listed blocks: the same operations in the same order, so a
+ * pool sample holds the bits the dense volume holds at that lattice index.
+ *
+ * pmn_mt_count_blocks / pmn_mt_emit_blocks are pmn_mt_count / pmn_mt_emit over the pool, with neighbours across block faces found
+ * through table.  min_weight > 0 (else PMN_ERR_ARG): a sample without a slot is unobserved.  vertex_mask, cell_triangles and the two
+ * INCLUSIVE int32 scans are [n_blocks][8][8][8] in pool order; so is the output: vertices by slot, sample within the block (x fastest),
+ * class; triangles by slot, cell, tetrahedron, triangle.  One launch each; no atomics decide a position. */
+int pmn_tsdf_mark_blocks(unsigned char *flags, int *overflow, const int *dims_host, const float *origin_host, float voxel, float trunc,
+                         const float *maps, long long slot_stride, const int *slots_host, const int *hw_host,
+                         const void *const *masks_host, const float *inv_cams_host, int n_views, void *stream);
+int pmn_tsdf_integrate_blocks(float *tsdf, float *weight, float *rgb, float *cweight, const int *blocks, int n_blocks,
+                              const int *dims_host, const float *origin_host, float voxel, float trunc, const float *maps,
+                              long long slot_stride, const int *slots_host, const int *hw_host, const void *const *masks_host,
+                              const void *const *images_host, const float *cams_host, int n_views, void *stream);
+int pmn_mt_count_blocks(const float *tsdf, const float *weight, const int *table, const int *blocks, int n_blocks,
+                        const int *dims_host, float min_weight, unsigned char *vertex_mask, unsigned char *cell_triangles, void *stream);
+int pmn_mt_emit_blocks(const float *tsdf, const float *weight, const float *rgb, const float *cweight, const int *table,
+                       const int *blocks, int n_blocks, const int *dims_host, const float *origin_host, float voxel, float min_weight,
+                       const unsigned char *vertex_mask, const unsigned char *cell_triangles, const int *vertex_scan,
+                       const int *triangle_scan, float *vertices, unsigned char *colors, float *normals, int *faces, void *stream);
 
 /* Added under ABI 25 (purely additive, as above).  A mesh or a cloud drawn into one camera (the reference has no
  * renderer; tests/render_ref.py is the numpy form).  cam_host: HOST float[21] = K row-major at the OUTPUT's size, then the upper 3 x 4 of

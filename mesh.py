@@ -7,7 +7,9 @@
 (depth_est/<id>.pfm|.bin and mask/<id>_final.png).  The masked depth maps of every reference view are integrated into a dense
 truncated-signed-distance volume on the device (pmn_tsdf_integrate) and the iso-surface is extracted by marching tetrahedra
 (pmn_mt_count / pmn_mt_emit): <output>/<scan>/mesh.ply, binary PLY with vertex colours and normals, closed wherever the volume was
-observed.  One process on one ROCm GPU; torchrun is not supported."""
+observed.  --volume sparse keeps only the 8 x 8 x 8-sample blocks near the surface: a scene whose dense lattice
+would exceed --max_voxels keeps its natural voxel, and where both fit the mesh is the dense one.  One process on one ROCm GPU; torchrun
+is not supported."""
 import argparse
 import os
 import sys
@@ -29,6 +31,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("XMIN", "YMIN", "ZMIN", "XMAX", "YMAX", "ZMAX"),
                    help="the volume (default: the 1st-99th percentile box of the back-projected masked pixels grown by trunc)")
     p.add_argument("--max_voxels", type=int, default=2 ** 29, help="largest lattice; a finer grid gets a larger voxel (and says so)")
+    p.add_argument("--volume", type=str, default="dense", choices=("dense", "sparse"),
+                   help="dense: the whole lattice (bounded by --max_voxels); sparse: only the blocks near the surface (--max_blocks)")
+    p.add_argument("--max_blocks", type=int, default=2 ** 20,
+                   help="--volume sparse: largest pool in blocks of 512 samples; a scene that needs more gets a larger voxel (and says so)")
     p.add_argument("--mask", type=str, default="final", choices=("final", "none"), help="which pixels of a depth map count")
     p.add_argument("--min_weight", type=float, default=1.0, help="observations a sample needs for its cells to be meshed")
     p.add_argument("--no_color", action="store_true", help="no colour planes: 8 instead of 24 bytes per sample, no vertex colours")
@@ -87,7 +93,7 @@ def _load_scan(args, scan, device):
 
 def mesh_scan(args, scan, device):
     import torch
-    from patchmatchnet_amd import tsdf
+    from patchmatchnet_amd import PmnError, ops, tsdf
     t0 = time.perf_counter()
     ids, maps, sizes, cam21, masks, images, cams = _load_scan(args, scan, device)
     t1 = time.perf_counter()
@@ -98,13 +104,34 @@ def mesh_scan(args, scan, device):
                                 cams[n]["extrinsics"])
         pts.append(p)
         foot.append(f)
-    origin, voxel, trunc, dims, note = tsdf.choose_grid(torch.cat(pts), torch.cat(foot), args.voxel, args.trunc, args.bounds,
-                                                        args.max_voxels)
-    del pts, foot
+    pts, foot = torch.cat(pts), torch.cat(foot)
     name = scan or args.input_folder
-    if note:
-        print("{}: {}".format(name, note))
-    vol = tsdf.TsdfVolume(origin, voxel, dims, trunc, device, color=not args.no_color)
+    sparse = args.volume == "sparse"
+    if not sparse:
+        origin, voxel, trunc, dims, note = tsdf.choose_grid(pts, foot, args.voxel, args.trunc, args.bounds, args.max_voxels)
+        if note:
+            print("{}: {}".format(name, note))
+        vol = tsdf.TsdfVolume(origin, voxel, dims, trunc, device, color=not args.no_color)
+    else:
+        voxel = args.voxel
+        while True:
+            origin, voxel, trunc, dims, note = tsdf.choose_grid(pts, foot, voxel, args.trunc, args.bounds, tsdf.MAX_VIRTUAL_VOXELS,
+                                                                "the virtual lattice's", ops.SPARSE_MAX_AXIS - 1)
+            if note:
+                print("{}: {}".format(name, note))
+            vol = tsdf.SparseTsdfVolume(origin, voxel, dims, trunc, device, color=not args.no_color, max_blocks=args.max_blocks)
+            try:
+                vol.allocate(maps, list(range(len(ids))), sizes, cam21, masks)
+                break
+            except PmnError:
+                if vol.needed <= args.max_blocks:
+                    raise
+            # the blocks follow the surface, whose area in voxels falls with the square of the voxel
+            voxel *= max((vol.needed / float(args.max_blocks)) ** 0.5, 1.01)
+            print("{}: {} blocks would exceed --max_blocks {}: voxel enlarged to {:.6g}{}".format(
+                name, vol.needed, args.max_blocks, voxel, "" if args.trunc is not None else " (trunc {:.6g})".format(4.0 * voxel)))
+            del vol
+    del pts, foot
     torch.cuda.synchronize(device)
     t2 = time.perf_counter()
     vol.integrate(maps, list(range(len(ids))), sizes, cam21, masks, images, batch=args.views_per_launch)
@@ -116,9 +143,13 @@ def mesh_scan(args, scan, device):
     out = os.path.join(args.output_folder, scan, "mesh.ply")
     tsdf.write_ply_mesh(out, vertices, faces, colors, normals)
     t5 = time.perf_counter()
-    print("{}: grid {} x {} x {} at origin ({:.6g}, {:.6g}, {:.6g}), voxel {:.6g}, trunc {:.6g}, {} views -> {} vertices, {} faces; "
+    blocks = ""
+    if sparse:
+        nb = vol.nblocks[0] * vol.nblocks[1] * vol.nblocks[2]
+        blocks = ", {} of {} blocks allocated ({:.3g} % of the virtual lattice)".format(vol.needed, nb, 100.0 * vol.needed / nb)
+    print("{}: grid {} x {} x {} at origin ({:.6g}, {:.6g}, {:.6g}), voxel {:.6g}, trunc {:.6g}{}, {} views -> {} vertices, {} faces; "
           "load {:.3f} s, grid {:.3f} s, integrate {:.3f} s, extract {:.3f} s, write {:.3f} s -> {}".format(
-              name, dims[0], dims[1], dims[2], origin[0], origin[1], origin[2], voxel, trunc, len(ids), vertices.shape[0],
+              name, dims[0], dims[1], dims[2], origin[0], origin[1], origin[2], voxel, trunc, blocks, len(ids), vertices.shape[0],
               faces.shape[0], t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, out))
 
 
@@ -135,6 +166,8 @@ def main(argv=None) -> int:
     from patchmatchnet_amd import PmnError
     if not 1 <= args.views_per_launch <= 16:
         raise PmnError("--views_per_launch must be 1..16")
+    if args.max_blocks < 1:
+        raise PmnError("--max_blocks must be at least 1")
     device = torch.device(args.device)
     if device.type != "cuda":
         raise PmnError("--device {}: mesh.py runs on a ROCm GPU (no CPU fallback)".format(args.device))

@@ -19,6 +19,7 @@ MAX_DEPTH = 64
 MAX_NEIGHBORS = 17
 MAX_FUSE_SRC = 32
 TSDF_MAX_VIEWS = 16
+TSDF_MARK_SPAN = 8
 RASTER_MAX_DIM = 16384
 RASTER_MAX_BOX = 64
 SPLAT_MAX_RADIUS = 32
@@ -86,6 +87,10 @@ SIGNATURES = {
     "pmn_tsdf_integrate": [_fp] * 4 + [_hp, _hp, _f, _f, _fp, ctypes.c_longlong] + [_hp] * 5 + [_i, _s],
     "pmn_mt_count": [_fp, _fp, _hp, _f, _ip, _ip, _s],
     "pmn_mt_emit": [_fp] * 4 + [_hp, _hp, _f, _f] + [_ip] * 4 + [_fp, _ip, _fp, _ip, _s],
+    "pmn_tsdf_mark_blocks": [_ip, _ip, _hp, _hp, _f, _f, _fp, ctypes.c_longlong] + [_hp] * 4 + [_i, _s],
+    "pmn_tsdf_integrate_blocks": [_fp] * 4 + [_ip, _i, _hp, _hp, _f, _f, _fp, ctypes.c_longlong] + [_hp] * 5 + [_i, _s],
+    "pmn_mt_count_blocks": [_fp, _fp, _ip, _ip, _i, _hp, _f, _ip, _ip, _s],
+    "pmn_mt_emit_blocks": [_fp] * 4 + [_ip, _ip, _i, _hp, _hp, _f, _f] + [_ip] * 4 + [_fp, _ip, _fp, _ip, _s],
     "pmn_raster_triangles": [_fp, _i, _ip, _i, _hp, _i, _i, ctypes.c_longlong, _ip, _ip, _ip, _s],
     "pmn_splat_points": [_fp, ctypes.c_longlong, _hp, _i, _i, _f, _f, _ip, _ip, _s],
     "pmn_raster_resolve": [_ip, _i, _i, _hp, _fp, ctypes.c_longlong, _ip, ctypes.c_longlong, _ip, _fp, _i, _fp, _ip, _ip, _fp, _s],

@@ -118,6 +118,14 @@ def _dlast(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
 
 
+def _dev_as(t: torch.Tensor, name: str, dtype: torch.dtype) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise PmnError(f"{name}: expected a tensor on a ROCm GPU (no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise PmnError(f"{name}: expected a contiguous {dtype} tensor")
+    return t
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -943,6 +951,43 @@ def _positive_f32(v, what):
     return v
 
 
+def _view_args(maps, slots, sizes, cams, masks, images, dev, what):
+    _dev(maps, "maps")
+    if maps.dim() < 2 or maps.device != dev:
+        raise PmnError(f"{what}: maps must be [S,...] slots on the volume's device")
+    S, stride = maps.shape[0], maps[0].numel()
+    V = len(slots)
+    if not 1 <= V <= _lib.TSDF_MAX_VIEWS:
+        raise PmnError(f"{what}: 1 .. {_lib.TSDF_MAX_VIEWS} views per launch, got {V}")
+    if len(sizes) != V or any(not 0 <= int(s) < S for s in slots) or any(h < 1 or w < 1 or h * w > stride for h, w in sizes):
+        raise PmnError(f"{what}: a slot is out of range or a view's depth map does not fit its slot")
+    cam = np.ascontiguousarray(np.asarray(cams, np.float32).reshape(-1))
+    if cam.size != 21 * V or not np.isfinite(cam).all():
+        raise PmnError(f"{what}: cams must hold 21 finite floats per view (K, then the upper 3x4 of the extrinsic)")
+
+    def table(items, shape_of, name):
+        if items is None:
+            return None, None
+        if len(items) != V:
+            raise PmnError(f"{what}: {name} must have one entry (a tensor or None) per view")
+        arr = (ctypes.c_void_p * V)()
+        for n, t in enumerate(items):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != torch.uint8 or \
+                    not t.is_contiguous() or tuple(t.shape) != shape_of(*sizes[n]):
+                raise PmnError(f"{what}: {name}[{n}] must be a contiguous uint8 tensor {shape_of(*sizes[n])} on the volume's device "
+                               f"(no CPU fallback)")
+            arr[n] = t.data_ptr()
+        return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+    m_arr, m_p = table(masks, lambda h, w: (h, w), "masks")
+    i_arr, i_p = table(images, lambda h, w: (h, w, 3), "images")
+    sl, sl_p = _host_i32(np.asarray(list(slots)), V, "slots")
+    hw, hw_p = _host_i32(np.asarray([x for s in sizes for x in s]), 2 * V, "sizes")
+    return V, int(stride), cam, (m_arr, i_arr, sl, hw), sl_p, hw_p, m_p, i_p
+
+
 def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, rgb: Optional[torch.Tensor], cweight: Optional[torch.Tensor], origin,
                    voxel: float, trunc: float, maps: torch.Tensor, slots: Sequence[int], sizes: Sequence[Tuple[int, int]], cams,
                    masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
@@ -954,48 +999,16 @@ def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, rgb: Optional[torch
     (K row-major at map size, then the upper 3x4 of the world-to-camera extrinsic; numpy, read on the host), ``masks[n]`` a uint8
     [h,w] tensor or None, ``images[n]`` a uint8 [h,w,3] tensor or None."""
     dims, dims_p = _volume_planes(tsdf, weight, rgb, cweight, "tsdf_integrate")
-    _dev(maps, "maps")
-    if maps.dim() < 2 or maps.device != tsdf.device:
-        raise PmnError("tsdf_integrate: maps must be [S,...] slots on the volume's device")
-    S, stride = maps.shape[0], maps[0].numel()
-    V = len(slots)
-    if not 1 <= V <= _lib.TSDF_MAX_VIEWS:
-        raise PmnError(f"tsdf_integrate: 1 .. {_lib.TSDF_MAX_VIEWS} views per launch, got {V}")
-    if len(sizes) != V or any(not 0 <= int(s) < S for s in slots) or any(h < 1 or w < 1 or h * w > stride for h, w in sizes):
-        raise PmnError("tsdf_integrate: a slot is out of range or a view's depth map does not fit its slot")
-    cam = np.ascontiguousarray(np.asarray(cams, np.float32).reshape(-1))
-    if cam.size != 21 * V or not np.isfinite(cam).all():
-        raise PmnError("tsdf_integrate: cams must hold 21 finite floats per view (K, then the upper 3x4 of the extrinsic)")
     org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
     if not np.isfinite(org).all():
         raise PmnError("tsdf_integrate: origin must be finite")
     voxel, trunc = _positive_f32(voxel, "tsdf_integrate: voxel"), _positive_f32(trunc, "tsdf_integrate: trunc")
-
-    def table(items, shape_of, name):
-        if items is None:
-            return None, None
-        if len(items) != V:
-            raise PmnError(f"tsdf_integrate: {name} must have one entry (a tensor or None) per view")
-        arr = (ctypes.c_void_p * V)()
-        for n, t in enumerate(items):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != tsdf.device or t.dtype != torch.uint8 or \
-                    not t.is_contiguous() or tuple(t.shape) != shape_of(*sizes[n]):
-                raise PmnError(f"tsdf_integrate: {name}[{n}] must be a contiguous uint8 tensor {shape_of(*sizes[n])} on the volume's "
-                               f"device (no CPU fallback)")
-            arr[n] = t.data_ptr()
-        return arr, ctypes.cast(arr, ctypes.c_void_p)
-
-    m_arr, m_p = table(masks, lambda h, w: (h, w), "masks")
-    i_arr, i_p = table(images, lambda h, w: (h, w, 3), "images")
-    sl, sl_p = _host_i32(np.asarray(list(slots)), V, "slots")
-    hw, hw_p = _host_i32(np.asarray([x for s in sizes for x in s]), 2 * V, "sizes")
+    V, stride, cam, keep, sl_p, hw_p, m_p, i_p = _view_args(maps, slots, sizes, cams, masks, images, tsdf.device, "tsdf_integrate")
     with torch.cuda.device(tsdf.device):
         check(_lib.lib().pmn_tsdf_integrate(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), dims_p, org_p, voxel, trunc,
-                                            maps.data_ptr(), int(stride), sl_p, hw_p, m_p, i_p, cam.ctypes.data_as(ctypes.c_void_p), V,
+                                            maps.data_ptr(), stride, sl_p, hw_p, m_p, i_p, cam.ctypes.data_as(ctypes.c_void_p), V,
                                             _stream(tsdf)), "pmn_tsdf_integrate")
-    del dims, org, m_arr, i_arr, sl, hw
+    del dims, org, keep
 
 
 def _popcount_u8(m: torch.Tensor) -> torch.Tensor:
@@ -1042,6 +1055,156 @@ def mt_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, m
                                 vmask.data_ptr(), ntri.data_ptr(), vscan.data_ptr(), tscan.data_ptr(), vertices.data_ptr(),
                                 _ptr(colors), _ptr(nrm), faces.data_ptr(), _stream(tsdf)), "pmn_mt_emit")
     del dims, org
+    return vertices, faces, colors, nrm
+
+
+# ---- block-sparse volume -----------------------------------------------------------------------------------
+
+SPARSE_BLOCK = 8            # samples per block side
+SPARSE_MAX_AXIS = 2 ** 19   # samples per axis of the virtual lattice (exclusive)
+SPARSE_MAX_TABLE = 2 ** 28  # blocks of the virtual lattice
+SPARSE_MAX_BLOCKS = (2 ** 31 - 1) // SPARSE_BLOCK ** 3  # slots of a pool
+
+
+def sparse_blocks(dims) -> Tuple[int, int, int]:
+    """(nbx, nby, nbz) of a virtual lattice of ``dims`` = (nx, ny, nz) samples; PmnError beyond the limits of include/pmn_hip.h."""
+    nx, ny, nz = (int(d) for d in dims)
+    nb = tuple(-(-n // SPARSE_BLOCK) for n in (nx, ny, nz))
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) >= SPARSE_MAX_AXIS or nb[0] * nb[1] * nb[2] > SPARSE_MAX_TABLE:
+        raise PmnError(f"sparse volume: dims {nx} x {ny} x {nz} must be 2 .. {SPARSE_MAX_AXIS - 1} per axis and at most "
+                       f"{SPARSE_MAX_TABLE} blocks of {SPARSE_BLOCK}^3 samples")
+    return nb
+
+
+def _grid_args(dims, origin, voxel, trunc, what):
+    nb = sparse_blocks(dims)
+    d, d_p = _host_i32(np.asarray([int(x) for x in dims]), 3, "dims")
+    org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
+    if not np.isfinite(org).all():
+        raise PmnError(f"{what}: origin must be finite")
+    return nb, (d, org), d_p, org_p, _positive_f32(voxel, f"{what}: voxel"), None if trunc is None else _positive_f32(trunc, f"{what}: trunc")
+
+
+def inverse_cameras(cams) -> np.ndarray:
+    """[V,21] float32: K^-1 row-major, then the upper 3x4 of the camera-to-world matrix, of [V,21] cameras (tsdf.camera21), inverted in
+    float64; PmnError for a singular or non-finite camera."""
+    cams = np.asarray(cams, np.float32).reshape(-1, 21).astype(np.float64)
+    out = np.empty((len(cams), 21), np.float32)
+    for n, c in enumerate(cams):
+        E = np.eye(4)
+        E[:3] = c[9:].reshape(3, 4)
+        try:
+            with np.errstate(all="ignore"):
+                out[n, :9] = np.linalg.inv(c[:9].reshape(3, 3)).reshape(9)
+                out[n, 9:] = np.linalg.inv(E)[:3].reshape(12)
+        except np.linalg.LinAlgError as e:
+            raise PmnError(f"tsdf_mark_blocks: camera {n} is singular") from e
+    if not np.isfinite(out).all():
+        raise PmnError("tsdf_mark_blocks: a camera has no finite float32 inverse")
+    return out
+
+
+def tsdf_mark_blocks(flags: torch.Tensor, overflow: torch.Tensor, dims, origin, voxel: float, trunc: float, maps: torch.Tensor,
+                     slots: Sequence[int], sizes: Sequence[Tuple[int, int]], cams,
+                     masks: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+    """pmn_tsdf_mark_blocks: sets ``flags`` (uint8 [nbz,nby,nbx], zeroed by the caller; calls accumulate) to 1 for the blocks of the
+    virtual lattice ``dims`` = (nx, ny, nz) near the surface of len(slots) views (1 .. _lib.TSDF_MAX_VIEWS), one launch (DESIGN.md
+    section 18).  ``overflow`` (int32 [1], zeroed by the caller) counts the pixels whose box was too large to mark: read it with the
+    flags.  The view arguments are tsdf_integrate's; the cameras are inverted here, in float64."""
+    _dev_as(flags, "flags", torch.uint8)
+    _dev_as(overflow, "overflow", torch.int32)
+    nb, keep, dims_p, org_p, voxel, trunc = _grid_args(dims, origin, voxel, trunc, "tsdf_mark_blocks")
+    if tuple(flags.shape) != nb[::-1]:
+        raise PmnError(f"tsdf_mark_blocks: flags must be a contiguous uint8 tensor {nb[::-1]} (nbz, nby, nbx)")
+    if overflow.numel() != 1 or overflow.device != flags.device:
+        raise PmnError("tsdf_mark_blocks: overflow must be one int32 on the flags' device")
+    V, stride, cam, keep2, sl_p, hw_p, m_p, _ = _view_args(maps, slots, sizes, cams, masks, None, flags.device, "tsdf_mark_blocks")
+    inv = np.ascontiguousarray(inverse_cameras(cam).reshape(-1))
+    with torch.cuda.device(flags.device):
+        check(_lib.lib().pmn_tsdf_mark_blocks(flags.data_ptr(), overflow.data_ptr(), dims_p, org_p, voxel, trunc, maps.data_ptr(), stride,
+                                              sl_p, hw_p, m_p, inv.ctypes.data_as(ctypes.c_void_p), V, _stream(flags)),
+              "pmn_tsdf_mark_blocks")
+    del keep, keep2
+
+
+def _pool_planes(tsdf, weight, rgb, cweight, blocks, what):
+    _dev(tsdf, "tsdf")
+    _dev(weight, "weight")
+    _dev_as(blocks, "blocks", torch.int32)
+    B = tsdf.shape[0] if tsdf.dim() == 4 else 0
+    shape = (B,) + (SPARSE_BLOCK,) * 3
+    if not 1 <= B <= SPARSE_MAX_BLOCKS or tuple(tsdf.shape) != shape or tuple(weight.shape) != shape or weight.device != tsdf.device:
+        raise PmnError(f"{what}: tsdf and weight must be [B,8,8,8] pool planes on one device, 1 <= B <= {SPARSE_MAX_BLOCKS}")
+    if (rgb is None) != (cweight is None):
+        raise PmnError(f"{what}: rgb and cweight come together or not at all")
+    if rgb is not None:
+        _dev(rgb, "rgb")
+        _dev(cweight, "cweight")
+        if tuple(rgb.shape) != (3,) + shape or tuple(cweight.shape) != shape or rgb.device != tsdf.device or cweight.device != tsdf.device:
+            raise PmnError(f"{what}: rgb must be [3,B,8,8,8] and cweight [B,8,8,8] on the pool's device")
+    if tuple(blocks.shape) != (B,) or blocks.device != tsdf.device:
+        raise PmnError(f"{what}: blocks must be a contiguous int32 [B] tensor on the pool's device")
+    return B
+
+
+def tsdf_integrate_blocks(tsdf: torch.Tensor, weight: torch.Tensor, rgb: Optional[torch.Tensor], cweight: Optional[torch.Tensor],
+                          blocks: torch.Tensor, dims, origin, voxel: float, trunc: float, maps: torch.Tensor, slots: Sequence[int],
+                          sizes: Sequence[Tuple[int, int]], cams, masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                          images: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+    """pmn_tsdf_integrate_blocks: tsdf_integrate on the samples of the blocks ``blocks`` (int32 [B], linear block indices of the virtual
+    lattice ``dims``, ascending) of a pool tsdf / weight [B,8,8,8], rgb [3,B,8,8,8] + cweight or None + None, IN PLACE, one launch: a
+    pool sample ends with the bits the dense volume holds at its lattice index."""
+    B = _pool_planes(tsdf, weight, rgb, cweight, blocks, "tsdf_integrate_blocks")
+    nb, keep, dims_p, org_p, voxel, trunc = _grid_args(dims, origin, voxel, trunc, "tsdf_integrate_blocks")
+    V, stride, cam, keep2, sl_p, hw_p, m_p, i_p = _view_args(maps, slots, sizes, cams, masks, images, tsdf.device, "tsdf_integrate_blocks")
+    with torch.cuda.device(tsdf.device):
+        check(_lib.lib().pmn_tsdf_integrate_blocks(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), blocks.data_ptr(), B,
+                                                   dims_p, org_p, voxel, trunc, maps.data_ptr(), stride, sl_p, hw_p, m_p, i_p,
+                                                   cam.ctypes.data_as(ctypes.c_void_p), V, _stream(tsdf)), "pmn_tsdf_integrate_blocks")
+    del keep, keep2
+
+
+def mt_extract_blocks(tsdf: torch.Tensor, weight: torch.Tensor, table: torch.Tensor, blocks: torch.Tensor, dims, origin, voxel: float,
+                      min_weight: float = 1.0, rgb: Optional[torch.Tensor] = None, cweight: Optional[torch.Tensor] = None,
+                      normals: bool = True):
+    """pmn_mt_count_blocks + scan + pmn_mt_emit_blocks: mt_extract over a pool.  ``table`` int32 [nbz,nby,nbx]
+    holds every block's slot or -1, ``blocks`` int32 [B] every slot's block.  Returns what mt_extract returns, in pool order (slot,
+    sample within the block, class / tetrahedron); as a set of triangles it is the mesh mt_extract gives on the dense planes of the
+    same samples.  min_weight must be > 0 (a sample without a slot is unobserved).  The scans are torch.cumsum over B * 512 entries;
+    one host read of the totals."""
+    B = _pool_planes(tsdf, weight, rgb, cweight, blocks, "mt_extract_blocks")
+    nb, keep, dims_p, org_p, voxel, _ = _grid_args(dims, origin, voxel, None, "mt_extract_blocks")
+    _dev_as(table, "table", torch.int32)
+    if tuple(table.shape) != nb[::-1] or table.device != tsdf.device:
+        raise PmnError(f"mt_extract_blocks: table must be a contiguous int32 tensor {nb[::-1]} (nbz, nby, nbx) on the pool's device")
+    min_weight = float(np.float32(min_weight))
+    if not (np.isfinite(min_weight) and min_weight > 0):
+        raise PmnError("mt_extract_blocks: min_weight must be positive and finite")
+    dev = tsdf.device
+    vmask = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
+    ntri = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L = _lib.lib()
+        check(L.pmn_mt_count_blocks(tsdf.data_ptr(), weight.data_ptr(), table.data_ptr(), blocks.data_ptr(), B, dims_p, min_weight,
+                                    vmask.data_ptr(), ntri.data_ptr(), _stream(tsdf)), "pmn_mt_count_blocks")
+        vcount = _popcount_u8(vmask)
+        totals = torch.stack((vcount.sum(dtype=torch.int64), ntri.sum(dtype=torch.int64))).tolist()  # the one host read
+        nv, nt = int(totals[0]), int(totals[1])
+        if nv > 2 ** 31 - 1 or nt > 2 ** 31 - 1:
+            raise PmnError(f"mt_extract_blocks: {nv} vertices / {nt} triangles do not fit int32 indices; use a larger voxel")
+        vscan = torch.cumsum(vcount.reshape(-1), 0, dtype=torch.int32)
+        tscan = torch.cumsum(ntri.reshape(-1), 0, dtype=torch.int32)
+        del vcount
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        colors = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if rgb is not None else None
+        nrm = torch.empty((nv, 3), dtype=torch.float32, device=dev) if normals else None
+        if nv:
+            check(L.pmn_mt_emit_blocks(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), table.data_ptr(), blocks.data_ptr(),
+                                       B, dims_p, org_p, voxel, min_weight, vmask.data_ptr(), ntri.data_ptr(), vscan.data_ptr(),
+                                       tscan.data_ptr(), vertices.data_ptr(), _ptr(colors), _ptr(nrm), faces.data_ptr(), _stream(tsdf)),
+                  "pmn_mt_emit_blocks")
+    del keep
     return vertices, faces, colors, nrm
 
 

@@ -3,12 +3,18 @@
 tests/synth.py seen from an arc), grids of 256^3, 512^3 and a DTU-like 600 x 600 x 500 box, with colour.
 
     python scripts/tsdf_bench.py [--grids 256,512,dtu] [--views 49] [--views_per_launch 1,4,8,16] [--repeats 5] [--log FILE]
+                                 [--volume dense|sparse|both]
 
 Per grid and batch size: device-event time of the integration of all views (median and spread over --repeats after one warm-up), the
 bytes the phase must move computed from the shapes (24 B per sample read and written once per launch; the depth maps, masks and
 images once per launch set) and the resulting GB/s against the 8.0 TB/s peak / 6.3 TB/s achievable HBM figures of the MI355X; then the
 extraction (count, scan, emit) the same way, with the share of the torch scan.  Kernel times come from a separate
-`rocprofv3 --kernel-trace --stats -- python scripts/tsdf_bench.py --grids 512 --views_per_launch 8 --repeats 2` run."""
+`rocprofv3 --kernel-trace --stats -- python scripts/tsdf_bench.py --grids 512 --views_per_launch 8 --repeats 2` run.
+
+--volume sparse times the block-sparse volume on the same scene and grids -- marking + dilation + list / table /
+pool (allocate), the integration of the allocated blocks and the extraction over the pool -- and reports the blocks allocated, their
+share of the virtual lattice and the pool's bytes; a grid may then be one the dense volume cannot hold (--grids 2048).  ``both`` runs
+the dense figures first, in the same process, for the comparison."""
 import argparse
 import os
 import sys
@@ -38,6 +44,41 @@ def timed(fn, repeats):
     return float(np.median(ms)), float(min(ms)), float(max(ms)), out
 
 
+def sparse_grid(say, args, tsdf, dev, dims, origin, voxel, trunc, maps, sizes, cam21, masks, imgs):
+    V = len(sizes)
+    slots = list(range(V))
+    vol = tsdf.SparseTsdfVolume(origin, voxel, dims, trunc, dev, color=True, max_blocks=2 ** 21)
+    med, lo, hi, B = timed(lambda: vol.allocate(maps, slots, sizes, cam21, masks), args.repeats)
+    nb = vol.nblocks[0] * vol.nblocks[1] * vol.nblocks[2]
+    say("  sparse allocate (mark %d views, dilate, list, table, pool): median %.2f ms (min %.2f, max %.2f); %d blocks marked, %d "
+        "allocated = %.3f %% of %d, pool %.3f GB with colour" % (V, med, lo, hi, vol.marked, B, 100.0 * B / nb, nb, 24 * 512 * B / 1e9))
+    for b in (int(x) for x in args.views_per_launch.split(",")):
+        def run():
+            vol.tsdf.fill_(1)
+            vol.weight.zero_()
+            vol.rgb.zero_()
+            vol.cweight.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            vol.integrate(maps, slots, sizes, cam21, masks, imgs, batch=b)
+            e1.record()
+            return e0, e1
+        ms = []
+        for r in range(args.repeats + 1):
+            e0, e1 = run()
+            torch.cuda.synchronize()
+            if r:
+                ms.append(e0.elapsed_time(e1))
+        launches = -(-V // b)
+        must = launches * 2 * 24 * 512 * B + V * sizes[0][0] * sizes[0][1] * (4 + 1 + 3)
+        say("  sparse integrate %2d views/launch (%2d launches): median %.2f ms (min %.2f, max %.2f, n=%d); must move %.1f GB -> %.0f GB/s"
+            % (b, launches, float(np.median(ms)), min(ms), max(ms), len(ms), must / 1e9, must / float(np.median(ms)) / 1e6))
+    med, lo, hi, out = timed(lambda: vol.extract(1.0, normals=True), args.repeats)
+    say("  sparse extract: %d vertices, %d faces; median %.2f ms (min %.2f, max %.2f)" % (out[0].shape[0], out[1].shape[0], med, lo, hi))
+    del out, vol
+    torch.cuda.empty_cache()
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--grids", default="256,512,dtu")
@@ -47,6 +88,7 @@ def main(argv=None):
     p.add_argument("--height", type=int, default=1200)
     p.add_argument("--width", type=int, default=1600)
     p.add_argument("--log", default="")
+    p.add_argument("--volume", default="dense", choices=("dense", "sparse", "both"))
     args = p.parse_args(argv)
     import synth
     from patchmatchnet_amd import ops, tsdf
@@ -70,11 +112,19 @@ def main(argv=None):
     centre = np.array([0.0, 0.0, 650.0])
     for g in args.grids.split(","):
         dims = (600, 600, 500) if g == "dtu" else (int(g),) * 3
+        torch.cuda.empty_cache()
         voxel = float((extent / (np.array(dims) - 1)).max())
         origin = centre - voxel * (np.array(dims) - 1) / 2
         trunc = 4 * voxel
         n = dims[0] * dims[1] * dims[2]
         say("grid %d x %d x %d (%.2f GB with colour), voxel %.4f, trunc %.4f" % (dims + (24 * n / 1e9, voxel, trunc)))
+        if args.volume != "dense":
+            sparse_grid(say, args, tsdf, dev, dims, origin, voxel, trunc, maps, [(H, W)] * V, cam21, masks, imgs)
+            if args.volume == "sparse":
+                continue
+        if n > 2 ** 31 - 1:
+            say("  dense: the lattice does not fit a dense volume")
+            continue
         vol = tsdf.TsdfVolume(origin, voxel, dims, trunc, dev, color=True)
         for b in (int(x) for x in args.views_per_launch.split(",")):
             def run():
