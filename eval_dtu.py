@@ -5,7 +5,8 @@ evaluations/dtu/BaseEvalMain_web.m + ComputeStat_web.m compute (patchmatchnet_am
 
 --data_path holds Points/stl/stl%03d_total.ply and ObsMask/{ObsMask<scan>_10,Plane<scan>}.mat (or .npz with the same field names).
 A scan's cloud is <ply_path>/<method>%03d_<light>.ply (the reference's naming) or, failing that, <ply_path>/scan<N>/fused.ply (what
-eval.py writes).  Scores go to <results_path>/dtu_scores.json; a scan already there is not recomputed unless --force.
+eval.py writes; --ply_name mesh.ply takes mesh.py's file instead).  With --sample_spacing S a file with faces is scored by points drawn on
+its triangles S apart (meshops.sample_surface), not by its vertices.  Scores go to <results_path>/dtu_scores.json; a scan already there is not recomputed unless --force.
 """
 from __future__ import annotations
 
@@ -30,6 +31,10 @@ def parse_args(argv=None):
     p.add_argument("--dst", type=float, default=0.2, help="minimum distance between points after the reduction")
     p.add_argument("--max_dist", type=float, default=20.0, help="outlier threshold of the statistics")
     p.add_argument("--seed", type=int, default=0, help="seed of the reduction's visiting order")
+    p.add_argument("--ply_name", default="fused.ply", help="the file looked for under <ply_path>/scan<N>/ (mesh.ply: mesh.py's output)")
+    p.add_argument("--sample_spacing", type=float, default=0.0,
+                   help="score points drawn on the triangles of a mesh this far apart (0 = off: the file's vertices)")
+    p.add_argument("--sample_seed", type=int, default=0, help="seed of --sample_spacing's points")
     p.add_argument("--force", action="store_true", help="recompute scans already in dtu_scores.json")
     p.add_argument("--device", default="cuda:0")
     return p.parse_args(argv)
@@ -44,7 +49,7 @@ def scan_inputs(args, scan: int) -> Dict[str, str]:
     obs = os.path.join(args.data_path, "ObsMask")
     want = {
         "ply": [os.path.join(args.ply_path, f"{args.method.lower()}{scan:03d}_{args.light}.ply"),
-                os.path.join(args.ply_path, f"scan{scan}", "fused.ply")],
+                os.path.join(args.ply_path, f"scan{scan}", args.ply_name)],
         "stl": [os.path.join(args.data_path, "Points", "stl", f"stl{scan:03d}_total.ply")],
         "obs_mask": [os.path.join(obs, f"ObsMask{scan}_10.mat"), os.path.join(obs, f"ObsMask{scan}_10.npz")],
         "plane": [os.path.join(obs, f"Plane{scan}.mat"), os.path.join(obs, f"Plane{scan}.npz")],
@@ -62,7 +67,15 @@ def score_scan(args, scan: int, files: Dict[str, str]) -> Dict:
 
     from patchmatchnet_amd import pointcloud as PC
     t0 = time.perf_counter()
-    data = torch.from_numpy(PC.read_ply_vertices(files["ply"])).to(args.device)
+    if args.sample_spacing > 0:
+        from patchmatchnet_amd import PmnError, meshops, render
+        model = render.read_ply_model(files["ply"])
+        if model["faces"] is None or len(model["faces"]) == 0:
+            raise PmnError(f"{files['ply']}: --sample_spacing needs a mesh, this file has no faces")
+        data = meshops.sample_surface(torch.from_numpy(model["vertices"]).to(args.device), torch.from_numpy(model["faces"]).to(args.device),
+                                      spacing=args.sample_spacing, seed=args.sample_seed)[0]
+    else:
+        data = torch.from_numpy(PC.read_ply_vertices(files["ply"])).to(args.device)
     stl = torch.from_numpy(PC.read_ply_vertices(files["stl"])).to(args.device)
     obs, bb, res = PC.load_obs_mask(files["obs_mask"])
     plane = PC.load_plane(files["plane"])
@@ -70,6 +83,8 @@ def score_scan(args, scan: int, files: Dict[str, str]) -> Dict:
     out = PC.dtu_score_scan(data, stl, obs, bb, res, plane, dst=args.dst, max_dist=args.max_dist, seed=args.seed)
     out["seconds"]["read"] = t1 - t0
     out["ply"] = files["ply"]
+    if args.sample_spacing > 0:
+        out["sampled_points"] = int(data.shape[0])
     return out
 
 
@@ -80,11 +95,16 @@ def main(argv=None) -> int:
     os.makedirs(args.results_path, exist_ok=True)
     out_path = os.path.join(args.results_path, "dtu_scores.json")
     settings = {"dst": args.dst, "max_dist": args.max_dist, "seed": args.seed}
+    if args.sample_spacing < 0:
+        raise SystemExit("eval_dtu.py: --sample_spacing must be >= 0")
+    if args.sample_spacing > 0:  # only then: a plain run's file keeps its keys, and the two kinds of scores are never mixed
+        settings.update({"sample_spacing": args.sample_spacing, "sample_seed": args.sample_seed})
+    sampling = ("sample_spacing", "sample_seed")
     scores: Dict[str, Dict] = {}
     if os.path.isfile(out_path) and not args.force:
         with open(out_path) as f:
             old = json.load(f)
-        if all(old.get(k) == v for k, v in settings.items()):
+        if all(old.get(k) == v for k, v in settings.items()) and all(old.get(k) == settings.get(k) for k in sampling):
             scores = old.get("scans", {})
     failed = []
     for scan in args.scans:
@@ -113,4 +133,8 @@ def main(argv=None) -> int:
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    from patchmatchnet_amd import PmnError
+    try:
+        sys.exit(main())
+    except PmnError as e:
+        sys.exit("eval_dtu.py: " + str(e))

@@ -7,7 +7,9 @@
 --dataset_dir holds <Scene>.ply (the ground truth), <Scene>.json (the crop volume), <Scene>_COLMAP_SfM.log (the reference trajectory)
 and <Scene>_trans.txt.  The reconstruction's cameras come from --trajectory LOG or from <mvs_folder>/cams/*_cam.txt; --init_transform
 FILE (a 4 x 4 matrix) replaces the trajectory alignment, --no_registration scores a cloud that already is in the ground truth's frame.
---ply_path may be a mesh: its vertices are read as a cloud.  Scores go to <results_path>/tnt_scores.json.
+--ply_path may be a mesh: its vertices are read as a cloud or, with --sample_spacing S, points drawn on its triangles S apart
+(meshops.sample_surface) are scored: the surface, not the lattice its vertices sit on.  Scores go to
+<results_path>/tnt_scores.json.
 """
 from __future__ import annotations
 
@@ -39,8 +41,13 @@ def parse_args(argv=None):
     p.add_argument("--max_points", type=int, default=RG.MAX_POINTS, help="round C thins both clouds to at most this many points")
     p.add_argument("--hist_max", type=float, default=None, help="cap of the distances and end of the histograms (default 5 tau)")
     p.add_argument("--hist_bins", type=int, default=RG.HIST_BINS)
+    p.add_argument("--sample_spacing", type=float, default=0.0,
+                   help="score points drawn on the triangles of --ply_path (a mesh) this far apart, in its own units (0 = off: the vertices)")
+    p.add_argument("--sample_seed", type=int, default=0, help="seed of --sample_spacing's points")
     p.add_argument("--device", default="cuda:0")
     args = p.parse_args(argv)
+    if args.sample_spacing < 0:
+        p.error("--sample_spacing must be >= 0")
     if args.scene is None:
         args.scene = os.path.basename(os.path.normpath(args.dataset_dir))
     if args.tau is None:
@@ -88,7 +95,16 @@ def main(argv=None) -> int:
 
     from patchmatchnet_amd import _lib, pointcloud as PC, registration as RG
     t0 = time.perf_counter()
-    est = torch.from_numpy(PC.read_ply_vertices(args.ply_path)).to(args.device)
+    if args.sample_spacing > 0:
+        from patchmatchnet_amd import meshops, render
+        model = render.read_ply_model(args.ply_path)
+        if model["faces"] is None or len(model["faces"]) == 0:
+            raise _lib.PmnError(f"{args.ply_path}: --sample_spacing needs a mesh, this file has no faces")
+        est = meshops.sample_surface(torch.from_numpy(model["vertices"]).to(args.device), torch.from_numpy(model["faces"]).to(args.device),
+                                     spacing=args.sample_spacing, seed=args.sample_seed)[0]
+        print("%s: %d points sampled on %d triangles" % (args.ply_path, est.shape[0], len(model["faces"])))
+    else:
+        est = torch.from_numpy(PC.read_ply_vertices(args.ply_path)).to(args.device)
     gt = torch.from_numpy(PC.read_ply_vertices(os.path.join(args.dataset_dir, f"{args.scene}.ply"))).to(args.device)
     volume = None if args.no_crop else RG.read_crop_json(os.path.join(args.dataset_dir, f"{args.scene}.json"))
     init = initial_transform(args)
@@ -106,10 +122,16 @@ def main(argv=None) -> int:
     os.makedirs(args.results_path, exist_ok=True)
     out.update({"scene": args.scene, "ply": args.ply_path, "abi": _lib.ABI_VERSION, "init_transform": init.tolist(),
                 "registration": not args.no_registration, "seconds": {"read": t1 - t0, "score": t2 - t1}})
+    if args.sample_spacing > 0:
+        out.update({"sample_spacing": args.sample_spacing, "sample_seed": args.sample_seed, "sampled_points": int(est.shape[0])})
     with open(os.path.join(args.results_path, "tnt_scores.json"), "w") as f:
         json.dump(out, f, indent=1)
     return 0
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    from patchmatchnet_amd import PmnError
+    try:
+        sys.exit(main())
+    except PmnError as e:
+        sys.exit("eval_tnt.py: " + str(e))

@@ -652,6 +652,44 @@ int pmn_voxel_mean(const float *xyz, const float *attr, int channels, long long 
 int pmn_crop_prism(const float *xyz, long long n, const double *polygon, int k, int axis, double axis_min, double axis_max,
                    const double *pose_host, unsigned char *mask, void *stream);
 
+/* Added under ABI 25 (purely additive, as above).  Operations on an indexed triangle mesh (the reference has none;
+ * patchmatchnet_amd/meshops.py is the caller, tests/meshops_ref.py the numpy form).  faces: DEVICE int32 [n_faces][3] into n_vertices
+ * vertices (vertices: DEVICE float32 [n_vertices][3]); 1 <= n_vertices, n_faces <= 2^31 - 256, else PMN_ERR_SHAPE.  A face with an index
+ * outside [0, n_vertices) is NEVER dereferenced: the kernel that meets it skips it and adds 1 to *invalid (DEVICE int32, zeroed by the
+ * caller), which the caller reads together with the host read it needs anyway.  Integer atomics only; no result depends on the order
+ * of the faces' arrival, on the launch shape or on the run.
+ *
+ * pmn_mesh_components: label [n_vertices] int32 = the SMALLEST vertex index of the vertex's connected component; two vertices are
+ * connected when some face names both, a vertex that no face names is its own component, (a, a, b) unites a and b, (a, a, a) nothing.
+ * n_faces may be 0 (faces is then not read).  Union-find in label itself: an init launch (label[v] = v), a launch with a thread per face
+ * that unites (a, b) and (b, c) -- find both roots, hook the larger root under the smaller with a 32-bit compare-and-swap on the larger
+ * root's slot, on failure go on from the value the swap returned -- and a launch that replaces every entry by its root.  Slots only ever
+ * decrease, so every walk and every retry loop descends and ends whatever it reads, no lane waits for another lane (no lock, no flag, no
+ * spin), and the final root is the component's minimum whatever the interleaving.  All accesses of label in the last two launches are
+ * relaxed agent-scope atomics; path halving is a best-effort store of a smaller ancestor.  Three launches.
+ *
+ * pmn_mesh_face_samples / pmn_mesh_sample: points on the triangles at `density` (finite, > 0) points per unit area, a function of
+ * (mesh, density, seed) alone.  All randomness comes from the splitmix64 finaliser
+ *   mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31        (mod 2^64)
+ *   h(face, k) = mix(mix(seed + G) + (((uint64)face << 32 | k) + 1) * G),  G = 0x9E3779B97F4A7C15
+ *   r1 = (h >> 40) * 2^-24,  r2 = ((h >> 16) & 0xFFFFFF) * 2^-24        (exact in float32, in [0, 1))
+ * Float32, no contraction, IEEE sqrtf, with A, B, C the face's vertices in its order:
+ *   counts[f] (int32 [n_faces]) = floor((double)area * density + (double)u) in float64, u = the r1 of k = 2^32 - 1 (unbiased rounding),
+ *   area = sqrtf((c.x c.x + c.y c.y) + c.z c.z) * 0.5f, c = (B - A) x (C - A) = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z,
+ *   e1.x e2.y - e1.y e2.x); 0 for an area that is not finite or not > 0 and for a face with a bad index; clamped at 2^31 - 1.
+ *   The caller scans the counts (INCLUSIVE, int64: sample_scan [n_faces]) and reads the total n_samples (1 .. 2^31 - 1).
+ *   Sample i (a thread each) belongs to the first face f with sample_scan[f] > i (binary search), k = i - sample_scan[f - 1]:
+ *   s = sqrtf(r1), b0 = 1 - s, b1 = s * (1 - r2), b2 = s * r2;  points [n_samples][3] = (b0 * A + b1 * B) + b2 * C per coordinate;
+ *   face [n_samples] int32 = f; and, if out_colors is not NULL (then colors, uint8 [n_vertices][3], must not be), out_colors
+ *   [n_samples][3] uint8 = the same blend of the bytes as floats, floorf(c + 0.5f) clamped to 0..255, as pmn_mt_emit rounds.
+ *   Samples are ordered by face, then k.  One launch each. */
+int pmn_mesh_components(const int *faces, int n_faces, int n_vertices, int *label, int *invalid, void *stream);
+int pmn_mesh_face_samples(const float *vertices, int n_vertices, const int *faces, int n_faces, double density, unsigned long long seed,
+                          int *counts, int *invalid, void *stream);
+int pmn_mesh_sample(const float *vertices, int n_vertices, const int *faces, int n_faces, const unsigned char *colors,
+                    const long long *sample_scan, long long n_samples, unsigned long long seed, float *points, int *face,
+                    unsigned char *out_colors, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@
 truncated-signed-distance volume on the device (pmn_tsdf_integrate) and the iso-surface is extracted by marching tetrahedra
 (pmn_mt_count / pmn_mt_emit): <output>/<scan>/mesh.ply, binary PLY with vertex colours and normals, closed wherever the volume was
 observed.  --volume sparse keeps only the 8 x 8 x 8-sample blocks near the surface: a scene whose dense lattice
-would exceed --max_voxels keeps its natural voxel, and where both fit the mesh is the dense one.  One process on one ROCm GPU; torchrun
+would exceed --max_voxels keeps its natural voxel, and where both fit the mesh is the dense one.  --min_component_faces N and
+--keep_components K drop the floaters before the file is written: connected components with fewer than N faces, or outside the K
+largest.  One process on one ROCm GPU; torchrun
 is not supported."""
 import argparse
 import os
@@ -39,6 +41,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min_weight", type=float, default=1.0, help="observations a sample needs for its cells to be meshed")
     p.add_argument("--no_color", action="store_true", help="no colour planes: 8 instead of 24 bytes per sample, no vertex colours")
     p.add_argument("--no_normals", action="store_true", help="no vertex normals")
+    p.add_argument("--min_component_faces", type=int, default=0,
+                   help="drop connected components with fewer faces than this (0 = off)")
+    p.add_argument("--keep_components", type=int, default=0,
+                   help="keep only this many connected components, the largest by face count (0 = off)")
     p.add_argument("--views_per_launch", type=int, default=8, help="views integrated per kernel launch (1..16)")
     return p
 
@@ -93,7 +99,7 @@ def _load_scan(args, scan, device):
 
 def mesh_scan(args, scan, device):
     import torch
-    from patchmatchnet_amd import PmnError, ops, tsdf
+    from patchmatchnet_amd import PmnError, meshops, ops, tsdf
     t0 = time.perf_counter()
     ids, maps, sizes, cam21, masks, images, cams = _load_scan(args, scan, device)
     t1 = time.perf_counter()
@@ -138,6 +144,13 @@ def mesh_scan(args, scan, device):
     torch.cuda.synchronize(device)
     t3 = time.perf_counter()
     vertices, faces, colors, normals = vol.extract(args.min_weight, normals=not args.no_normals)
+    cleaned = None
+    if args.min_component_faces > 0 or args.keep_components > 0:
+        nv0, nf0 = vertices.shape[0], faces.shape[0]
+        vertices, faces, colors, normals, (found, kept) = meshops.remove_components(
+            vertices, faces, colors, normals, min_faces=args.min_component_faces, keep_largest=args.keep_components, return_counts=True)
+        cleaned = "{}: {} components, {} kept; {} vertices and {} faces dropped".format(
+            name, found, kept, nv0 - vertices.shape[0], nf0 - faces.shape[0])
     torch.cuda.synchronize(device)
     t4 = time.perf_counter()
     out = os.path.join(args.output_folder, scan, "mesh.ply")
@@ -151,6 +164,8 @@ def mesh_scan(args, scan, device):
           "load {:.3f} s, grid {:.3f} s, integrate {:.3f} s, extract {:.3f} s, write {:.3f} s -> {}".format(
               name, dims[0], dims[1], dims[2], origin[0], origin[1], origin[2], voxel, trunc, blocks, len(ids), vertices.shape[0],
               faces.shape[0], t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, out))
+    if cleaned:
+        print(cleaned)
 
 
 def main(argv=None) -> int:
@@ -168,6 +183,8 @@ def main(argv=None) -> int:
         raise PmnError("--views_per_launch must be 1..16")
     if args.max_blocks < 1:
         raise PmnError("--max_blocks must be at least 1")
+    if args.min_component_faces < 0 or args.keep_components < 0:
+        raise PmnError("--min_component_faces and --keep_components must be >= 0")
     device = torch.device(args.device)
     if device.type != "cuda":
         raise PmnError("--device {}: mesh.py runs on a ROCm GPU (no CPU fallback)".format(args.device))

@@ -98,6 +98,9 @@ SIGNATURES = {
                            _fp, ctypes.c_longlong, _fp, _s],
     "pmn_voxel_mean": [_fp, _fp, _i, ctypes.c_longlong, _ip, ctypes.c_longlong, _fp, _fp, _s],
     "pmn_crop_prism": [_fp, ctypes.c_longlong, _fp, _i, _i, ctypes.c_double, ctypes.c_double, _hp, _ip, _s],
+    "pmn_mesh_components": [_ip, _i, _i, _ip, _ip, _s],
+    "pmn_mesh_face_samples": [_fp, _i, _ip, _i, ctypes.c_double, ctypes.c_ulonglong, _ip, _ip, _s],
+    "pmn_mesh_sample": [_fp, _i, _ip, _i, _ip, _ip, ctypes.c_longlong, ctypes.c_ulonglong, _fp, _ip, _ip, _s],
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)
