@@ -1,0 +1,723 @@
+"""The convolution kernel space: one row per call of the convolution-side entry points (pmn_conv2d, pmn_conv2d_mfma, pmn_conv2d_f16s,
+pmn_conv2d_f16s_pair, pmn_offset_heads_f16s, pmn_fpn_level, pmn_fpn_tail, pmn_deconv3x3s2, pmn_stem, pmn_stem_f16s,
+pmn_stem_f16s_views, pmn_refine_front, pmn_refine_tail, pmn_refine_fused), each naming the kernel instantiation its shape selects.
+Rows use the smallest shapes at which these kernels can go wrong: 1x1 (2x2 where the ABI wants even sizes) and 3x5 images, exactly
+one tile / one pixel short / one past (16x16; 16x32 for the f16s stem; 14x14 for the pair kernel), odd and even sizes under stride 2,
+tile counts below, at and past the 8-way pmn_xcd_tile remap with N = 1, 2, 3, offset heads on images smaller than their dilation,
+relu 0 and 1, BatchNorm-folded and bias-only weights, image bases off by one float, two depth ranges.  Every row fits in 64x64
+pixels; the two conv_kernel<..., TP = 4, ...> rows need N*Ho*Wo >= 1,500,000 (launch_conv in csrc/conv.hip: `pix >= 1500000L`): the
+cin = 1 row is THE large row (1 x 1200 x 1250 = exactly the threshold, Wo % 4 == 2); the cin = 3 instantiation can be reached by no
+smaller workload either, so it gets a second row of that size, 379 images of 64x62 (1,503,872 pixels).
+
+Plain helper module (no tests here): tests/test_conv_space.py checks the table on the CPU, tests/test_conv_space_gpu.py runs every
+row on the device against tests/conv_ref64.py."""
+from __future__ import annotations
+
+import ctypes
+import functools
+import json
+import os
+import subprocess
+import sys
+import zlib
+from dataclasses import dataclass, replace
+from typing import Dict, List, Tuple
+
+import numpy as np
+
+import conv_ref64 as R
+import kernel_space as KS
+
+Env = Tuple[Tuple[str, str], ...]
+E_S0C8: Env = (("PMN_CONV_CC5", "8"), ("PMN_CONV_SPLIT", "0"))
+E_C8: Env = (("PMN_CONV_CC5", "8"),)
+# conv_tiled_kernel<32, 4, 64, 64, 5, 2, false, false> needs PMN_CONV_SPLIT=0 with PMN_CONV_CC5 unset (pmn_conv2d: `cc5 == 4 && K == 5`
+# after the split64 == 32 block is skipped): a third environment, so the device test starts three child processes, not two.
+E_S0: Env = (("PMN_CONV_SPLIT", "0"),)
+ENVS = (E_S0C8, E_C8, E_S0)
+
+
+@dataclass(frozen=True)
+class Row:
+    op: str                  # conv2d | mfma1x1 | f16s | pair | heads | fpn_level | fpn_tail | deconv | stem | stem_f16s | stem_views |
+    #                          refine_front | refine_tail | refine_fused
+    kernel: str              # the instantiation this row selects (readable form; mangle() gives the symbol)
+    N: int = 1
+    H: int = 16              # input size (deconv: the half-resolution input; refine: the full-resolution output)
+    W: int = 16
+    cin: int = 0
+    cout: int = 0
+    K: int = 3
+    S: int = 1
+    pad: int = 1
+    dil: int = 1
+    relu: int = 1
+    bn: bool = True          # BatchNorm-folded weights (False: bias only)
+    ca: int = 0              # split outputs: channels of the first
+    up: bool = False         # an x2 bilinearly up-sampled map is added
+    nchw_in: bool = False
+    planar: bool = False     # planar [N,C,H,W] output
+    misalign: bool = False   # image base off by one float: the scalar-staging kernel, same bits as the aligned call
+    views: int = 0           # stem_views: N = views * B
+    env: Env = ()            # PMN_CONV_SPLIT / PMN_CONV_CC5 of the process that runs the row (read once per process)
+    large: bool = False      # the one large row
+    res_max: float = 0.0     # refine_tail / refine_fused: conv3 and res weights are scaled so that max |res| is this, in normalised depth
+    device_only: bool = False  # > 48 KB of dynamic LDS: recording needs a device
+    seed: int = 0
+
+    @property
+    def id(self) -> str:
+        k = self.kernel.replace(" ", "").replace("true", "T").replace("false", "F")
+        e = "".join(f"-{a[4:]}{b}" for a, b in self.env)
+        return f"{self.op}-{k}-{self.N}x{self.H}x{self.W}{'-mis' if self.misalign else ''}{e}-s{self.seed}"
+
+
+def _b(v: bool) -> str:
+    return "true" if v else "false"
+
+
+def _t(cin, cc, co, cop, k, s, planar=False, up=False) -> str:
+    return f"conv_tiled_kernel<{cin}, {cc}, {co}, {cop}, {k}, {s}, {_b(planar)}, {_b(up)}>"
+
+
+# (H, W, N).  First half: 1x1, 3x5, one tile, one short, a strip.  Second half: one past (4 tiles x 2 = 8), 18 = 8 * 2 + 2 tiles,
+# 12 tiles, 8 tiles, tall (8 tiles).  A kernel's rows alternate between the halves (add() below).
+SZ = [(1, 1, 1), (3, 5, 2), (16, 16, 1), (15, 15, 3), (7, 40, 1), (17, 17, 2), (17, 33, 3), (33, 49, 1), (32, 64, 1), (64, 9, 2)]
+SZ_EVEN = [(2, 2, 1), (16, 16, 1), (14, 14, 3), (6, 40, 2), (18, 18, 2), (18, 34, 3), (34, 50, 1), (32, 64, 1)]
+
+
+def _key(op, kernel, env=(), misalign=False) -> str:
+    return f"{op}|{kernel}|{env}|{int(misalign)}"
+
+
+def _rows() -> List[Row]:
+    rows: List[Row] = []
+    count: Dict[str, int] = {}
+
+    def add(op, kernel, sizes=SZ, n=1, **kw):
+        """n rows of one kernel.  Sizes, relu and BatchNorm / bias come from a hash of the kernel and the row's index j among that
+        kernel's rows, never from its place in the table, so an edit elsewhere leaves them alone: sizes alternate between the two
+        halves of ``sizes`` (an image of at most a tile, then one of several tiles), relu alternates with j, bn with j // 2."""
+        key = _key(op, kernel, kw.get("env", ()))
+        h = zlib.crc32(key.encode())
+        half = len(sizes) // 2
+        for _ in range(n):
+            j = count.get(key, 0)
+            count[key] = j + 1
+            H, W, N = sizes[(h + half * (j % 2) + j // 2) % len(sizes)]
+            d = dict(H=H, W=W, N=N, relu=((h >> 8) + j) % 2, bn=((h >> 9) + j // 2) % 2 == 0)
+            d.update(kw)
+            rows.append(Row(op, kernel, **d))
+
+    # ---- pmn_conv2d: conv_kernel (planar image in, 8 channels out); TP = 4 from N*Ho*Wo >= 1,500,000 (launch_conv) -------------------
+    add("conv2d", "conv_kernel<3, 8, 3, 1, 2, true, false>", n=3, cin=3, cout=8, nchw_in=True)
+    add("conv2d", "conv_kernel<1, 8, 3, 1, 2, true, false>", n=3, cin=1, cout=8, nchw_in=True)
+    rows.append(Row("conv2d", "conv_kernel<1, 8, 3, 1, 4, true, false>", N=1, H=1200, W=1250, cin=1, cout=8, nchw_in=True, large=True))
+    rows.append(Row("conv2d", "conv_kernel<3, 8, 3, 1, 4, true, false>", N=379, H=64, W=62, cin=3, cout=8, nchw_in=True, relu=0, bn=False))
+    # ---- pmn_conv2d: conv_tiled_kernel, the 3x3 / 5x5 stride 2 / 1x1 layers ----------------------------------------------------------
+    for cin, cout, cc in ((8, 8, 8), (16, 8, 16), (16, 16, 16), (32, 32, 16)):
+        add("conv2d", _t(cin, cc, cout, cout, 3, 1), n=2, cin=cin, cout=cout)
+    add("conv2d", _t(64, 16, 32, 64, 3, 1), n=2, cin=64, cout=64)
+    add("conv2d", _t(64, 16, 64, 64, 3, 1), n=2, cin=64, cout=64, env=E_S0C8)
+    L5 = dict(K=5, S=2, pad=2)
+    add("conv2d", _t(8, 4, 16, 16, 5, 2), n=2, cin=8, cout=16, **L5)
+    add("conv2d", _t(16, 4, 32, 32, 5, 2), n=2, cin=16, cout=32, **L5)
+    add("conv2d", _t(32, 4, 32, 64, 5, 2), n=2, cin=32, cout=64, **L5)
+    add("conv2d", _t(8, 8, 16, 16, 5, 2), n=2, cin=8, cout=16, env=E_C8, device_only=True, **L5)
+    add("conv2d", _t(16, 8, 32, 32, 5, 2), n=2, cin=16, cout=32, env=E_C8, device_only=True, **L5)
+    add("conv2d", _t(32, 8, 32, 64, 5, 2), n=2, cin=32, cout=64, env=E_C8, device_only=True, **L5)
+    add("conv2d", _t(32, 8, 64, 64, 5, 2), n=2, cin=32, cout=64, env=E_S0C8, device_only=True, **L5)
+    add("conv2d", _t(32, 4, 64, 64, 5, 2), n=1, cin=32, cout=64, env=E_S0, **L5)
+    P1 = dict(K=1, pad=0)
+    for cin, cout in ((16, 64), (32, 64), (64, 32), (64, 16)):
+        add("conv2d", _t(cin, 16, cout, cout, 1, 1), n=2, cin=cin, cout=cout, **P1)
+    add("conv2d", _t(64, 16, 32, 64, 1, 1), n=2, cin=64, cout=64, **P1)
+    add("conv2d", _t(64, 16, 64, 64, 1, 1), n=2, cin=64, cout=64, env=E_S0C8, **P1)
+    for cin in (16, 32, 64):  # the FPN lateral form: two blocks of 32 channels, bilinear x2 of `up` seeds the accumulators
+        add("conv2d", _t(cin, 16, 32, 64, 1, 1, up=True), sizes=SZ_EVEN, n=2, cin=cin, cout=64, up=True, bn=False, **P1)
+    # ---- pmn_conv2d: the planar offset-head forms, every (cin, COUTP) of the dispatch; dilation as the cascade uses it -----------------
+    for cin, dil in ((64, 2), (32, 4), (16, 6)):
+        for cp, cout in ((8, 2), (16, 10), (32, 18), (48, 34)):
+            add("conv2d", _t(cin, 8, min(cp, 16), cp, 3, 1, planar=True), n=2 if cp == 32 else 1, cin=cin, cout=cout, pad=dil, dil=dil,
+                planar=True, relu=0, bn=False)
+    add("conv2d", _t(8, 8, 8, 8, 3, 1, planar=True), n=2, cin=8, cout=1, planar=True, relu=0, bn=False)
+    # ---- pmn_conv2d_mfma: the product library carries the split 1x1 form alone (conv_mfma.hip, #ifndef PMN_EXPERIMENTAL) --------------
+    add("mfma1x1", "conv_mfma_kernel<64, 32, 128, 1, 1, 1, 4, 1, 4, false>", n=3, cin=64, cout=112, ca=64, K=1, pad=0, relu=0, bn=False)
+    add("mfma1x1", "conv_mfma_kernel<64, 32, 128, 1, 1, 1, 4, 1, 4, false>", n=2, cin=64, cout=128, ca=16, K=1, pad=0, relu=0, bn=False)
+    # ---- pmn_conv2d_f16s: all six layers (tiles 16 wide x 16 or 8 rows) ---------------------------------------------------------------
+    F = "conv_f16s_kernel"
+    add("f16s", f"{F}<16, 16, 3, 1, 16, 16, 4, 4, 1, 0, true>", n=3, cin=16, cout=16)
+    add("f16s", f"{F}<32, 32, 3, 1, 16, 16, 2, 4, 1, 0, false>", n=3, cin=32, cout=32)
+    add("f16s", f"{F}<64, 64, 3, 1, 16, 16, 2, 3, 1, 0, true>", n=3, cin=64, cout=64)
+    add("f16s", f"{F}<8, 16, 5, 2, 8, 8, 2, 4, 1, 0, true>", n=3, cin=8, cout=16, **L5)
+    add("f16s", f"{F}<16, 32, 5, 2, 8, 8, 2, 4, 1, 0, false>", n=3, cin=16, cout=32, **L5)
+    add("f16s", f"{F}<32, 64, 5, 2, 16, 24, 2, 2, 1, 0, true>", n=3, cin=32, cout=64, device_only=True, **L5)
+    # ---- pmn_conv2d_f16s_pair: 14x14 tiles --------------------------------------------------------------------------------------------
+    for H, W, N in ((1, 1, 1), (3, 5, 2), (14, 14, 1), (13, 13, 3), (15, 15, 2), (15, 29, 3), (29, 43, 1)):
+        rows.append(Row("pair", "conv_f16s_pair16_kernel<4>", N=N, H=H, W=W, cin=16, cout=16, relu=1 if (H + N) % 2 else 0))
+    # ---- pmn_offset_heads_f16s: (cin, dil) x coutp 32 / 48 / 64, ca == cout and ca < cout; images smaller than the dilation -----------
+    for cin, dil, wps in ((64, 2, 3), (32, 4, 4), (16, 6, 4)):
+        for cp, cout, ca in ((32, 18, 18), (32, 32, 16), (48, 34, 16), (48, 48, 48), (64, 50, 32), (64, 64, 64)):
+            add("heads", f"{F}<{cin}, {cp}, 3, 1, 16, 16, 2, {min(wps, 3) if cp == 64 else wps}, {dil}, 1, false>", cin=cin, cout=cout,
+                ca=ca, pad=dil, dil=dil, relu=0, bn=False)
+    # ---- pmn_fpn_level / pmn_fpn_tail / pmn_deconv3x3s2 / pmn_stem ----------------------------------------------------------------------
+    add("fpn_level", "fpn_level_kernel<64, 112, 64, false>", n=4, cin=64, cout=112, ca=64, device_only=True)
+    add("fpn_level", "fpn_level_kernel<32, 48, 32, true>", sizes=SZ_EVEN, n=4, cin=32, cout=48, ca=32, up=True, device_only=True)
+    add("fpn_level", "fpn_level_kernel<16, 16, 16, true>", sizes=SZ_EVEN, n=4, cin=16, cout=16, ca=16, up=True)
+    add("fpn_tail", "fpn_tail_kernel<16, 64, 16>", sizes=SZ_EVEN, n=5, cin=16, cout=16, up=True)
+    add("deconv", "deconv3x3s2_kernel<8, 8>", n=6, cin=8, cout=8)
+    add("stem", "stem_kernel", n=7, cin=3, cout=8, relu=1, bn=True)
+    # ---- pmn_stem_f16s (tiles 16 wide x 32 rows): VEC4 staging with W % 4 == 0 and an aligned base, scalar otherwise ----------------
+    SV, SS = "stem_f16s_kernel<true, 32>", "stem_f16s_kernel<false, 32>"
+    for H, W, N in ((1, 4, 1), (32, 16, 1), (33, 20, 2), (31, 12, 3), (40, 32, 1)):
+        rows.append(Row("stem_f16s", SV, N=N, H=H, W=W, cin=3, cout=8))
+    for H, W, N in ((1, 1, 1), (3, 5, 2), (31, 15, 3), (33, 17, 2), (64, 9, 1)):
+        rows.append(Row("stem_f16s", SS, N=N, H=H, W=W, cin=3, cout=8))
+    for H, W, N in ((32, 16, 1), (33, 20, 2)):
+        rows.append(Row("stem_f16s", SS, N=N, H=H, W=W, cin=3, cout=8, misalign=True))
+    rows.append(Row("stem_views", SV, N=6, views=3, H=33, W=20, cin=3, cout=8))
+    rows.append(Row("stem_views", SS, N=2, views=2, H=17, W=15, cin=3, cout=8))
+    # ---- Refinement: B = 2 rows use both depth ranges (kernel_space.DEPTH_RANGES); every refine_tail / refine_fused row carries
+    #      res_max = 0.25 (set below): case() scales the res weights so that max |res| is 0.25 in normalised depth units, inside
+    #      [0.05, 0.5], so the residual is NOT small against dnorm in [0, 1] ----------------------------------------------------------
+    RS = ((2, 2, 1), (16, 16, 2), (14, 14, 2), (18, 18, 1), (18, 34, 2), (34, 50, 1), (32, 64, 2), (6, 40, 2))
+    for H, W, N in RS:
+        rows.append(Row("refine_front", "refine_front_kernel", N=N, H=H, W=W, cin=3, cout=16))
+    for H, W, N in RS:
+        rows.append(Row("refine_tail", "refine_tail_kernel", N=N, H=H, W=W, cin=16, cout=1, device_only=True))
+    for H, W, N in RS:
+        rows.append(Row("refine_fused", f"refine_fused_kernel<{_b(W % 4 == 0)}>", N=N, H=H, W=W, cin=3, cout=1, device_only=True))
+    for H, W, N in ((16, 16, 2), (32, 64, 2), (6, 40, 1)):
+        rows.append(Row("refine_fused", "refine_fused_kernel<false>", N=N, H=H, W=W, cin=3, cout=1, device_only=True, misalign=True))
+    rows.append(Row("fpn_tail", "fpn_tail_kernel<16, 64, 16>", N=1, H=2, W=2, cin=16, cout=16, up=True))
+    rows.append(Row("stem", "stem_kernel", N=1, H=1, W=1, cin=3, cout=8))
+    rows.append(Row("stem", "stem_kernel", N=2, H=3, W=5, cin=3, cout=8))
+    out, nth = [], {}
+    for r in rows:  # the seed too: a hash of the kernel and the row's index among that kernel's rows
+        key = _key(r.op, r.kernel, r.env, r.misalign)
+        j = nth[key] = nth.get(key, -1) + 1
+        out.append(replace(r, seed=zlib.crc32(f"{key}|{j}".encode()) % 100000,
+                           res_max=0.25 if r.op in ("refine_tail", "refine_fused") else 0.0))
+    assert len({r.id for r in out}) == len(out)
+    return out
+
+
+ROWS: List[Row] = _rows()
+
+# Compiled but unreachable through the C ABI (exact: tests/test_conv_space.py fails when this list and the library disagree).  Empty:
+# every instantiation of the families below that libpmn_hip.so compiles is selected by some row.  (pmn_conv2d_mfma's layer forms and
+# its planar dilated form are compiled into the research build only -- conv_mfma.hip, #ifndef PMN_EXPERIMENTAL -- so the product
+# library has nothing of them to reach.)
+DEAD: Dict[str, str] = {}
+
+FAMILIES = {
+    "conv_kernel": "PKfS1_S1_S1_Pf8ConvArgs",
+    "conv_tiled_kernel": "PKfS1_S1_S1_Pf8ConvArgs",
+    "conv_mfma_kernel": "PKfPK15HIP_vector_typeIfLj4EES1_PfS6_12MfmaConvArgs",
+    "conv_f16s_kernel": "PKfPKDv8_DF16_S1_Pf8F16sArgs",
+    "conv_f16s_pair16_kernel": "PKfPKDv8_DF16_S1_S4_S1_Pf8F16sArgs",
+    "fpn_level_kernel": "PKfS1_S1_S1_PfS2_iii",
+    "fpn_tail_kernel": "PKfS1_S1_S1_S1_Pfiii",
+    "deconv3x3s2_kernel": "PKfS1_S1_Pfiiii",
+    "stem_f16s_kernel": "PKfS1_S1_PKDv8_DF16_S1_PfiiiPKS1_i",
+    "refine_fused_kernel": "PKfS1_S1_S1_S1_S1_PKDv8_DF16_S1_S1_S1_S1_S1_Pfiii",
+}
+OTHER_KERNELS = {
+    "stem_kernel": "_Z11stem_kernelPKfS0_S0_S0_S0_Pfiii",
+    "refine_front_kernel": "_Z19refine_front_kernelPKfS0_S0_S0_S0_S0_Pfiii",
+    "refine_tail_kernel": "_Z18refine_tail_kernelPKfS0_S0_S0_S0_S0_S0_Pfiii",
+}
+
+
+def mangle(readable: str) -> str:
+    return KS.mangle(readable, FAMILIES, OTHER_KERNELS)
+
+
+def out_hw(row: Row) -> Tuple[int, int]:
+    if row.op == "deconv":
+        return 2 * row.H, 2 * row.W
+    f = lambda n: (n + 2 * row.pad - row.dil * (row.K - 1) - 1) // row.S + 1  # noqa: E731
+    return (f(row.H), f(row.W)) if row.op in ("conv2d", "mfma1x1", "f16s", "heads") else (row.H, row.W)
+
+
+# ---- launch-plan recording ---------------------------------------------------------------------------------------------------------
+
+def record(row: Row, L=None) -> Tuple[int, List[str]]:
+    """Records the row's call in THIS process (whatever its environment) -> (return code, recorded kernel names)."""
+    from patchmatchnet_amd import _lib
+    L = L or _lib.lib()
+    A = 0x100000
+    img = A + 4 if row.misalign else A
+    N, H, W = row.N, row.H, row.W
+    p = ctypes.c_void_p()
+    assert L.pmn_plan_create(ctypes.byref(p)) == 0
+    assert L.pmn_plan_begin(p) == 0
+    try:
+        if row.op == "conv2d":
+            Ho, Wo = out_hw(row)
+            rc = L.pmn_conv2d(A, A, A, A if row.up else None, A, N, H, W, row.cin, row.cout, row.K, row.S, row.pad, row.dil, row.relu,
+                              int(row.nchw_in), int(row.planar), Ho // 2 if row.up else 0, Wo // 2 if row.up else 0, None)
+        elif row.op == "mfma1x1":
+            rc = L.pmn_conv2d_mfma(A, A, A, A, A, N, H, W, 64, row.cout, row.ca, 1, 1, 0, 1, row.relu, 0, None)
+        elif row.op == "f16s":
+            rc = L.pmn_conv2d_f16s(A, A, A, A, N, H, W, row.cin, row.cout, row.K, row.S, row.relu, None)
+        elif row.op == "pair":
+            rc = L.pmn_conv2d_f16s_pair(A, A, A, A, A, A, N, H, W, 16, row.relu, None)
+        elif row.op == "heads":
+            rc = L.pmn_offset_heads_f16s(A, A, A, A, A if row.ca < row.cout else None, N, H, W, row.cin, row.cout, row.ca, row.dil, None)
+        elif row.op == "fpn_level":
+            rc = L.pmn_fpn_level(A, A if row.up else None, A, A, A, A if row.ca < row.cout else None, N, H, W, row.cin, row.cout, row.ca,
+                                 None)
+        elif row.op == "fpn_tail":
+            rc = L.pmn_fpn_tail(A, A, A, A, A, A, N, H, W, 16, 64, 16, None)
+        elif row.op == "deconv":
+            rc = L.pmn_deconv3x3s2(A, A, A, A, N, H, W, 8, 8, row.relu, None)
+        elif row.op == "stem":
+            rc = L.pmn_stem(A, A, A, A, A, A, N, H, W, None)
+        elif row.op == "stem_f16s":
+            rc = L.pmn_stem_f16s(img, A, A, A, A, A, N, H, W, None)
+        elif row.op == "stem_views":
+            rc = L.pmn_stem_f16s_views(A, row.views, A, A, A, A, A, N // row.views, H, W, None)
+        elif row.op == "refine_front":
+            rc = L.pmn_refine_front(A, A, A, A, A, A, A, N, H, W, None)
+        elif row.op == "refine_tail":
+            rc = L.pmn_refine_tail(A, A, A, A, A, A, A, A, N, H, W, None)
+        elif row.op == "refine_fused":
+            rc = L.pmn_refine_fused(img, A, A, A, A, A, A, A, A, A, A, A, A, N, H, W, None)
+        else:
+            raise ValueError(row.op)
+    finally:
+        assert L.pmn_plan_end(p) == 0
+    names = [L.pmn_plan_kernel_name(p, i).decode() for i in range(L.pmn_plan_count(p))]
+    L.pmn_plan_destroy(p)
+    return rc, names
+
+
+def child(env: Env, what: str, timeout: float) -> subprocess.CompletedProcess:
+    """A fresh interpreter with ``env`` set that runs conv_space.child_main(what) (the variables are read once per process)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    e = {k: v for k, v in os.environ.items() if k not in ("PMN_CONV_SPLIT", "PMN_CONV_CC5")}
+    e.update(dict(env))
+    e["PYTHONPATH"] = os.pathsep.join([here, os.path.dirname(here)] + ([e["PYTHONPATH"]] if e.get("PYTHONPATH") else []))
+    code = f"import conv_space as C; C.child_main({what!r}, {tuple(env)!r})"
+    return subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=timeout)
+
+
+def child_main(what: str, env: Env) -> None:
+    out = {}
+    for row in ROWS:
+        if row.env != tuple(env):
+            continue
+        if what == "record":
+            out[row.id] = record(row)
+        else:
+            rc, names = record(row)
+            got, errs = run_device(row), {}
+            ref = reference(row)
+            errs = {"rc": rc, "names": names, "err": error(row, got, ref)}
+            out[row.id] = errs
+    print("CONV_SPACE_JSON " + json.dumps(out))
+
+
+@functools.lru_cache(maxsize=None)
+def record_env(env: Env) -> Dict[str, Tuple[int, List[str]]]:
+    r = child(env, "record", 300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("CONV_SPACE_JSON ")][-1]
+    return {k: (v[0], v[1]) for k, v in json.loads(line[len("CONV_SPACE_JSON "):]).items()}
+
+
+# ---- weights and inputs (seeded; float32 as the kernels get them) ------------------------------------------------------------------
+
+def _layer(rng, cout, cin, K, bn, transposed=False):
+    shape = (cin, cout, K, K) if transposed else (cout, cin, K, K)
+    d = {"w": (rng.standard_normal(shape) * (1.5 / np.sqrt(cin * K * K))).astype(np.float32)}
+    if bn:
+        d["bn"] = tuple(a.astype(np.float32) for a in (0.5 + rng.random(cout), 0.3 * rng.standard_normal(cout), 0.3 * rng.standard_normal(cout),
+                                                       0.5 + rng.random(cout)))
+    else:
+        d["bias"] = (0.3 * rng.standard_normal(cout)).astype(np.float32)
+    return d
+
+
+@functools.lru_cache(maxsize=8)
+def case(row: Row) -> Dict:
+    """The row's unpacked weights and inputs: planar float32 arrays (x [N,C,H,W]); dicts w / bn / bias per layer."""
+    rng = np.random.default_rng(1000 + row.seed)
+    N, H, W = row.N, row.H, row.W
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)  # noqa: E731
+    c: Dict = {}
+    if row.op in ("conv2d", "mfma1x1", "f16s", "heads"):
+        c["x"] = f(N, row.cin, H, W)
+        c["l"] = _layer(rng, row.cout, row.cin, row.K, row.bn)
+        if not row.relu:  # relu = 0 must show: a tiny image whose outputs are all positive gets the layer negated
+            l = c["l"]
+            if R.conv_bn(c["x"], l["w"], l.get("bn"), l.get("bias"), **_conv_kw(row))[0].min() > -0.1:
+                if "bn" in l:
+                    l["bn"] = (-l["bn"][0], -l["bn"][1]) + l["bn"][2:]
+                else:
+                    l["w"], l["bias"] = -l["w"], -l["bias"]
+        if row.up:
+            Ho, Wo = out_hw(row)
+            c["u"] = f(N, row.cout, Ho // 2, Wo // 2)
+    elif row.op == "pair":
+        c["x"] = f(N, 16, H, W)
+        c["la"], c["lb"] = _layer(rng, 16, 16, 3, True), _layer(rng, 16, 16, 3, True)
+    elif row.op == "fpn_level":
+        c["x"] = f(N, row.cin, H, W)
+        c["w"] = (rng.standard_normal((row.cin, row.cout)) / np.sqrt(row.cin)).astype(np.float32)
+        c["b"] = (0.3 * rng.standard_normal(row.cout)).astype(np.float32)
+        if row.up:
+            c["u"] = f(N, row.cout, H // 2, W // 2)
+    elif row.op == "fpn_tail":
+        c["x"], c["u"] = f(N, 16, H, W), f(N, 64, H // 2, W // 2)
+        c["inner"], c["outer"] = _layer(rng, 64, 16, 1, False), {"w": (rng.standard_normal((16, 64, 1, 1)) / 8.0).astype(np.float32)}
+    elif row.op == "deconv":
+        c["x"] = f(N, 8, H, W)
+        c["l"] = _layer(rng, 8, 8, 3, row.bn, transposed=True)
+    elif row.op in ("stem", "stem_f16s", "stem_views"):
+        c["x"] = rng.random((N, 3, H, W)).astype(np.float32) * 2 - 1
+        c["la"], c["lb"] = _layer(rng, 8, 3, 3, True), _layer(rng, 8, 8, 3, True)
+    elif row.op.startswith("refine"):
+        lo = np.array([KS.DEPTH_RANGES[b % 2][0] for b in range(N)], np.float32)
+        hi = np.array([KS.DEPTH_RANGES[b % 2][1] for b in range(N)], np.float32)
+        c.update(dmin=lo, dmax=hi, img=rng.random((N, 3, H, W)).astype(np.float32) * 2 - 1, t2=np.maximum(f(N, 8, H // 2, W // 2), 0),
+                 dnorm=rng.random((N, 1, H // 2, W // 2)).astype(np.float32), c0=_layer(rng, 8, 3, 3, True),
+                 dc=_layer(rng, 8, 8, 3, True, transposed=True), c3=_layer(rng, 8, 16, 3, True))
+        c["x16"] = np.maximum(f(N, 16, H, W), 0)
+        wr = rng.standard_normal((1, 8, 3, 3))
+        x16 = c["x16"] if row.op == "refine_tail" else R.refine_front(c["img"], c["t2"], c["c0"], c["dc"])[0]
+        m, _ = R.conv_bn(x16, c["c3"]["w"], c["c3"]["bn"], relu=True, pad=1)
+        res, _ = R.conv2d(m, wr, pad=1)
+        c["wr"] = (wr * ((row.res_max or 0.25) / np.abs(res).max())).astype(np.float32)  # max |res| = row.res_max (refine_front: unused)
+    return c
+
+
+def _conv_kw(row: Row) -> Dict:
+    return dict(stride=row.S, pad=row.pad, dil=row.dil)
+
+
+def reference(row: Row, **mk) -> Dict[str, np.ndarray]:
+    """conv_ref64's outputs of the row: y (planar float64) and A, its magnitude bound; refine rows: depth, norm, res.  Keyword
+    arguments select one kernel mistake (conv_ref64's)."""
+    c = case(row)
+    relu = bool(row.relu)
+    if row.op in ("conv2d", "mfma1x1", "f16s", "heads"):
+        ac = mk.pop("align_corners", False)
+        force_relu = mk.pop("force_relu", False)
+        y, A = R.conv_bn(c["x"], c["l"]["w"], c["l"].get("bn"), c["l"].get("bias"), relu=False, **_conv_kw(row), **mk)
+        if row.up:
+            u = R.bilinear2(c["u"], ac)
+            y, A = y + u, A + np.abs(u)
+        return {"y": np.maximum(y, 0) if relu or force_relu else y, "A": A}
+    if row.op == "pair":
+        y, A = R.chain2(c["x"], c["la"], c["lb"], relu=relu or mk.pop("force_relu", False), **mk)
+    elif row.op in ("stem", "stem_f16s", "stem_views"):
+        y, A = R.chain2(c["x"], c["la"], c["lb"], relu=True, **mk)
+    elif row.op == "fpn_level":
+        y, A = R.fpn_level(c["x"], c.get("u"), c["w"], c["b"], **mk)
+    elif row.op == "fpn_tail":
+        y, A = R.fpn_tail(c["x"], c["u"], c["inner"]["w"], c["inner"]["bias"], c["outer"]["w"], **mk)
+    elif row.op == "deconv":
+        force_relu = mk.pop("force_relu", False)
+        y, A = R.deconv_bn(c["x"], c["l"]["w"], c["l"].get("bn"), relu=relu or force_relu, **mk)
+    elif row.op == "refine_front":
+        y, A = R.refine_front(c["img"], c["t2"], c["c0"], c["dc"], **mk)
+    elif row.op == "refine_tail":
+        return R.refine_tail(c["x16"], c["c3"], c["wr"], c["dnorm"], c["dmin"], c["dmax"], **mk)
+    elif row.op == "refine_fused":
+        return R.refine_fused(c["img"], c["t2"], c["c0"], c["dc"], c["c3"], c["wr"], c["dnorm"], c["dmin"], c["dmax"], **mk)
+    else:
+        raise ValueError(row.op)
+    return {"y": y, "A": A}
+
+
+# ---- error metrics, families and tolerances --------------------------------------------------------------------------------------------
+
+METRIC = {"conv2d": "single", "mfma1x1": "single", "f16s": "single", "heads": "single", "fpn_level": "single", "deconv": "single",
+          "refine_front": "single", "pair": "fused", "stem": "fused", "stem_f16s": "fused", "stem_views": "fused", "fpn_tail": "fused",
+          "refine_tail": "refine", "refine_fused": "refine"}
+F16S_OPS = ("f16s", "pair", "heads", "stem_f16s", "stem_views", "refine_fused")
+
+
+def family(row: Row) -> str:
+    if row.op == "conv2d":
+        return row.kernel.split("<")[0]
+    return "stem_f16s" if row.op == "stem_views" else row.op
+
+
+def error(row: Row, got, ref: Dict[str, np.ndarray]) -> float:
+    """single-layer rows: max |got - ref| / A element-wise; fused rows: per output channel, max error over the channel's max magnitude;
+    refine rows: normalised depth (out - min) / span, error over the row's max |res|."""
+    got = np.asarray(got, np.float64)
+    m = METRIC[row.op]
+    if m == "refine":
+        c = case(row)
+        lo, hi = R.f64(c["dmin"]).reshape(-1, 1, 1, 1), R.f64(c["dmax"]).reshape(-1, 1, 1, 1)
+        if got.shape != ref["depth"].shape:
+            return float("inf")
+        d = np.abs((got - lo) / (hi - lo) - ref["norm"]) / np.abs(ref["res"]).max()
+    else:
+        y = ref["y"]
+        if got.shape != y.shape:
+            return float("inf")
+        d = np.abs(got - y)
+        if m == "single":
+            d = d / np.maximum(ref["A"], 1e-30)
+        else:
+            d = d.max(axis=(0, 2, 3)) / np.maximum(np.abs(y).max(axis=(0, 2, 3)), 1e-30)
+    d = np.where(np.isnan(d), np.inf, d)
+    return float(d.max())
+
+
+# family -> tolerance.  fp32 kernels: 8 x the largest error, over the family's rows, of a torch CPU float32 evaluation of the row layer by
+# layer against conv_ref64 in the row's metric (the margin covers another accumulation order and FMA contraction).  Split-fp16 kernels: 4 x
+# the largest error of the emulation of their arithmetic (conv_ref64.f16s_conv; fp32 stages in torch float32), which leaves accumulation
+# order alone.  tests/test_conv_space.py re-measures and asserts margin x measured <= TOL.  MEASURED holds the values these came from.
+MARGIN = {False: 8.0, True: 4.0}
+MEASURED: Dict[str, float] = {  # largest error over the family's rows (torch 2.x CPU float32 / the emulation), in the family's metric
+    "conv_kernel": 3.245e-07, "conv_tiled_kernel": 2.669e-07, "mfma1x1": 3.627e-07, "deconv": 2.063e-07, "fpn_level": 2.952e-07,
+    "fpn_tail": 7.888e-07, "stem": 4.658e-07, "refine_front": 1.950e-07, "refine_tail": 6.594e-07,                # float32, x 8
+    "f16s": 7.952e-08, "heads": 1.085e-07, "pair": 9.739e-07, "stem_f16s": 6.627e-07, "refine_fused": 5.815e-07,  # emulation, x 4
+}
+TOL: Dict[str, float] = {
+    "conv_kernel": 2.6e-6, "conv_tiled_kernel": 2.2e-6, "mfma1x1": 3.0e-6, "deconv": 1.7e-6, "fpn_level": 2.4e-6, "fpn_tail": 6.4e-6,
+    "stem": 3.8e-6, "refine_front": 1.6e-6, "refine_tail": 5.3e-6,
+    "f16s": 3.2e-7, "heads": 4.4e-7, "pair": 3.9e-6, "stem_f16s": 2.7e-6, "refine_fused": 2.4e-6,
+}
+
+
+def is_f16s(row: Row) -> bool:
+    return row.op in F16S_OPS
+
+
+# ---- the float32 evaluation (torch CPU, layer by layer) and the split-fp16 emulation ---------------------------------------------------
+
+def _tconv(x, l, relu, stride=1, pad=0, dil=1):
+    import torch
+    import torch.nn.functional as Fn
+    y = Fn.conv2d(x, torch.from_numpy(l["w"]), torch.from_numpy(l["bias"]) if "bias" in l else None, stride, pad, dil)
+    if "bn" in l:
+        g, b, m, v = (torch.from_numpy(a) for a in l["bn"])
+        y = Fn.batch_norm(y, m, v, g, b, False, 0.0, R.BN_EPS)
+    return torch.relu(y) if relu else y
+
+
+def _tdeconv(x, l, relu):
+    import torch
+    import torch.nn.functional as Fn
+    y = Fn.conv_transpose2d(x, torch.from_numpy(l["w"]), None, 2, 1, 1)
+    if "bn" in l:
+        g, b, m, v = (torch.from_numpy(a) for a in l["bn"])
+        y = Fn.batch_norm(y, m, v, g, b, False, 0.0, R.BN_EPS)
+    return torch.relu(y) if relu else y
+
+
+def _emu(x32, l, K, S, dil, CC, relu, **kw):
+    w, sh = R.fold(l["w"], l.get("bn"), l.get("bias"))
+    return R.f16s_conv(np.asarray(x32, np.float32), w.astype(np.float32).astype(np.float64), sh.astype(np.float32), K, S, dil, CC, relu, **kw)
+
+
+def evaluate(row: Row, dtype="float32", drop_lo: bool = False) -> np.ndarray:
+    """The row in torch on the CPU, layer by layer with torch.nn.functional (conv2d, conv_transpose2d, interpolate, batch_norm), in
+    ``dtype``.  float64: the check that conv_ref64 itself is right.  float32: what fp32 arithmetic costs; the split-fp16 layers of
+    the f16s ops then go through the emulation conv_ref64.f16s_conv."""
+    import torch
+    import torch.nn.functional as Fn
+    from patchmatchnet_amd import params
+    c = case(row)
+    dt = getattr(torch, dtype)
+    emu = dtype == "float32" and is_f16s(row)
+
+    def T(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dt)
+
+    def L(l):
+        return {k: (tuple(a.astype(dtype) for a in v) if k == "bn" else v.astype(dtype)) for k, v in l.items()}
+
+    up2 = lambda u: Fn.interpolate(T(u), scale_factor=2, mode="bilinear", align_corners=False)  # noqa: E731
+    relu = bool(row.relu)
+    if row.op in ("conv2d", "mfma1x1", "f16s", "heads"):
+        if emu:
+            return _emu(c["x"], c["l"], row.K, row.S, row.dil, 16 if row.op == "heads" else params.f16s_chunk(row.cin, row.K), relu,
+                        drop_lo=drop_lo)
+        y = _tconv(T(c["x"]), L(c["l"]), False, row.S, row.pad, row.dil)
+        if row.up:
+            y = up2(c["u"]) + y
+        return (torch.relu(y) if relu else y).numpy()
+    if row.op in ("pair", "stem", "stem_f16s", "stem_views"):
+        r = relu or row.op != "pair"
+        if emu and row.op == "pair":
+            return _emu(_emu(c["x"], c["la"], 3, 1, 1, 16, r, drop_lo=drop_lo), c["lb"], 3, 1, 1, 16, r, drop_lo=drop_lo)
+        m = _tconv(T(c["x"]), L(c["la"]), r, 1, 1)
+        if emu:
+            return _emu(m.numpy(), c["lb"], 3, 1, 1, 8, True, drop_lo=drop_lo)
+        return _tconv(m, L(c["lb"]), r, 1, 1).numpy()
+    if row.op == "fpn_level":
+        y = Fn.conv2d(T(c["x"]), T(c["w"].T[:, :, None, None]), T(c["b"]))
+        return (up2(c["u"]) + y if row.up else y).numpy()
+    if row.op == "fpn_tail":
+        return _tconv(up2(c["u"]) + _tconv(T(c["x"]), L(c["inner"]), False), L(c["outer"]), False).numpy()
+    if row.op == "deconv":
+        return _tdeconv(T(c["x"]), L(c["l"]), relu).numpy()
+    front = lambda: torch.cat([_tdeconv(T(c["t2"]), L(c["dc"]), True), _tconv(T(c["img"]), L(c["c0"]), True, 1, 1)], 1)  # noqa: E731
+    if row.op == "refine_front":
+        return front().numpy()
+    x16 = T(c["x16"]) if row.op == "refine_tail" else front()
+    m = T(_emu(x16.numpy(), c["c3"], 3, 1, 1, 16, True, drop_lo=drop_lo)) if emu else _tconv(x16, L(c["c3"]), True, 1, 1)
+    res = Fn.conv2d(m, T(c["wr"]), None, 1, 1)
+    lo, hi = T(c["dmin"]).view(-1, 1, 1, 1), T(c["dmax"]).view(-1, 1, 1, 1)
+    return ((Fn.interpolate(T(c["dnorm"]), scale_factor=2, mode="nearest") + res) * (hi - lo) + lo).numpy()
+
+
+# ---- plausible kernel mistakes -----------------------------------------------------------------------------------------------------------
+
+def _out(ref):
+    return ref["depth"] if "depth" in ref else ref["y"]
+
+
+def mistakes(row: Row, ref: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """name -> the row's output when the computation makes one plausible kernel mistake (from conv_ref64; 'lo terms dropped' from the
+    emulation)."""
+    out: Dict[str, np.ndarray] = {}
+    t = np.array(_out(ref), copy=True)
+    t[..., -1, -1] = 0.0 if "y" in ref else case(row)["dmin"].astype(np.float64).reshape(-1, 1)
+    out["tail pixel unwritten"] = t
+    Ho, Wo = out_hw(row)
+    if row.op in ("conv2d", "f16s", "heads") and row.K > 1:
+        out["clamp instead of zero padding"] = reference(row, border="clamp")["y"]
+        if Wo > 16:
+            out["tap column dropped at a tile seam"] = reference(row, drop=(0, 16))["y"]
+    if row.op in ("conv2d", "mfma1x1", "f16s", "heads", "pair", "deconv") and not row.relu:
+        out["relu applied when 0 was asked"] = reference(row, force_relu=True)["y"]
+    if row.up and row.op in ("conv2d", "fpn_level", "fpn_tail") and max(Ho, Wo) > 2:
+        out["bilinear up-sampling with aligned corners"] = reference(row, align_corners=True)["y"]
+    if row.op in ("pair", "stem", "stem_f16s", "stem_views"):
+        out["input padded instead of the intermediate map"] = reference(row, pad_input=True)["y"]
+    if row.op == "deconv":
+        out["last row and column missing"] = reference(row, short=True)["y"]
+        out["parity classes swapped"] = reference(row, swap=True)["y"]
+    if row.op == "refine_front":
+        out["last row and column of the transposed convolution missing"] = reference(row, short=True)["y"]
+        out["parity classes swapped"] = reference(row, swap=True)["y"]
+    if row.op == "refine_fused":
+        out["last row and column of the transposed convolution missing"] = reference(row, front_kw=dict(short=True))["depth"]
+        out["parity classes swapped"] = reference(row, front_kw=dict(swap=True))["depth"]
+    if row.op in ("refine_tail", "refine_fused"):
+        if max(row.H, row.W) > 2:  # (a 1x1 dnorm has one value whatever the index)
+            out["nearest x2 indexed one pixel off"] = reference(row, near_shift=1)["depth"]
+        out["conv3 channel halves swapped"] = reference(row, swap_halves=True)["depth"]
+        out["x16 padded instead of the conv3 map"] = reference(row, pad_input=True)["depth"]
+        if row.N > 1:
+            out["depth range of sample 0 used for sample 1"] = reference(row, roll_range=True)["depth"]
+    if is_f16s(row):
+        out["lo terms dropped"] = evaluate(row, "float32", drop_lo=True).astype(np.float64)
+    return out
+
+
+# ---- the row on the device -----------------------------------------------------------------------------------------------------------------
+
+def run_device(row: Row, want_aligned: bool = False):
+    """The row through patchmatchnet_amd.ops on cuda:0 -> planar float32 numpy output (with ``want_aligned``: (output, the output of
+    the same call on an aligned base / through pmn_stem_f16s per view), for the same-bits checks)."""
+    import torch
+
+    import patchmatchnet_amd as P
+    from patchmatchnet_amd import params
+    ops = P.ops
+    dev = "cuda:0"
+    c = case(row)
+
+    def t(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def cl(a):  # planar -> channels-last
+        return t(np.asarray(a).transpose(0, 2, 3, 1))
+
+    def pl(x):  # channels-last device tensor -> planar numpy
+        return x.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+
+    def mis(a):  # the same values at a base one float past a 16-byte boundary
+        buf = torch.empty(a.size + 4, dtype=torch.float32, device=dev)
+        v = buf[1:1 + a.size].view(a.shape)
+        v.copy_(t(a))
+        assert v.data_ptr() % 16 == 4
+        return v
+
+    def TW(l):
+        return {k: (tuple(torch.from_numpy(a) for a in v) if k == "bn" else torch.from_numpy(v)) for k, v in l.items()}
+
+    def pk(fn, l, **kw):
+        L = TW(l)
+        return tuple(t(a) for a in fn(L["w"], **({"bn": L["bn"]} if "bn" in L else {"bias": L["bias"]} if "bias" in L else {}), **kw))
+
+    relu = bool(row.relu)
+    other = None
+    with torch.no_grad():
+        if row.op == "conv2d":
+            w, s = pk(params.pack_conv, c["l"])
+            y = ops.conv2d(t(c["x"]) if row.nchw_in else cl(c["x"]), w, s, row.cout, row.K, row.S, row.pad, row.dil, relu,
+                           cl(c["u"]) if row.up else None, row.nchw_in, row.planar)
+            out = y.cpu().numpy() if row.planar else pl(y)
+        elif row.op == "mfma1x1":
+            w, s = pk(params.pack_conv_mfma, c["l"])
+            a, b = ops.pointwise_split_mfma(cl(c["x"]), w, s, row.cout, row.ca)
+            out = np.concatenate([pl(a), pl(b)], 1)
+        elif row.op == "f16s":
+            w, s = pk(params.pack_conv_f16s, c["l"])
+            out = pl(ops.conv2d_f16s(cl(c["x"]), w, s, row.K, row.S, relu))
+        elif row.op == "pair":
+            (wa, sa), (wb, sb) = pk(params.pack_conv_f16s, c["la"]), pk(params.pack_conv_f16s, c["lb"])
+            out = pl(ops.conv2d_f16s_pair(cl(c["x"]), wa, sa, wb, sb, relu))
+        elif row.op == "heads":
+            L = TW(c["l"])
+            w, s = (t(a) for a in params.pack_offset_heads_f16s(L["w"], L["bias"]))
+            a, b = ops.offset_heads_f16s(cl(c["x"]), w, s, row.cout, row.ca, row.dil)
+            out = np.concatenate([a.cpu().numpy()] + ([b.cpu().numpy()] if b is not None else []), 1)
+        elif row.op == "fpn_level":
+            a, b = ops.fpn_level(cl(c["x"]), cl(c["u"]) if row.up else None, t(c["w"]), t(c["b"]), row.ca)
+            out = np.concatenate([pl(a)] + ([pl(b)] if b is not None else []), 1)
+        elif row.op == "fpn_tail":
+            (wi, bi), (wo, _) = pk(params.pack_conv, c["inner"]), pk(params.pack_conv, c["outer"])
+            out = pl(ops.fpn_tail(cl(c["x"]), cl(c["u"]), wi, bi, wo))
+        elif row.op == "deconv":
+            L = TW(c["l"])
+            w, s = (t(a) for a in params.pack_deconv(L["w"], L.get("bn")))
+            out = pl(ops.deconv3x3s2(cl(c["x"]), w, s, relu))
+        elif row.op in ("stem", "stem_f16s", "stem_views"):
+            w0, s0 = pk(params.pack_conv, c["la"])
+            if row.op == "stem":
+                w1, s1 = pk(params.pack_conv, c["lb"])
+                out = pl(ops.stem(t(c["x"]), w0, s0, w1, s1))
+            else:
+                Lb = TW(c["lb"])
+                w1, s1 = (t(a) for a in params.pack_stem_conv1_f16s(Lb["w"], Lb["bn"]))
+                if row.op == "stem_f16s":
+                    out = pl(ops.stem_f16s(mis(c["x"]) if row.misalign else t(c["x"]), w0, s0, w1, s1))
+                    if want_aligned:
+                        other = pl(ops.stem_f16s(t(c["x"]), w0, s0, w1, s1))
+                else:
+                    V, B = row.views, row.N // row.views
+                    imgs = [t(c["x"][v * B:(v + 1) * B]) for v in range(V)]
+                    tab = ops.SourceTable(torch.tensor([i.data_ptr() for i in imgs], dtype=torch.int64, device=dev), (V, B, 3, row.H, row.W))
+                    out = pl(ops.stem_f16s_views(tab, w0, s0, w1, s1))
+                    if want_aligned:
+                        other = np.concatenate([pl(ops.stem_f16s(i, w0, s0, w1, s1)) for i in imgs], 0)
+        else:
+            T0, Td, T3 = TW(c["c0"]), TW(c["dc"]), TW(c["c3"])
+            w0, s0 = (t(a) for a in params.pack_conv(T0["w"], bn=T0["bn"]))
+            wd, sd = (t(a) for a in params.pack_deconv(Td["w"], Td["bn"]))
+            w3, s3, wr = (t(a) for a in params.pack_refine_tail(T3["w"], T3["bn"], torch.from_numpy(c["wr"])))
+            tail = (t(c["dnorm"]), t(c["dmin"]), t(c["dmax"]))
+            if row.op == "refine_front":
+                out = pl(ops.refine_front(t(c["img"]), cl(c["t2"]), w0, s0, wd, sd))
+            elif row.op == "refine_tail":
+                out = ops.refine_tail(cl(c["x16"]), w3, s3, wr, *tail).cpu().numpy()
+            else:
+                w3a, s3a = (t(a) for a in params.pack_refine_conv3_f16s(T3["w"], T3["bn"]))
+                args = (cl(c["t2"]), w0, s0, wd, sd, w3a, s3a, wr) + tail
+                out = ops.refine_fused(mis(c["img"]) if row.misalign else t(c["img"]), *args).cpu().numpy()
+                if want_aligned:
+                    other = ops.refine_fused(t(c["img"]), *args).cpu().numpy()
+        torch.cuda.synchronize()
+    return (out, other) if want_aligned else out

@@ -211,8 +211,11 @@ OTHER_KERNELS = {  # pmn_confidence / pmn_normalize_depth: plain functions
 }
 
 
-def mangle(readable: str) -> str:
-    """'gather_corr_kernel<64, 8, 0, 16, true>' -> '_Z18gather_corr_kernelILi64ELi8ELi0ELi16ELb1EEv10GatherArgs'."""
+def mangle(readable: str, families: Optional[Dict[str, str]] = None, others: Optional[Dict[str, str]] = None) -> str:
+    """'gather_corr_kernel<64, 8, 0, 16, true>' -> '_Z18gather_corr_kernelILi64ELi8ELi0ELi16ELb1EEv10GatherArgs'.  ``families`` /
+    ``others``: another table's kernel families and plain kernels (tests/conv_space.py); default: this module's."""
+    FAMILIES, OTHER_KERNELS = (globals()["FAMILIES"] if families is None else families,
+                               globals()["OTHER_KERNELS"] if others is None else others)
     if readable in OTHER_KERNELS:
         return OTHER_KERNELS[readable]
     name, args = readable.split("<", 1)
@@ -246,8 +249,8 @@ def dynamic_symbols(path: str) -> List[str]:
     return names
 
 
-def library_instantiations(path: str) -> Dict[str, str]:
-    """{kernel symbol the launch plan records: host stub} for every kernel of FAMILIES the library compiles.  A `__global__` f has a
+def library_instantiations(path: str, families: Optional[Dict[str, str]] = None) -> Dict[str, str]:
+    """{kernel symbol the launch plan records: host stub} for every kernel of ``families`` (default FAMILIES) the library compiles.  A `__global__` f has a
     host stub `_Z<n>__device_stub__f...`; the kernel itself is `_Z<n-15>f...` (the same mangling without the 15-character prefix).
     Raises when the library has no stubs at all (a stripped or foreign build must fail, not pass vacuously)."""
     out = {}
@@ -261,7 +264,8 @@ def library_instantiations(path: str) -> Dict[str, str]:
         out[kern] = s
     if not out:
         raise AssertionError(f"{path}: no __device_stub__ symbols in .dynsym")
-    return {k: v for k, v in out.items() if any(k.startswith(f"_Z{len(f)}{f}I") for f in FAMILIES)}
+    fams = FAMILIES if families is None else families
+    return {k: v for k, v in out.items() if any(k.startswith(f"_Z{len(f)}{f}I") for f in fams)}
 
 
 # ---- launch-plan recording (fake device addresses: recording validates arguments and dereferences nothing) -------------------------
