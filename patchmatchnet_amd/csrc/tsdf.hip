@@ -51,11 +51,77 @@ struct TsdfView {
     int pad;
 };
 
-struct TsdfArgs {
+// ---- the grid every entry point is told about ---------------------------------------------------------------------------------
+// The block-sparse volume (section 18, below) cuts the lattice into blocks of 8 x 8 x 8 samples; its limits differ from the dense ones.
+#define TSDF_SB 8                                   // samples per block side
+#define TSDF_SB3 (TSDF_SB * TSDF_SB * TSDF_SB)      // samples per block = threads per workgroup
+#define TSDF_MAX_AXIS (1 << 19)
+#define TSDF_MAX_TABLE (1LL << 28)
+
+struct TsdfLattice {
+    int nx, ny, nz, nbx, nby, nbz;  // samples per axis; blocks per axis (a dense volume has none: 0)
+};
+
+// Lattice, placement and the one threshold of the call; every argument struct below derives from it.
+struct TsdfGrid {
+    TsdfLattice l;
+    float ox, oy, oz, voxel;
+    float trunc;       // integration and marking
+    float min_weight;  // marching tetrahedra
+};
+
+// the dense lattice: n >= 1 per axis, nz <= 65535 (it is a launch grid's z), fewer than 2^31 samples
+static int tsdf_dense_lattice(TsdfLattice& l, const int* dims_host) {
+    l.nx = dims_host[0];
+    l.ny = dims_host[1];
+    l.nz = dims_host[2];
+    if (l.nx < 1 || l.ny < 1 || l.nz < 1 || l.nz > 65535 || (long long)l.nx * l.ny * l.nz > 2147483647LL) return PMN_ERR_SHAPE;
+    return PMN_OK;
+}
+
+// the virtual lattice of the block-sparse volume: 2 <= n < 2^19 per axis, at most 2^28 blocks
+static int tsdf_lattice(TsdfLattice& l, const int* dims_host) {
+    l.nx = dims_host[0];
+    l.ny = dims_host[1];
+    l.nz = dims_host[2];
+    if (l.nx < 2 || l.ny < 2 || l.nz < 2 || l.nx >= TSDF_MAX_AXIS || l.ny >= TSDF_MAX_AXIS || l.nz >= TSDF_MAX_AXIS) return PMN_ERR_SHAPE;
+    l.nbx = (l.nx + TSDF_SB - 1) / TSDF_SB;
+    l.nby = (l.ny + TSDF_SB - 1) / TSDF_SB;
+    l.nbz = (l.nz + TSDF_SB - 1) / TSDF_SB;
+    if ((long long)l.nbx * l.nby * l.nbz > TSDF_MAX_TABLE) return PMN_ERR_SHAPE;
+    return PMN_OK;
+}
+
+static bool tsdf_positive(float v) { return v > 0.0f && std::isfinite(v); }
+
+// Checks and fills what every entry point shares: the lattice (``blocks`` picks the virtual lattice's limits), a finite origin and a
+// positive finite voxel.  The threshold's rule differs per entry point and stays with the caller.
+static int tsdf_grid(TsdfGrid& g, bool blocks, const int* dims_host, const float* origin_host, float voxel) {
+    if (!dims_host || !origin_host || !tsdf_positive(voxel)) return PMN_ERR_ARG;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(origin_host[c])) return PMN_ERR_ARG;
+    const int rc = blocks ? tsdf_lattice(g.l, dims_host) : tsdf_dense_lattice(g.l, dims_host);
+    if (rc != PMN_OK) return rc;
+    g.ox = origin_host[0];
+    g.oy = origin_host[1];
+    g.oz = origin_host[2];
+    g.voxel = voxel;
+    return PMN_OK;
+}
+
+static dim3 tsdf_dense_launch(const TsdfLattice& l) { return dim3((l.nx + TSDF_BX - 1) / TSDF_BX, (l.ny + TSDF_BY - 1) / TSDF_BY, l.nz); }
+
+static bool tsdf_pool_size_ok(int n_blocks) { return n_blocks >= 1 && (long long)n_blocks * TSDF_SB3 <= 2147483647LL; }
+
+struct TsdfArgs : TsdfGrid {
     float *tsdf, *weight, *rgb, *cweight;
-    int nx, ny, nz, nviews;
-    float ox, oy, oz, voxel, trunc;
+    int nviews;
     TsdfView v[PMN_TSDF_MAX_VIEWS];
+};
+
+struct TsdfBlockArgs : TsdfArgs {
+    const int* blocks;  // the linear block index of every slot of the pool
+    int nblocks;
 };
 
 // One sample of a volume through the views of a launch: the arithmetic of the header comment, shared by the dense kernel and the
@@ -118,8 +184,8 @@ __device__ __forceinline__ void tsdf_fold_sample(const Args& a, size_t s, size_t
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const TsdfArgs a) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * TSDF_BX + (threadIdx.x & 63), j = blockIdx.y * TSDF_BY + (threadIdx.x >> 6), k = blockIdx.z;
-    if (i >= a.nx || j >= a.ny) return;
-    const size_t n = (size_t)a.nx * a.ny * a.nz, s = ((size_t)k * a.ny + j) * a.nx + i;
+    if (i >= a.l.nx || j >= a.l.ny) return;
+    const size_t n = (size_t)a.l.nx * a.l.ny * a.l.nz, s = ((size_t)k * a.l.ny + j) * a.l.nx + i;
     const float x = a.ox + (float)i * a.voxel, y = a.oy + (float)j * a.voxel, z = a.oz + (float)k * a.voxel;
     tsdf_fold_sample(a, s, n, x, y, z);
 }
@@ -143,37 +209,35 @@ static int tsdf_fill_views(TsdfView* out, const float* maps, long long slot_stri
     return PMN_OK;
 }
 
-extern "C" int pmn_tsdf_integrate(float* tsdf, float* weight, float* rgb, float* cweight, const int* dims_host, const float* origin_host,
-                                  float voxel, float trunc, const float* maps, long long slot_stride, const int* slots_host,
-                                  const int* hw_host, const void* const* masks_host, const void* const* images_host,
-                                  const float* cams_host, int n_views, void* stream) {
-    if (!tsdf || !weight || !dims_host || !origin_host || !maps || !slots_host || !hw_host || !cams_host) return PMN_ERR_ARG;
-    if ((rgb == nullptr) != (cweight == nullptr)) return PMN_ERR_ARG;
-    if (!(voxel > 0.0f) || !(trunc > 0.0f) || !std::isfinite(voxel) || !std::isfinite(trunc) || slot_stride < 1) return PMN_ERR_ARG;
+// what both integrate kernels are told (``a`` zeroed by the caller): the planes, the grid and the per-view block
+static int tsdf_integrate_fill(TsdfArgs& a, bool blocks, float* tsdf, float* weight, float* rgb, float* cweight, const int* dims_host,
+                               const float* origin_host, float voxel, float trunc, const float* maps, long long slot_stride,
+                               const int* slots_host, const int* hw_host, const void* const* masks_host, const void* const* images_host,
+                               const float* cams_host, int n_views) {
+    if (!tsdf || !weight || !maps || !slots_host || !hw_host || !cams_host || slot_stride < 1) return PMN_ERR_ARG;
+    if ((rgb == nullptr) != (cweight == nullptr) || !tsdf_positive(trunc)) return PMN_ERR_ARG;
     if (n_views < 1 || n_views > PMN_TSDF_MAX_VIEWS) return PMN_ERR_SHAPE;
-    const int nx = dims_host[0], ny = dims_host[1], nz = dims_host[2];
-    if (nx < 1 || ny < 1 || nz < 1 || nz > 65535 || (long long)nx * ny * nz > 2147483647LL) return PMN_ERR_SHAPE;
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(origin_host[c])) return PMN_ERR_ARG;
-    TsdfArgs a;
-    memset(&a, 0, sizeof(a));
+    const int rc = tsdf_grid(a, blocks, dims_host, origin_host, voxel);
+    if (rc != PMN_OK) return rc;
     a.tsdf = tsdf;
     a.weight = weight;
     a.rgb = rgb;
     a.cweight = cweight;
-    a.nx = nx;
-    a.ny = ny;
-    a.nz = nz;
     a.nviews = n_views;
-    a.ox = origin_host[0];
-    a.oy = origin_host[1];
-    a.oz = origin_host[2];
-    a.voxel = voxel;
     a.trunc = trunc;
-    const int rc = tsdf_fill_views(a.v, maps, slot_stride, slots_host, hw_host, masks_host, images_host, cams_host, n_views);
+    return tsdf_fill_views(a.v, maps, slot_stride, slots_host, hw_host, masks_host, images_host, cams_host, n_views);
+}
+
+extern "C" int pmn_tsdf_integrate(float* tsdf, float* weight, float* rgb, float* cweight, const int* dims_host, const float* origin_host,
+                                  float voxel, float trunc, const float* maps, long long slot_stride, const int* slots_host,
+                                  const int* hw_host, const void* const* masks_host, const void* const* images_host,
+                                  const float* cams_host, int n_views, void* stream) {
+    TsdfArgs a;
+    memset(&a, 0, sizeof(a));
+    const int rc = tsdf_integrate_fill(a, false, tsdf, weight, rgb, cweight, dims_host, origin_host, voxel, trunc, maps, slot_stride,
+                                       slots_host, hw_host, masks_host, images_host, cams_host, n_views);
     if (rc != PMN_OK) return rc;
-    const dim3 grid((nx + TSDF_BX - 1) / TSDF_BX, (ny + TSDF_BY - 1) / TSDF_BY, nz);
-    PMN_LAUNCH(tsdf_integrate_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    PMN_LAUNCH(tsdf_integrate_kernel, tsdf_dense_launch(a.l), dim3(256), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
@@ -193,10 +257,8 @@ __constant__ unsigned char MT_TET[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3,
 // bit t = tetrahedron t is negatively oriented (orders 1,4,2 / 2,1,4 / 4,2,1)
 #define MT_NEGATIVE 0x26
 
-struct MtArgs {
+struct MtArgs : TsdfGrid {
     const float *tsdf, *weight, *rgb, *cweight;
-    int nx, ny, nz;
-    float ox, oy, oz, voxel, min_weight;
     unsigned char *vmask, *ntri;  // count: outputs; emit: inputs
     const int *vincl, *tincl;     // emit: INCLUSIVE scans of popcount(vmask) and of ntri
     float* vertices;
@@ -205,34 +267,51 @@ struct MtArgs {
     int* faces;
 };
 
-__device__ __forceinline__ bool mt_ok(const MtArgs& a, int i, int j, int k) {
-    if (i < 0 || j < 0 || k < 0 || i >= a.nx || j >= a.ny || k >= a.nz) return false;
-    return a.weight[((size_t)k * a.ny + j) * a.nx + i] >= a.min_weight;
-}
-
-// bit c = corner c of the cell at (i, j, k) is inside (tsdf < 0); the cell must lie in the lattice
-__device__ __forceinline__ unsigned mt_inside(const MtArgs& a, int i, int j, int k) {
-    unsigned in = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        in |= (a.tsdf[((size_t)(k + (c >> 2)) * a.ny + (j + ((c >> 1) & 1))) * a.nx + (i + (c & 1))] < 0.0f ? 1u : 0u) << c;
-    return in;
-}
-
 __device__ __forceinline__ unsigned mt_tet_case(unsigned in, int t) {
     return ((in >> MT_TET[t][0]) & 1u) | (((in >> MT_TET[t][1]) & 1u) << 1) | (((in >> MT_TET[t][2]) & 1u) << 2) |
            (((in >> MT_TET[t][3]) & 1u) << 3);
 }
 
-__global__ __launch_bounds__(256) void mt_count_kernel(const MtArgs a) {
-    const int i = blockIdx.x * TSDF_BX + (threadIdx.x & 63), j = blockIdx.y * TSDF_BY + (threadIdx.x >> 6), k = blockIdx.z;
-    if (i >= a.nx || j >= a.ny) return;
-    const size_t s = ((size_t)k * a.ny + j) * a.nx + i;
+// The rule is written once, over a SAMPLER: the thread's own sample -- (i, j, k) in the lattice, ``self`` its index in a plane,
+// ``planes`` the stride between the three colour planes -- and, for the sample at the offset (dx, dy, dz), -1 .. +2 per axis, from it:
+//     ok(dx, dy, dz)     1 if it is observed (inside the lattice, present, weight >= min_weight), else 0
+//     tsdf(dx, dy, dz)   its value; asked only where the rule has established that the sample is inside the lattice
+//     index(dx, dy, dz)  its index in a plane; -1 where its block has no slot, which only a sampler with kHoles may answer
+// MtDenseSampler reads the planes of a dense volume from global memory; MtPoolSampler (section 18, below) the LDS tile of a block.
+struct MtDenseSampler {
+    static constexpr bool kHoles = false;
+    const MtArgs& a;
+    const int i, j, k;
+    const size_t self, planes;
+    __device__ __forceinline__ MtDenseSampler(const MtArgs& a_, int i_, int j_, int k_)
+        : a(a_), i(i_), j(j_), k(k_), self(((size_t)k_ * a_.l.ny + j_) * a_.l.nx + i_), planes((size_t)a_.l.nx * a_.l.ny * a_.l.nz) {}
+    __device__ __forceinline__ size_t index(int dx, int dy, int dz) const {
+        return ((size_t)(k + dz) * a.l.ny + (j + dy)) * a.l.nx + (i + dx);
+    }
+    __device__ __forceinline__ unsigned ok(int dx, int dy, int dz) const {
+        const int x = i + dx, y = j + dy, z = k + dz;
+        if (x < 0 || y < 0 || z < 0 || x >= a.l.nx || y >= a.l.ny || z >= a.l.nz) return 0u;
+        return a.weight[index(dx, dy, dz)] >= a.min_weight ? 1u : 0u;
+    }
+    __device__ __forceinline__ float tsdf(int dx, int dy, int dz) const { return a.tsdf[index(dx, dy, dz)]; }
+};
+
+// bit c = corner c of the sample's cell is inside (tsdf < 0); the cell must lie in the lattice
+template <class Sampler>
+__device__ __forceinline__ unsigned mt_inside(const Sampler& s) {
+    unsigned in = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in |= (s.tsdf(c & 1, (c >> 1) & 1, c >> 2) < 0.0f ? 1u : 0u) << c;
+    return in;
+}
+
+// One sample's share of the count: the mask of the edge classes that carry a vertex, and the triangles of its cell.
+template <class Sampler>
+__device__ __forceinline__ void mt_count_sample(const MtArgs& a, const Sampler& s) {
     // which samples of the 3 x 3 x 3 neighbourhood are observed: bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)
     unsigned okb = 0;
 #pragma unroll
-    for (int q = 0; q < 27; ++q)
-        okb |= (mt_ok(a, i + q % 3 - 1, j + (q / 3) % 3 - 1, k + q / 9 - 1) ? 1u : 0u) << q;
+    for (int q = 0; q < 27; ++q) okb |= s.ok(q % 3 - 1, (q / 3) % 3 - 1, q / 9 - 1) << q;
     // live[m]: the cell at this sample - m (m = corner bits) is live
     unsigned live = 0;
 #pragma unroll
@@ -244,7 +323,7 @@ __global__ __launch_bounds__(256) void mt_count_kernel(const MtArgs a) {
     }
     unsigned mask = 0;
     if (live) {
-        const bool in0 = a.tsdf[s] < 0.0f;
+        const bool in0 = s.tsdf(0, 0, 0) < 0.0f;
 #pragma unroll
         for (int c = 1; c < 8; ++c) {
             unsigned users = 0;  // the cells that contain the edge of class c: m a subset of ~c
@@ -252,152 +331,178 @@ __global__ __launch_bounds__(256) void mt_count_kernel(const MtArgs a) {
             for (int m = 0; m < 8; ++m)
                 if ((m & c) == 0) users |= 1u << m;
             if (live & users) {  // then the far end is inside the lattice
-                const bool in1 = a.tsdf[((size_t)(k + (c >> 2)) * a.ny + (j + ((c >> 1) & 1))) * a.nx + (i + (c & 1))] < 0.0f;
+                const bool in1 = s.tsdf(c & 1, (c >> 1) & 1, c >> 2) < 0.0f;
                 if (in0 != in1) mask |= 1u << (c - 1);
             }
         }
     }
-    a.vmask[s] = (unsigned char)mask;
+    a.vmask[s.self] = (unsigned char)mask;
     unsigned nt = 0;
     if (live & 1u) {
-        const unsigned in = mt_inside(a, i, j, k);
+        const unsigned in = mt_inside(s);
         if (in != 0u && in != 255u) {
 #pragma unroll
             for (int t = 0; t < 6; ++t) nt += MT_CASES[mt_tet_case(in, t)].ntri;
         }
     }
-    a.ntri[s] = (unsigned char)nt;
+    a.ntri[s.self] = (unsigned char)nt;
 }
 
-__device__ __forceinline__ int mt_vertex_index(const MtArgs& a, size_t owner, int cls) {
+template <class Index>
+__device__ __forceinline__ int mt_vertex_index(const MtArgs& a, Index owner, int cls) {
     const unsigned m = a.vmask[owner];
     return a.vincl[owner] - __popc(m) + __popc(m & ((1u << (cls - 1)) - 1u));
 }
 
-// central-difference gradient of tsdf at a sample; false where a neighbour is outside the lattice or unobserved
-__device__ __forceinline__ bool mt_gradient(const MtArgs& a, int i, int j, int k, float& gx, float& gy, float& gz) {
+// central-difference gradient of tsdf at the sample at (dx, dy, dz), 0 .. 1 per axis; false where a neighbour is outside the lattice or
+// unobserved
+template <class Sampler>
+__device__ __forceinline__ bool mt_gradient(const Sampler& s, int dx, int dy, int dz, float& gx, float& gy, float& gz) {
 #pragma clang fp contract(off)
-    if (!(mt_ok(a, i - 1, j, k) && mt_ok(a, i + 1, j, k) && mt_ok(a, i, j - 1, k) && mt_ok(a, i, j + 1, k) && mt_ok(a, i, j, k - 1) &&
-          mt_ok(a, i, j, k + 1)))
+    if (!(s.ok(dx - 1, dy, dz) && s.ok(dx + 1, dy, dz) && s.ok(dx, dy - 1, dz) && s.ok(dx, dy + 1, dz) && s.ok(dx, dy, dz - 1) &&
+          s.ok(dx, dy, dz + 1)))
         return false;
-    const size_t s = ((size_t)k * a.ny + j) * a.nx + i, sy = (size_t)a.nx, sz = (size_t)a.nx * a.ny;
-    gx = a.tsdf[s + 1] - a.tsdf[s - 1];
-    gy = a.tsdf[s + sy] - a.tsdf[s - sy];
-    gz = a.tsdf[s + sz] - a.tsdf[s - sz];
+    gx = s.tsdf(dx + 1, dy, dz) - s.tsdf(dx - 1, dy, dz);
+    gy = s.tsdf(dx, dy + 1, dz) - s.tsdf(dx, dy - 1, dz);
+    gz = s.tsdf(dx, dy, dz + 1) - s.tsdf(dx, dy, dz - 1);
     return true;
 }
 
-__global__ __launch_bounds__(256) void mt_emit_kernel(const MtArgs a) {
+// The vertices the sample owns (mask = its vmask, non-zero): position, colour and normal of every class in the mask, in class order.
+template <class Sampler>
+__device__ __forceinline__ void mt_emit_vertices(const MtArgs& a, const Sampler& s, unsigned mask) {
 #pragma clang fp contract(off)
-    const int i = blockIdx.x * TSDF_BX + (threadIdx.x & 63), j = blockIdx.y * TSDF_BY + (threadIdx.x >> 6), k = blockIdx.z;
-    if (i >= a.nx || j >= a.ny) return;
-    const size_t n = (size_t)a.nx * a.ny * a.nz, s = ((size_t)k * a.ny + j) * a.nx + i;
-    const unsigned mask = a.vmask[s];
-    if (mask) {
-        int out = a.vincl[s] - __popc(mask);
-        const float v0 = a.tsdf[s];
-        const float x0 = a.ox + (float)i * a.voxel, y0 = a.oy + (float)j * a.voxel, z0 = a.oz + (float)k * a.voxel;
-        float g0x = 0.0f, g0y = 0.0f, g0z = 0.0f;
-        const bool have_g0 = a.normals && mt_gradient(a, i, j, k, g0x, g0y, g0z);
-        for (int c = 1; c < 8; ++c) {
-            if (!((mask >> (c - 1)) & 1u)) continue;
-            const int i1 = i + (c & 1), j1 = j + ((c >> 1) & 1), k1 = k + (c >> 2);
-            const size_t s1 = ((size_t)k1 * a.ny + j1) * a.nx + i1;
-            const float v1 = a.tsdf[s1];
-            const float t = v0 / (v0 - v1);
-            const float x1 = a.ox + (float)i1 * a.voxel, y1 = a.oy + (float)j1 * a.voxel, z1 = a.oz + (float)k1 * a.voxel;
-            a.vertices[3 * (size_t)out + 0] = x0 + t * (x1 - x0);
-            a.vertices[3 * (size_t)out + 1] = y0 + t * (y1 - y0);
-            a.vertices[3 * (size_t)out + 2] = z0 + t * (z1 - z0);
-            if (a.colors) {
-                const float cw0 = a.cweight[s], cw1 = a.cweight[s1];
+    int out = a.vincl[s.self] - __popc(mask);
+    const float v0 = s.tsdf(0, 0, 0);
+    const float x0 = a.ox + (float)s.i * a.voxel, y0 = a.oy + (float)s.j * a.voxel, z0 = a.oz + (float)s.k * a.voxel;
+    float g0x = 0.0f, g0y = 0.0f, g0z = 0.0f;
+    const bool have_g0 = a.normals && mt_gradient(s, 0, 0, 0, g0x, g0y, g0z);
+    for (int c = 1; c < 8; ++c) {
+        if (!((mask >> (c - 1)) & 1u)) continue;
+        const int dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;
+        const float v1 = s.tsdf(dx, dy, dz);
+        const float t = v0 / (v0 - v1);
+        const float x1 = a.ox + (float)(s.i + dx) * a.voxel, y1 = a.oy + (float)(s.j + dy) * a.voxel, z1 = a.oz + (float)(s.k + dz) * a.voxel;
+        a.vertices[3 * (size_t)out + 0] = x0 + t * (x1 - x0);
+        a.vertices[3 * (size_t)out + 1] = y0 + t * (y1 - y0);
+        a.vertices[3 * (size_t)out + 2] = z0 + t * (z1 - z0);
+        if (a.colors) {
+            const auto p1 = s.index(dx, dy, dz);             // observed, so a pool has a slot for its block;
+            const bool hole = Sampler::kHoles && p1 < 0;     // constant false for a sampler without holes
+            const size_t s1 = hole ? s.self : (size_t)p1;
+            const float cw0 = a.cweight[s.self], cw1 = hole ? 0.0f : a.cweight[s1];
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float c0 = a.rgb[ch * n + s], c1 = a.rgb[ch * n + s1];
-                    float cv = 128.0f;
-                    if (cw0 > 0.0f && cw1 > 0.0f) cv = c0 + t * (c1 - c0);
-                    else if (cw0 > 0.0f) cv = c0;
-                    else if (cw1 > 0.0f) cv = c1;
-                    cv = floorf(cv + 0.5f);
-                    a.colors[3 * (size_t)out + ch] = (unsigned char)fminf(fmaxf(cv, 0.0f), 255.0f);
-                }
+            for (int ch = 0; ch < 3; ++ch) {
+                const float c0 = a.rgb[ch * s.planes + s.self], c1 = a.rgb[ch * s.planes + s1];
+                float cv = 128.0f;
+                if (cw0 > 0.0f && cw1 > 0.0f) cv = c0 + t * (c1 - c0);
+                else if (cw0 > 0.0f) cv = c0;
+                else if (cw1 > 0.0f) cv = c1;
+                cv = floorf(cv + 0.5f);
+                a.colors[3 * (size_t)out + ch] = (unsigned char)fminf(fmaxf(cv, 0.0f), 255.0f);
             }
-            if (a.normals) {
-                float nx = 0.0f, ny = 0.0f, nz = 0.0f, g1x, g1y, g1z;
-                if (have_g0 && mt_gradient(a, i1, j1, k1, g1x, g1y, g1z)) {
-                    const float gx = g0x + t * (g1x - g0x), gy = g0y + t * (g1y - g0y), gz = g0z + t * (g1z - g0z);
-                    const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
-                    if (len > 0.0f && len < __builtin_inff()) {
-                        nx = gx / len;
-                        ny = gy / len;
-                        nz = gz / len;
-                    }
-                }
-                a.normals[3 * (size_t)out + 0] = nx;
-                a.normals[3 * (size_t)out + 1] = ny;
-                a.normals[3 * (size_t)out + 2] = nz;
-            }
-            ++out;
         }
-    }
-    const unsigned nt = a.ntri[s];
-    if (nt) {
-        int f = a.tincl[s] - (int)nt;
-        const unsigned in = mt_inside(a, i, j, k);
-        for (int t = 0; t < 6; ++t) {
-            const MtCase& cs = MT_CASES[mt_tet_case(in, t)];
-            const bool neg = (MT_NEGATIVE >> t) & 1;
-            for (int tri = 0; tri < cs.ntri; ++tri) {
-                int idx[3];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    const unsigned code = cs.edge[3 * tri + e];
-                    const int lo = MT_TET[t][code & 3u], hi = MT_TET[t][code >> 2];
-                    const size_t owner = ((size_t)(k + (lo >> 2)) * a.ny + (j + ((lo >> 1) & 1))) * a.nx + (i + (lo & 1));
-                    idx[e] = mt_vertex_index(a, owner, hi ^ lo);
+        if (a.normals) {
+            float nx = 0.0f, ny = 0.0f, nz = 0.0f, g1x, g1y, g1z;
+            if (have_g0 && mt_gradient(s, dx, dy, dz, g1x, g1y, g1z)) {
+                const float gx = g0x + t * (g1x - g0x), gy = g0y + t * (g1y - g0y), gz = g0z + t * (g1z - g0z);
+                const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
+                if (len > 0.0f && len < __builtin_inff()) {
+                    nx = gx / len;
+                    ny = gy / len;
+                    nz = gz / len;
                 }
-                a.faces[3 * (size_t)f + 0] = idx[0];
-                a.faces[3 * (size_t)f + 1] = neg ? idx[2] : idx[1];
-                a.faces[3 * (size_t)f + 2] = neg ? idx[1] : idx[2];
-                ++f;
             }
+            a.normals[3 * (size_t)out + 0] = nx;
+            a.normals[3 * (size_t)out + 1] = ny;
+            a.normals[3 * (size_t)out + 2] = nz;
+        }
+        ++out;
+    }
+}
+
+// The triangles of the sample's cell (nt = its ntri, non-zero), by tetrahedron, then triangle.
+template <class Sampler>
+__device__ __forceinline__ void mt_emit_faces(const MtArgs& a, const Sampler& s, unsigned nt) {
+    int f = a.tincl[s.self] - (int)nt;
+    const unsigned in = mt_inside(s);
+    for (int t = 0; t < 6; ++t) {
+        const MtCase& cs = MT_CASES[mt_tet_case(in, t)];
+        const bool neg = (MT_NEGATIVE >> t) & 1;
+        for (int tri = 0; tri < cs.ntri; ++tri) {
+            int idx[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                const unsigned code = cs.edge[3 * tri + e];
+                const int lo = MT_TET[t][code & 3u], hi = MT_TET[t][code >> 2];
+                const auto owner = s.index(lo & 1, (lo >> 1) & 1, lo >> 2);  // a corner of a live cell, so a pool has its block
+                idx[e] = Sampler::kHoles && owner < 0 ? 0 : mt_vertex_index(a, owner, hi ^ lo);
+            }
+            a.faces[3 * (size_t)f + 0] = idx[0];
+            a.faces[3 * (size_t)f + 1] = neg ? idx[2] : idx[1];
+            a.faces[3 * (size_t)f + 2] = neg ? idx[1] : idx[2];
+            ++f;
         }
     }
 }
 
-static int mt_fill(MtArgs& a, const float* tsdf, const float* weight, const int* dims_host, const float* origin_host, float voxel,
-                   float min_weight) {
-    if (!tsdf || !weight || !dims_host || !origin_host) return PMN_ERR_ARG;
-    if (!(voxel > 0.0f) || !std::isfinite(voxel) || !std::isfinite(min_weight)) return PMN_ERR_ARG;
-    const int nx = dims_host[0], ny = dims_host[1], nz = dims_host[2];
-    if (nx < 1 || ny < 1 || nz < 1 || nz > 65535 || (long long)nx * ny * nz > 2147483647LL) return PMN_ERR_SHAPE;
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(origin_host[c])) return PMN_ERR_ARG;
-    memset(&a, 0, sizeof(a));
+__global__ __launch_bounds__(256) void mt_count_kernel(const MtArgs a) {
+    const int i = blockIdx.x * TSDF_BX + (threadIdx.x & 63), j = blockIdx.y * TSDF_BY + (threadIdx.x >> 6), k = blockIdx.z;
+    if (i >= a.l.nx || j >= a.l.ny) return;
+    mt_count_sample(a, MtDenseSampler(a, i, j, k));
+}
+
+__global__ __launch_bounds__(256) void mt_emit_kernel(const MtArgs a) {
+    const int i = blockIdx.x * TSDF_BX + (threadIdx.x & 63), j = blockIdx.y * TSDF_BY + (threadIdx.x >> 6), k = blockIdx.z;
+    if (i >= a.l.nx || j >= a.l.ny) return;
+    const MtDenseSampler s(a, i, j, k);
+    const unsigned mask = a.vmask[s.self];
+    if (mask) mt_emit_vertices(a, s, mask);
+    const unsigned nt = a.ntri[s.self];
+    if (nt) mt_emit_faces(a, s, nt);
+}
+
+// What count and emit share (``a`` zeroed by the caller).  A pool sample without a slot has weight 0 and must stay unobserved, so
+// there min_weight must be positive.
+static int mt_fill(MtArgs& a, bool blocks, const float* tsdf, const float* weight, const int* dims_host, const float* origin_host,
+                   float voxel, float min_weight, const unsigned char* vertex_mask, const unsigned char* cell_triangles) {
+    if (!tsdf || !weight || !vertex_mask || !cell_triangles) return PMN_ERR_ARG;
+    if (blocks ? !tsdf_positive(min_weight) : !std::isfinite(min_weight)) return PMN_ERR_ARG;
+    const int rc = tsdf_grid(a, blocks, dims_host, origin_host, voxel);
+    if (rc != PMN_OK) return rc;
     a.tsdf = tsdf;
     a.weight = weight;
-    a.nx = nx;
-    a.ny = ny;
-    a.nz = nz;
-    a.ox = origin_host[0];
-    a.oy = origin_host[1];
-    a.oz = origin_host[2];
-    a.voxel = voxel;
     a.min_weight = min_weight;
+    a.vmask = const_cast<unsigned char*>(vertex_mask);
+    a.ntri = const_cast<unsigned char*>(cell_triangles);
     return PMN_OK;
 }
 
+// what emit adds to mt_fill
+static int mt_fill_emit(MtArgs& a, const float* rgb, const float* cweight, const int* vertex_scan, const int* triangle_scan,
+                        float* vertices, unsigned char* colors, float* normals, int* faces) {
+    if (!vertex_scan || !triangle_scan || !vertices || !faces) return PMN_ERR_ARG;
+    if ((rgb == nullptr) != (cweight == nullptr) || (colors != nullptr && rgb == nullptr)) return PMN_ERR_ARG;
+    a.rgb = rgb;
+    a.cweight = cweight;
+    a.vincl = vertex_scan;
+    a.tincl = triangle_scan;
+    a.vertices = vertices;
+    a.colors = colors;
+    a.normals = normals;
+    a.faces = faces;
+    return PMN_OK;
+}
+
+static const float MT_NO_ORIGIN[3] = {0.0f, 0.0f, 0.0f};  // counting places nothing
+
 extern "C" int pmn_mt_count(const float* tsdf, const float* weight, const int* dims_host, float min_weight, unsigned char* vertex_mask,
                             unsigned char* cell_triangles, void* stream) {
-    static const float origin[3] = {0.0f, 0.0f, 0.0f};
-    if (!vertex_mask || !cell_triangles) return PMN_ERR_ARG;
     MtArgs a;
-    const int rc = mt_fill(a, tsdf, weight, dims_host, origin, 1.0f, min_weight);
+    memset(&a, 0, sizeof(a));
+    const int rc = mt_fill(a, false, tsdf, weight, dims_host, MT_NO_ORIGIN, 1.0f, min_weight, vertex_mask, cell_triangles);
     if (rc != PMN_OK) return rc;
-    a.vmask = vertex_mask;
-    a.ntri = cell_triangles;
-    const dim3 grid((a.nx + TSDF_BX - 1) / TSDF_BX, (a.ny + TSDF_BY - 1) / TSDF_BY, a.nz);
-    PMN_LAUNCH(mt_count_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    PMN_LAUNCH(mt_count_kernel, tsdf_dense_launch(a.l), dim3(256), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
@@ -406,23 +511,12 @@ extern "C" int pmn_mt_emit(const float* tsdf, const float* weight, const float* 
                            const float* origin_host, float voxel, float min_weight, const unsigned char* vertex_mask,
                            const unsigned char* cell_triangles, const int* vertex_scan, const int* triangle_scan, float* vertices,
                            unsigned char* colors, float* normals, int* faces, void* stream) {
-    if (!vertex_mask || !cell_triangles || !vertex_scan || !triangle_scan || !vertices || !faces) return PMN_ERR_ARG;
-    if ((rgb == nullptr) != (cweight == nullptr) || (colors != nullptr && rgb == nullptr)) return PMN_ERR_ARG;
     MtArgs a;
-    const int rc = mt_fill(a, tsdf, weight, dims_host, origin_host, voxel, min_weight);
+    memset(&a, 0, sizeof(a));
+    int rc = mt_fill(a, false, tsdf, weight, dims_host, origin_host, voxel, min_weight, vertex_mask, cell_triangles);
+    if (rc == PMN_OK) rc = mt_fill_emit(a, rgb, cweight, vertex_scan, triangle_scan, vertices, colors, normals, faces);
     if (rc != PMN_OK) return rc;
-    a.rgb = rgb;
-    a.cweight = cweight;
-    a.vmask = const_cast<unsigned char*>(vertex_mask);
-    a.ntri = const_cast<unsigned char*>(cell_triangles);
-    a.vincl = vertex_scan;
-    a.tincl = triangle_scan;
-    a.vertices = vertices;
-    a.colors = colors;
-    a.normals = normals;
-    a.faces = faces;
-    const dim3 grid((a.nx + TSDF_BX - 1) / TSDF_BX, (a.ny + TSDF_BY - 1) / TSDF_BY, a.nz);
-    PMN_LAUNCH(mt_emit_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    PMN_LAUNCH(mt_emit_kernel, tsdf_dense_launch(a.l), dim3(256), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
@@ -436,41 +530,17 @@ extern "C" int pmn_mt_emit(const float* tsdf, const float* weight, const float* 
 // A sample of a border block whose index is >= n on some axis is outside the lattice: never integrated, never meshed.  A sample outside
 // the lattice or in a block without a slot reads as tsdf 1, weight 0, cweight 0, so with min_weight > 0 (required) no cell that touches
 // one is live and everything the dense kernels would emit from the same planes comes out of the pool, in pool order.
-#define TSDF_SB 8                                   // samples per block side
-#define TSDF_SB3 (TSDF_SB * TSDF_SB * TSDF_SB)      // samples per block = threads per workgroup
-#define TSDF_MAX_AXIS (1 << 19)
-#define TSDF_MAX_TABLE (1LL << 28)
-
-struct TsdfLattice {
-    int nx, ny, nz, nbx, nby, nbz;
-};
-
-static int tsdf_lattice(TsdfLattice& l, const int* dims_host) {
-    if (!dims_host) return PMN_ERR_ARG;
-    l.nx = dims_host[0];
-    l.ny = dims_host[1];
-    l.nz = dims_host[2];
-    if (l.nx < 2 || l.ny < 2 || l.nz < 2 || l.nx >= TSDF_MAX_AXIS || l.ny >= TSDF_MAX_AXIS || l.nz >= TSDF_MAX_AXIS) return PMN_ERR_SHAPE;
-    l.nbx = (l.nx + TSDF_SB - 1) / TSDF_SB;
-    l.nby = (l.ny + TSDF_SB - 1) / TSDF_SB;
-    l.nbz = (l.nz + TSDF_SB - 1) / TSDF_SB;
-    if ((long long)l.nbx * l.nby * l.nbz > TSDF_MAX_TABLE) return PMN_ERR_SHAPE;
-    return PMN_OK;
-}
-
-static bool tsdf_pool_size_ok(int n_blocks) { return n_blocks >= 1 && (long long)n_blocks * TSDF_SB3 <= 2147483647LL; }
-
+// (TSDF_SB, the lattice limits and the pool's argument struct of the integration are with the grid, at the top.)
+//
 // Marking: a thread per pixel of every view of the launch (blockIdx.y = the view, so the view block is read with scalar loads).  The
 // samples that pmn_tsdf_integrate maps to a valid pixel (u, v) of depth d with |sdf| <= trunc lie in the section of the pyramid through
 // the pixel's corners (u +- 0.5, v +- 0.5) between the camera depths max(d - trunc, 0) (0 = the apex: a superset of any positive clamp
 // and free of a unit) and d + trunc.  Its eight corners go to the world through K^-1 and E^-1 (v.cam holds K^-1 row-major, then the
 // upper 3 x 4 of E^-1, inverted on the host in float64); their axis-aligned box grown by one voxel and clipped to the lattice gives the
 // blocks.  flags get plain byte stores of 1: whichever thread writes, the byte is 1.
-struct TsdfMarkArgs {
+struct TsdfMarkArgs : TsdfGrid {
     unsigned char* flags;  // [nbz][nby][nbx]
     int* overflow;
-    TsdfLattice l;
-    float ox, oy, oz, voxel, trunc;
     TsdfView v[PMN_TSDF_MAX_VIEWS];
 };
 
@@ -528,29 +598,17 @@ __global__ __launch_bounds__(256) void tsdf_mark_blocks_kernel(const TsdfMarkArg
             for (int bx = b0[0]; bx <= b1[0]; ++bx) a.flags[((size_t)bz * a.l.nby + by) * a.l.nbx + bx] = 1;
 }
 
-static int tsdf_check_grid(const float* origin_host, float voxel, float trunc) {
-    if (!origin_host || !(voxel > 0.0f) || !(trunc > 0.0f) || !std::isfinite(voxel) || !std::isfinite(trunc)) return PMN_ERR_ARG;
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(origin_host[c])) return PMN_ERR_ARG;
-    return PMN_OK;
-}
-
 extern "C" int pmn_tsdf_mark_blocks(unsigned char* flags, int* overflow, const int* dims_host, const float* origin_host, float voxel,
                                     float trunc, const float* maps, long long slot_stride, const int* slots_host, const int* hw_host,
                                     const void* const* masks_host, const float* inv_cams_host, int n_views, void* stream) {
-    if (!flags || !overflow || !dims_host || !maps || !slots_host || !hw_host || !inv_cams_host || slot_stride < 1) return PMN_ERR_ARG;
-    int rc = tsdf_check_grid(origin_host, voxel, trunc);
-    if (rc != PMN_OK) return rc;
+    if (!flags || !overflow || !maps || !slots_host || !hw_host || !inv_cams_host || slot_stride < 1 || !tsdf_positive(trunc)) return PMN_ERR_ARG;
     if (n_views < 1 || n_views > PMN_TSDF_MAX_VIEWS) return PMN_ERR_SHAPE;
     TsdfMarkArgs a;
     memset(&a, 0, sizeof(a));
-    if ((rc = tsdf_lattice(a.l, dims_host)) != PMN_OK) return rc;
+    int rc = tsdf_grid(a, true, dims_host, origin_host, voxel);
+    if (rc != PMN_OK) return rc;
     a.flags = flags;
     a.overflow = overflow;
-    a.ox = origin_host[0];
-    a.oy = origin_host[1];
-    a.oz = origin_host[2];
-    a.voxel = voxel;
     a.trunc = trunc;
     if ((rc = tsdf_fill_views(a.v, maps, slot_stride, slots_host, hw_host, masks_host, nullptr, inv_cams_host, n_views)) != PMN_OK) return rc;
     long long pixels = 0;
@@ -564,15 +622,6 @@ extern "C" int pmn_tsdf_mark_blocks(unsigned char* flags, int* overflow, const i
 
 // Integration of the listed blocks: a workgroup per block, a thread per sample (a wave = one 8 x 8 plane = 256 contiguous bytes of
 // every pool plane); the sample's lattice index comes from the block list, everything else is tsdf_fold_sample.
-struct TsdfBlockArgs {
-    float *tsdf, *weight, *rgb, *cweight;
-    const int* blocks;
-    int nblocks, nviews;
-    TsdfLattice l;
-    float ox, oy, oz, voxel, trunc;
-    TsdfView v[PMN_TSDF_MAX_VIEWS];
-};
-
 __global__ __launch_bounds__(TSDF_SB3) void tsdf_integrate_blocks_kernel(const TsdfBlockArgs a) {
 #pragma clang fp contract(off)
     const int lb = a.blocks[blockIdx.x];
@@ -589,51 +638,31 @@ extern "C" int pmn_tsdf_integrate_blocks(float* tsdf, float* weight, float* rgb,
                                          const int* dims_host, const float* origin_host, float voxel, float trunc, const float* maps,
                                          long long slot_stride, const int* slots_host, const int* hw_host, const void* const* masks_host,
                                          const void* const* images_host, const float* cams_host, int n_views, void* stream) {
-    if (!tsdf || !weight || !blocks || !dims_host || !maps || !slots_host || !hw_host || !cams_host || slot_stride < 1) return PMN_ERR_ARG;
-    if ((rgb == nullptr) != (cweight == nullptr)) return PMN_ERR_ARG;
-    int rc = tsdf_check_grid(origin_host, voxel, trunc);
-    if (rc != PMN_OK) return rc;
-    if (n_views < 1 || n_views > PMN_TSDF_MAX_VIEWS || !tsdf_pool_size_ok(n_blocks)) return PMN_ERR_SHAPE;
+    if (!blocks) return PMN_ERR_ARG;
+    if (!tsdf_pool_size_ok(n_blocks)) return PMN_ERR_SHAPE;
     TsdfBlockArgs a;
     memset(&a, 0, sizeof(a));
-    if ((rc = tsdf_lattice(a.l, dims_host)) != PMN_OK) return rc;
-    a.tsdf = tsdf;
-    a.weight = weight;
-    a.rgb = rgb;
-    a.cweight = cweight;
+    const int rc = tsdf_integrate_fill(a, true, tsdf, weight, rgb, cweight, dims_host, origin_host, voxel, trunc, maps, slot_stride,
+                                       slots_host, hw_host, masks_host, images_host, cams_host, n_views);
+    if (rc != PMN_OK) return rc;
     a.blocks = blocks;
     a.nblocks = n_blocks;
-    a.nviews = n_views;
-    a.ox = origin_host[0];
-    a.oy = origin_host[1];
-    a.oz = origin_host[2];
-    a.voxel = voxel;
-    a.trunc = trunc;
-    if ((rc = tsdf_fill_views(a.v, maps, slot_stride, slots_host, hw_host, masks_host, images_host, cams_host, n_views)) != PMN_OK) return rc;
     PMN_LAUNCH(tsdf_integrate_blocks_kernel, dim3(n_blocks), dim3(TSDF_SB3), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
 
-// Marching tetrahedra over the pool: the rule of mt_count_kernel / mt_emit_kernel with the block and its halo staged in LDS.  Counting
-// reads the samples at -1 .. +1 of every sample, emitting (the gradients of both ends of an edge) at -1 .. +2: both stage the 11^3
-// samples at block-local -1 .. 9 -- tsdf and the bit weight >= min_weight, 6.7 KB -- through the slots of the 27 blocks around, read
-// from the table once per workgroup, instead of up to 20 table lookups per sample.
+// Marching tetrahedra over the pool: mt_count_sample / mt_emit_vertices / mt_emit_faces, the very code of the dense kernels, over a
+// sampler that reads the block and its halo from LDS.  Counting reads the samples at -1 .. +1 of every sample, emitting (the gradients
+// of both ends of an edge) at -1 .. +2: both stage the 11^3 samples at block-local -1 .. 9 -- tsdf and the bit weight >= min_weight,
+// 6.7 KB -- through the slots of the 27 blocks around, read from the table once per workgroup, instead of up to 20 table lookups per
+// sample.
 #define MT_HALO 11
 #define MT_HALO3 (MT_HALO * MT_HALO * MT_HALO)
 
-struct MtBlockArgs {
-    const float *tsdf, *weight, *rgb, *cweight;
+struct MtBlockArgs : MtArgs {  // the planes are the pool's: [B][8][8][8], the scans in pool order
     const int *table, *blocks;
     int nblocks;
-    TsdfLattice l;
-    float ox, oy, oz, voxel, min_weight;
-    unsigned char *vmask, *ntri;  // [B][8][8][8]; count: outputs; emit: inputs
-    const int *vincl, *tincl;     // emit: INCLUSIVE scans of popcount(vmask) and of ntri in pool order
-    float* vertices;
-    unsigned char* colors;
-    float* normals;
-    int* faces;
 };
 
 struct MtTile {
@@ -691,186 +720,63 @@ __device__ __forceinline__ bool mt_stage(const MtBlockArgs& a, MtTile& m) {
     return true;
 }
 
-// bit c = corner c of the cell at block-local (li, lj, lk) is inside (tsdf < 0)
-__device__ __forceinline__ unsigned mt_tile_inside(const MtTile& m, int li, int lj, int lk) {
-    unsigned in = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) in |= (m.t[mt_tile_at(li + (c & 1), lj + ((c >> 1) & 1), lk + (c >> 2))] < 0.0f ? 1u : 0u) << c;
-    return in;
-}
+// the sampler of mt_count_sample / mt_emit_* over a staged tile: neighbours come from LDS, plane indices through the 27 slots
+struct MtPoolSampler {
+    static constexpr bool kHoles = true;
+    const MtTile& m;
+    const int li, lj, lk;  // block-local
+    const int i, j, k;
+    const size_t self, planes;
+    __device__ __forceinline__ MtPoolSampler(const MtBlockArgs& a, const MtTile& m_, size_t self_)
+        : m(m_), li(threadIdx.x & 7), lj((threadIdx.x >> 3) & 7), lk(threadIdx.x >> 6), i(m_.bi * TSDF_SB + li), j(m_.bj * TSDF_SB + lj),
+          k(m_.bk * TSDF_SB + lk), self(self_), planes((size_t)a.nblocks * TSDF_SB3) {}
+    __device__ __forceinline__ int index(int dx, int dy, int dz) const { return mt_pool_at(m, li + dx, lj + dy, lk + dz); }
+    __device__ __forceinline__ unsigned ok(int dx, int dy, int dz) const { return m.ok[mt_tile_at(li + dx, lj + dy, lk + dz)]; }
+    __device__ __forceinline__ float tsdf(int dx, int dy, int dz) const { return m.t[mt_tile_at(li + dx, lj + dy, lk + dz)]; }
+};
 
 __global__ __launch_bounds__(TSDF_SB3) void mt_count_blocks_kernel(const MtBlockArgs a) {
     __shared__ MtTile m;
-    const int li = threadIdx.x & 7, lj = (threadIdx.x >> 3) & 7, lk = threadIdx.x >> 6;
     const size_t s = (size_t)blockIdx.x * TSDF_SB3 + threadIdx.x;
     if (!mt_stage(a, m)) {  // the scans must not see what the caller's buffers held
         a.vmask[s] = 0;
         a.ntri[s] = 0;
         return;
     }
-    unsigned okb = 0;  // as in mt_count_kernel: bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)
-#pragma unroll
-    for (int q = 0; q < 27; ++q) okb |= (unsigned)m.ok[mt_tile_at(li + q % 3 - 1, lj + (q / 3) % 3 - 1, lk + q / 9 - 1)] << q;
-    unsigned live = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int bx = 1 - (c & 1), by = 1 - ((c >> 1) & 1), bz = 1 - (c >> 2);
-        const unsigned need = (1u << (bz * 9 + by * 3 + bx)) * (1u | 2u | 8u | 16u | 512u | 1024u | 4096u | 8192u);
-        live |= ((okb & need) == need ? 1u : 0u) << c;
-    }
-    unsigned mask = 0;
-    if (live) {
-        const bool in0 = m.t[mt_tile_at(li, lj, lk)] < 0.0f;
-#pragma unroll
-        for (int c = 1; c < 8; ++c) {
-            unsigned users = 0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if ((q & c) == 0) users |= 1u << q;
-            if (live & users) {
-                const bool in1 = m.t[mt_tile_at(li + (c & 1), lj + ((c >> 1) & 1), lk + (c >> 2))] < 0.0f;
-                if (in0 != in1) mask |= 1u << (c - 1);
-            }
-        }
-    }
-    a.vmask[s] = (unsigned char)mask;
-    unsigned nt = 0;
-    if (live & 1u) {
-        const unsigned in = mt_tile_inside(m, li, lj, lk);
-        if (in != 0u && in != 255u) {
-#pragma unroll
-            for (int t = 0; t < 6; ++t) nt += MT_CASES[mt_tet_case(in, t)].ntri;
-        }
-    }
-    a.ntri[s] = (unsigned char)nt;
-}
-
-// central-difference gradient at block-local (li, lj, lk), 0 .. 8 per axis; false where a neighbour is outside or unobserved
-__device__ __forceinline__ bool mt_tile_gradient(const MtTile& m, int li, int lj, int lk, float& gx, float& gy, float& gz) {
-#pragma clang fp contract(off)
-    const int c = mt_tile_at(li, lj, lk), sy = MT_HALO, sz = MT_HALO * MT_HALO;
-    if (!(m.ok[c - 1] && m.ok[c + 1] && m.ok[c - sy] && m.ok[c + sy] && m.ok[c - sz] && m.ok[c + sz])) return false;
-    gx = m.t[c + 1] - m.t[c - 1];
-    gy = m.t[c + sy] - m.t[c - sy];
-    gz = m.t[c + sz] - m.t[c - sz];
-    return true;
+    mt_count_sample(a, MtPoolSampler(a, m, s));
 }
 
 __global__ __launch_bounds__(TSDF_SB3) void mt_emit_blocks_kernel(const MtBlockArgs a) {
-#pragma clang fp contract(off)
     __shared__ MtTile m;
-    const size_t n = (size_t)a.nblocks * TSDF_SB3, s = (size_t)blockIdx.x * TSDF_SB3 + threadIdx.x;
+    const size_t s = (size_t)blockIdx.x * TSDF_SB3 + threadIdx.x;
     const unsigned mask = a.vmask[s], nt = a.ntri[s];
     if (!__syncthreads_or((int)(mask | nt))) return;  // most blocks of the band hold no surface: nothing to stage
     if (!mt_stage(a, m)) return;
-    const int li = threadIdx.x & 7, lj = (threadIdx.x >> 3) & 7, lk = threadIdx.x >> 6;
-    const int i = m.bi * TSDF_SB + li, j = m.bj * TSDF_SB + lj, k = m.bk * TSDF_SB + lk;
-    if (mask) {
-        int out = a.vincl[s] - __popc(mask);
-        const float v0 = m.t[mt_tile_at(li, lj, lk)];
-        const float x0 = a.ox + (float)i * a.voxel, y0 = a.oy + (float)j * a.voxel, z0 = a.oz + (float)k * a.voxel;
-        float g0x = 0.0f, g0y = 0.0f, g0z = 0.0f;
-        const bool have_g0 = a.normals && mt_tile_gradient(m, li, lj, lk, g0x, g0y, g0z);
-        for (int c = 1; c < 8; ++c) {
-            if (!((mask >> (c - 1)) & 1u)) continue;
-            const int dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;
-            const float v1 = m.t[mt_tile_at(li + dx, lj + dy, lk + dz)];
-            const float t = v0 / (v0 - v1);
-            const float x1 = a.ox + (float)(i + dx) * a.voxel, y1 = a.oy + (float)(j + dy) * a.voxel, z1 = a.oz + (float)(k + dz) * a.voxel;
-            a.vertices[3 * (size_t)out + 0] = x0 + t * (x1 - x0);
-            a.vertices[3 * (size_t)out + 1] = y0 + t * (y1 - y0);
-            a.vertices[3 * (size_t)out + 2] = z0 + t * (z1 - z0);
-            if (a.colors) {
-                const int p1 = mt_pool_at(m, li + dx, lj + dy, lk + dz);  // observed, so its block has a slot
-                const size_t s1 = p1 < 0 ? s : (size_t)p1;
-                const float cw0 = a.cweight[s], cw1 = p1 < 0 ? 0.0f : a.cweight[s1];
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float c0 = a.rgb[ch * n + s], c1 = a.rgb[ch * n + s1];
-                    float cv = 128.0f;
-                    if (cw0 > 0.0f && cw1 > 0.0f) cv = c0 + t * (c1 - c0);
-                    else if (cw0 > 0.0f) cv = c0;
-                    else if (cw1 > 0.0f) cv = c1;
-                    cv = floorf(cv + 0.5f);
-                    a.colors[3 * (size_t)out + ch] = (unsigned char)fminf(fmaxf(cv, 0.0f), 255.0f);
-                }
-            }
-            if (a.normals) {
-                float nx = 0.0f, ny = 0.0f, nz = 0.0f, g1x, g1y, g1z;
-                if (have_g0 && mt_tile_gradient(m, li + dx, lj + dy, lk + dz, g1x, g1y, g1z)) {
-                    const float gx = g0x + t * (g1x - g0x), gy = g0y + t * (g1y - g0y), gz = g0z + t * (g1z - g0z);
-                    const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
-                    if (len > 0.0f && len < __builtin_inff()) {
-                        nx = gx / len;
-                        ny = gy / len;
-                        nz = gz / len;
-                    }
-                }
-                a.normals[3 * (size_t)out + 0] = nx;
-                a.normals[3 * (size_t)out + 1] = ny;
-                a.normals[3 * (size_t)out + 2] = nz;
-            }
-            ++out;
-        }
-    }
-    if (nt) {
-        int f = a.tincl[s] - (int)nt;
-        const unsigned in = mt_tile_inside(m, li, lj, lk);
-        for (int t = 0; t < 6; ++t) {
-            const MtCase& cs = MT_CASES[mt_tet_case(in, t)];
-            const bool neg = (MT_NEGATIVE >> t) & 1;
-            for (int tri = 0; tri < cs.ntri; ++tri) {
-                int idx[3];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    const unsigned code = cs.edge[3 * tri + e];
-                    const int lo = MT_TET[t][code & 3u], hi = MT_TET[t][code >> 2], cls = hi ^ lo;
-                    const int owner = mt_pool_at(m, li + (lo & 1), lj + ((lo >> 1) & 1), lk + (lo >> 2));  // a corner of a live cell
-                    const unsigned om = owner < 0 ? 0u : a.vmask[owner];
-                    idx[e] = owner < 0 ? 0 : a.vincl[owner] - __popc(om) + __popc(om & ((1u << (cls - 1)) - 1u));
-                }
-                a.faces[3 * (size_t)f + 0] = idx[0];
-                a.faces[3 * (size_t)f + 1] = neg ? idx[2] : idx[1];
-                a.faces[3 * (size_t)f + 2] = neg ? idx[1] : idx[2];
-                ++f;
-            }
-        }
-    }
+    const MtPoolSampler smp(a, m, s);
+    if (mask) mt_emit_vertices(a, smp, mask);
+    if (nt) mt_emit_faces(a, smp, nt);
 }
 
+// mt_fill, then what the pool adds
 static int mt_blocks_fill(MtBlockArgs& a, const float* tsdf, const float* weight, const int* table, const int* blocks, int n_blocks,
-                          const int* dims_host, const float* origin_host, float voxel, float min_weight) {
-    if (!tsdf || !weight || !table || !blocks || !origin_host) return PMN_ERR_ARG;
-    if (!(voxel > 0.0f) || !std::isfinite(voxel) || !(min_weight > 0.0f) || !std::isfinite(min_weight)) return PMN_ERR_ARG;
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(origin_host[c])) return PMN_ERR_ARG;
+                          const int* dims_host, const float* origin_host, float voxel, float min_weight, const unsigned char* vertex_mask,
+                          const unsigned char* cell_triangles) {
+    if (!table || !blocks) return PMN_ERR_ARG;
     if (!tsdf_pool_size_ok(n_blocks)) return PMN_ERR_SHAPE;
-    memset(&a, 0, sizeof(a));
-    const int rc = tsdf_lattice(a.l, dims_host);
-    if (rc != PMN_OK) return rc;
-    a.tsdf = tsdf;
-    a.weight = weight;
     a.table = table;
     a.blocks = blocks;
     a.nblocks = n_blocks;
-    a.ox = origin_host[0];
-    a.oy = origin_host[1];
-    a.oz = origin_host[2];
-    a.voxel = voxel;
-    a.min_weight = min_weight;
-    return PMN_OK;
+    return mt_fill(a, true, tsdf, weight, dims_host, origin_host, voxel, min_weight, vertex_mask, cell_triangles);
 }
 
 extern "C" int pmn_mt_count_blocks(const float* tsdf, const float* weight, const int* table, const int* blocks, int n_blocks,
                                    const int* dims_host, float min_weight, unsigned char* vertex_mask, unsigned char* cell_triangles,
                                    void* stream) {
-    static const float origin[3] = {0.0f, 0.0f, 0.0f};
-    if (!vertex_mask || !cell_triangles) return PMN_ERR_ARG;
     MtBlockArgs a;
-    const int rc = mt_blocks_fill(a, tsdf, weight, table, blocks, n_blocks, dims_host, origin, 1.0f, min_weight);
+    memset(&a, 0, sizeof(a));
+    const int rc = mt_blocks_fill(a, tsdf, weight, table, blocks, n_blocks, dims_host, MT_NO_ORIGIN, 1.0f, min_weight, vertex_mask,
+                                  cell_triangles);
     if (rc != PMN_OK) return rc;
-    a.vmask = vertex_mask;
-    a.ntri = cell_triangles;
     PMN_LAUNCH(mt_count_blocks_kernel, dim3(n_blocks), dim3(TSDF_SB3), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
@@ -881,21 +787,11 @@ extern "C" int pmn_mt_emit_blocks(const float* tsdf, const float* weight, const 
                                   float min_weight, const unsigned char* vertex_mask, const unsigned char* cell_triangles,
                                   const int* vertex_scan, const int* triangle_scan, float* vertices, unsigned char* colors, float* normals,
                                   int* faces, void* stream) {
-    if (!vertex_mask || !cell_triangles || !vertex_scan || !triangle_scan || !vertices || !faces) return PMN_ERR_ARG;
-    if ((rgb == nullptr) != (cweight == nullptr) || (colors != nullptr && rgb == nullptr)) return PMN_ERR_ARG;
     MtBlockArgs a;
-    const int rc = mt_blocks_fill(a, tsdf, weight, table, blocks, n_blocks, dims_host, origin_host, voxel, min_weight);
+    memset(&a, 0, sizeof(a));
+    int rc = mt_blocks_fill(a, tsdf, weight, table, blocks, n_blocks, dims_host, origin_host, voxel, min_weight, vertex_mask, cell_triangles);
+    if (rc == PMN_OK) rc = mt_fill_emit(a, rgb, cweight, vertex_scan, triangle_scan, vertices, colors, normals, faces);
     if (rc != PMN_OK) return rc;
-    a.rgb = rgb;
-    a.cweight = cweight;
-    a.vmask = const_cast<unsigned char*>(vertex_mask);
-    a.ntri = const_cast<unsigned char*>(cell_triangles);
-    a.vincl = vertex_scan;
-    a.tincl = triangle_scan;
-    a.vertices = vertices;
-    a.colors = colors;
-    a.normals = normals;
-    a.faces = faces;
     PMN_LAUNCH(mt_emit_blocks_kernel, dim3(n_blocks), dim3(TSDF_SB3), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;

@@ -924,11 +924,8 @@ def depth_normals(depth: torch.Tensor, intrinsics, radius: int = 2, rel_thres: f
 
 
 
-def _volume_planes(tsdf, weight, rgb, cweight, what):
-    _dev(tsdf, "tsdf")
-    _dev(weight, "weight")
-    if tsdf.dim() != 3 or tsdf.numel() == 0 or weight.shape != tsdf.shape or weight.device != tsdf.device:
-        raise PmnError(f"{what}: tsdf and weight must be [nz,ny,nx] planes of one volume on one device")
+def _colour_planes(tsdf, rgb, cweight, what, layout):
+    """rgb and cweight come as a pair, on the device and in the shape of tsdf; ``layout`` words the shape rule for the message."""
     if (rgb is None) != (cweight is None):
         raise PmnError(f"{what}: rgb and cweight come together or not at all")
     if rgb is not None:
@@ -936,7 +933,15 @@ def _volume_planes(tsdf, weight, rgb, cweight, what):
         _dev(cweight, "cweight")
         if tuple(rgb.shape) != (3,) + tuple(tsdf.shape) or cweight.shape != tsdf.shape or rgb.device != tsdf.device or \
                 cweight.device != tsdf.device:
-            raise PmnError(f"{what}: rgb must be [3,nz,ny,nx] and cweight [nz,ny,nx] on the volume's device")
+            raise PmnError(f"{what}: {layout}")
+
+
+def _volume_planes(tsdf, weight, rgb, cweight, what):
+    _dev(tsdf, "tsdf")
+    _dev(weight, "weight")
+    if tsdf.dim() != 3 or tsdf.numel() == 0 or weight.shape != tsdf.shape or weight.device != tsdf.device:
+        raise PmnError(f"{what}: tsdf and weight must be [nz,ny,nx] planes of one volume on one device")
+    _colour_planes(tsdf, rgb, cweight, what, "rgb must be [3,nz,ny,nx] and cweight [nz,ny,nx] on the volume's device")
     nz, ny, nx = tsdf.shape
     if nz > 65535 or tsdf.numel() > 2 ** 31 - 1:
         raise PmnError(f"{what}: a volume holds at most 2^31 - 1 samples and 65535 planes")
@@ -949,6 +954,14 @@ def _positive_f32(v, what):
     if not (np.isfinite(v) and v > 0.0):
         raise PmnError(f"{what} must be a positive finite float32")
     return v
+
+
+def _placement(origin, voxel, trunc, what):
+    """-> (origin array, its pointer, voxel, trunc | None) as the library takes them: a finite origin, positive finite float32 sizes."""
+    org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
+    if not np.isfinite(org).all():
+        raise PmnError(f"{what}: origin must be finite")
+    return org, org_p, _positive_f32(voxel, f"{what}: voxel"), None if trunc is None else _positive_f32(trunc, f"{what}: trunc")
 
 
 def _view_args(maps, slots, sizes, cams, masks, images, dev, what):
@@ -999,10 +1012,7 @@ def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, rgb: Optional[torch
     (K row-major at map size, then the upper 3x4 of the world-to-camera extrinsic; numpy, read on the host), ``masks[n]`` a uint8
     [h,w] tensor or None, ``images[n]`` a uint8 [h,w,3] tensor or None."""
     dims, dims_p = _volume_planes(tsdf, weight, rgb, cweight, "tsdf_integrate")
-    org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
-    if not np.isfinite(org).all():
-        raise PmnError("tsdf_integrate: origin must be finite")
-    voxel, trunc = _positive_f32(voxel, "tsdf_integrate: voxel"), _positive_f32(trunc, "tsdf_integrate: trunc")
+    org, org_p, voxel, trunc = _placement(origin, voxel, trunc, "tsdf_integrate")
     V, stride, cam, keep, sl_p, hw_p, m_p, i_p = _view_args(maps, slots, sizes, cams, masks, images, tsdf.device, "tsdf_integrate")
     with torch.cuda.device(tsdf.device):
         check(_lib.lib().pmn_tsdf_integrate(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), dims_p, org_p, voxel, trunc,
@@ -1017,6 +1027,31 @@ def _popcount_u8(m: torch.Tensor) -> torch.Tensor:
     return (m + (m >> 4)) & 0x0F
 
 
+def _mt_extract(what, tsdf, color, normals, count, emit):
+    """The body of mt_extract and mt_extract_blocks over planes shaped like ``tsdf``: count, the scans, the outputs, emit.
+    ``count(vmask, ntri)`` and ``emit(vmask, ntri, vscan, tscan, vertices, colors, nrm, faces)`` make the two library calls."""
+    dev = tsdf.device
+    vmask = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
+    ntri = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        count(vmask, ntri)
+        vcount = _popcount_u8(vmask)
+        totals = torch.stack((vcount.sum(dtype=torch.int64), ntri.sum(dtype=torch.int64))).tolist()  # the feature's one host read
+        nv, nt = int(totals[0]), int(totals[1])
+        if nv > 2 ** 31 - 1 or nt > 2 ** 31 - 1:
+            raise PmnError(f"{what}: {nv} vertices / {nt} triangles do not fit int32 indices; use a larger voxel")
+        vscan = torch.cumsum(vcount.reshape(-1), 0, dtype=torch.int32)
+        tscan = torch.cumsum(ntri.reshape(-1), 0, dtype=torch.int32)
+        del vcount
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        colors = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if color else None
+        nrm = torch.empty((nv, 3), dtype=torch.float32, device=dev) if normals else None
+        if nv:
+            emit(vmask, ntri, vscan, tscan, vertices, colors, nrm, faces)
+    return vertices, faces, colors, nrm
+
+
 def mt_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, min_weight: float = 1.0,
                rgb: Optional[torch.Tensor] = None, cweight: Optional[torch.Tensor] = None, normals: bool = True):
     """pmn_mt_count + scan + pmn_mt_emit: the iso-surface tsdf = 0 of a volume by marching tetrahedra.
@@ -1024,38 +1059,23 @@ def mt_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, m
     or None), on the volume's device; vertices ordered by owning sample then edge class, faces by cell, tetrahedron, triangle.  The two
     scans are torch.cumsum on the device; ONE host read (the two totals, to size the outputs) is the only synchronisation."""
     dims, dims_p = _volume_planes(tsdf, weight, rgb, cweight, "mt_extract")
-    org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
-    if not np.isfinite(org).all():
-        raise PmnError("mt_extract: origin must be finite")
-    voxel = _positive_f32(voxel, "mt_extract: voxel")
+    org, org_p, voxel, _ = _placement(origin, voxel, None, "mt_extract")
     min_weight = float(np.float32(min_weight))
     if not np.isfinite(min_weight):
         raise PmnError("mt_extract: min_weight must be finite")
-    dev = tsdf.device
-    vmask = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
-    ntri = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L = _lib.lib()
-        check(L.pmn_mt_count(tsdf.data_ptr(), weight.data_ptr(), dims_p, min_weight, vmask.data_ptr(), ntri.data_ptr(), _stream(tsdf)),
-              "pmn_mt_count")
-        vcount = _popcount_u8(vmask)
-        totals = torch.stack((vcount.sum(dtype=torch.int64), ntri.sum(dtype=torch.int64))).tolist()  # the feature's one host read
-        nv, nt = int(totals[0]), int(totals[1])
-        if nv > 2 ** 31 - 1 or nt > 2 ** 31 - 1:
-            raise PmnError(f"mt_extract: {nv} vertices / {nt} triangles do not fit int32 indices; use a larger voxel")
-        vscan = torch.cumsum(vcount.reshape(-1), 0, dtype=torch.int32)
-        tscan = torch.cumsum(ntri.reshape(-1), 0, dtype=torch.int32)
-        del vcount
-        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
-        colors = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if rgb is not None else None
-        nrm = torch.empty((nv, 3), dtype=torch.float32, device=dev) if normals else None
-        if nv:
-            check(L.pmn_mt_emit(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), dims_p, org_p, voxel, min_weight,
-                                vmask.data_ptr(), ntri.data_ptr(), vscan.data_ptr(), tscan.data_ptr(), vertices.data_ptr(),
-                                _ptr(colors), _ptr(nrm), faces.data_ptr(), _stream(tsdf)), "pmn_mt_emit")
+    L, planes, stream = _lib.lib(), (tsdf.data_ptr(), weight.data_ptr()), _stream(tsdf)
+
+    def count(vmask, ntri):
+        check(L.pmn_mt_count(*planes, dims_p, min_weight, vmask.data_ptr(), ntri.data_ptr(), stream), "pmn_mt_count")
+
+    def emit(vmask, ntri, vscan, tscan, vertices, colors, nrm, faces):
+        check(L.pmn_mt_emit(*planes, _ptr(rgb), _ptr(cweight), dims_p, org_p, voxel, min_weight, vmask.data_ptr(), ntri.data_ptr(),
+                            vscan.data_ptr(), tscan.data_ptr(), vertices.data_ptr(), _ptr(colors), _ptr(nrm), faces.data_ptr(), stream),
+              "pmn_mt_emit")
+
+    out = _mt_extract("mt_extract", tsdf, rgb is not None, normals, count, emit)
     del dims, org
-    return vertices, faces, colors, nrm
+    return out
 
 
 # ---- block-sparse volume (DESIGN.md section 18) -----------------------------------------------------------------------------------
@@ -1079,10 +1099,8 @@ def sparse_blocks(dims) -> Tuple[int, int, int]:
 def _grid_args(dims, origin, voxel, trunc, what):
     nb = sparse_blocks(dims)
     d, d_p = _host_i32(np.asarray([int(x) for x in dims]), 3, "dims")
-    org, org_p = _host_f32(np.asarray(origin, np.float32), 3, "origin")
-    if not np.isfinite(org).all():
-        raise PmnError(f"{what}: origin must be finite")
-    return nb, (d, org), d_p, org_p, _positive_f32(voxel, f"{what}: voxel"), None if trunc is None else _positive_f32(trunc, f"{what}: trunc")
+    org, org_p, voxel, trunc = _placement(origin, voxel, trunc, what)
+    return nb, (d, org), d_p, org_p, voxel, trunc
 
 
 def inverse_cameras(cams) -> np.ndarray:
@@ -1135,13 +1153,7 @@ def _pool_planes(tsdf, weight, rgb, cweight, blocks, what):
     shape = (B,) + (SPARSE_BLOCK,) * 3
     if not 1 <= B <= SPARSE_MAX_BLOCKS or tuple(tsdf.shape) != shape or tuple(weight.shape) != shape or weight.device != tsdf.device:
         raise PmnError(f"{what}: tsdf and weight must be [B,8,8,8] pool planes on one device, 1 <= B <= {SPARSE_MAX_BLOCKS}")
-    if (rgb is None) != (cweight is None):
-        raise PmnError(f"{what}: rgb and cweight come together or not at all")
-    if rgb is not None:
-        _dev(rgb, "rgb")
-        _dev(cweight, "cweight")
-        if tuple(rgb.shape) != (3,) + shape or tuple(cweight.shape) != shape or rgb.device != tsdf.device or cweight.device != tsdf.device:
-            raise PmnError(f"{what}: rgb must be [3,B,8,8,8] and cweight [B,8,8,8] on the pool's device")
+    _colour_planes(tsdf, rgb, cweight, what, "rgb must be [3,B,8,8,8] and cweight [B,8,8,8] on the pool's device")
     if tuple(blocks.shape) != (B,) or blocks.device != tsdf.device:
         raise PmnError(f"{what}: blocks must be a contiguous int32 [B] tensor on the pool's device")
     return B
@@ -1180,32 +1192,19 @@ def mt_extract_blocks(tsdf: torch.Tensor, weight: torch.Tensor, table: torch.Ten
     min_weight = float(np.float32(min_weight))
     if not (np.isfinite(min_weight) and min_weight > 0):
         raise PmnError("mt_extract_blocks: min_weight must be positive and finite")
-    dev = tsdf.device
-    vmask = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
-    ntri = torch.empty(tsdf.shape, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L = _lib.lib()
-        check(L.pmn_mt_count_blocks(tsdf.data_ptr(), weight.data_ptr(), table.data_ptr(), blocks.data_ptr(), B, dims_p, min_weight,
-                                    vmask.data_ptr(), ntri.data_ptr(), _stream(tsdf)), "pmn_mt_count_blocks")
-        vcount = _popcount_u8(vmask)
-        totals = torch.stack((vcount.sum(dtype=torch.int64), ntri.sum(dtype=torch.int64))).tolist()  # the one host read
-        nv, nt = int(totals[0]), int(totals[1])
-        if nv > 2 ** 31 - 1 or nt > 2 ** 31 - 1:
-            raise PmnError(f"mt_extract_blocks: {nv} vertices / {nt} triangles do not fit int32 indices; use a larger voxel")
-        vscan = torch.cumsum(vcount.reshape(-1), 0, dtype=torch.int32)
-        tscan = torch.cumsum(ntri.reshape(-1), 0, dtype=torch.int32)
-        del vcount
-        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
-        colors = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if rgb is not None else None
-        nrm = torch.empty((nv, 3), dtype=torch.float32, device=dev) if normals else None
-        if nv:
-            check(L.pmn_mt_emit_blocks(tsdf.data_ptr(), weight.data_ptr(), _ptr(rgb), _ptr(cweight), table.data_ptr(), blocks.data_ptr(),
-                                       B, dims_p, org_p, voxel, min_weight, vmask.data_ptr(), ntri.data_ptr(), vscan.data_ptr(),
-                                       tscan.data_ptr(), vertices.data_ptr(), _ptr(colors), _ptr(nrm), faces.data_ptr(), _stream(tsdf)),
-                  "pmn_mt_emit_blocks")
+    L, planes, lists, stream = _lib.lib(), (tsdf.data_ptr(), weight.data_ptr()), (table.data_ptr(), blocks.data_ptr(), B), _stream(tsdf)
+
+    def count(vmask, ntri):
+        check(L.pmn_mt_count_blocks(*planes, *lists, dims_p, min_weight, vmask.data_ptr(), ntri.data_ptr(), stream), "pmn_mt_count_blocks")
+
+    def emit(vmask, ntri, vscan, tscan, vertices, colors, nrm, faces):
+        check(L.pmn_mt_emit_blocks(*planes, _ptr(rgb), _ptr(cweight), *lists, dims_p, org_p, voxel, min_weight, vmask.data_ptr(),
+                                   ntri.data_ptr(), vscan.data_ptr(), tscan.data_ptr(), vertices.data_ptr(), _ptr(colors), _ptr(nrm),
+                                   faces.data_ptr(), stream), "pmn_mt_emit_blocks")
+
+    out = _mt_extract("mt_extract_blocks", tsdf, rgb is not None, normals, count, emit)
     del keep
-    return vertices, faces, colors, nrm
+    return out
 
 
 # ---- rendering ---------------------------------------------------------------------------------------------

@@ -18,45 +18,63 @@ MAX_BLOCKS = 2 ** 20  # mesh.py --max_blocks: as many pooled samples
 MAX_VIRTUAL_VOXELS = 2 ** 36  # mesh.py --volume sparse: the virtual lattice (its block table then stays below ops.SPARSE_MAX_TABLE)
 
 
-class TsdfVolume:
+class _Volume:
+    """What the two volumes share: where the lattice sits, and the batching of ``integrate``.  A subclass supplies ``_integrate_views``,
+    the op call of one launch."""
+
+    def _place(self, origin, voxel: float, trunc: float, device) -> None:
+        name = type(self).__name__
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise PmnError(f"{name}: device {self.device} is not a ROCm GPU (no CPU fallback)")
+        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
+        self.voxel, self.trunc = float(np.float32(voxel)), float(np.float32(trunc))
+        if not (np.isfinite(self.origin).all() and np.isfinite(self.voxel) and self.voxel > 0 and np.isfinite(self.trunc) and self.trunc > 0):
+            raise PmnError(f"{name}: origin must be finite, voxel and trunc positive and finite")
+
+    def _allocated(self, what) -> None:
+        """Raises where the planes do not exist yet."""
+
+    def integrate(self, maps: torch.Tensor, slots: Sequence[int], sizes: Sequence[Tuple[int, int]], cams, masks=None, images=None,
+                  batch: int = 8) -> None:
+        """Folds the views in, ``batch`` per launch, in the given order (see ops.tsdf_integrate for the arguments; any batch size
+        leaves the same bits).  For a SparseTsdfVolume the views should be those ``allocate`` saw: a surface outside the allocated
+        band is not integrated."""
+        self._allocated("integrate")
+        if not 1 <= int(batch) <= _lib.TSDF_MAX_VIEWS:
+            raise PmnError(f"{type(self).__name__}.integrate: batch must be 1 .. {_lib.TSDF_MAX_VIEWS}")
+        cams = np.asarray(cams, np.float32).reshape(len(slots), 21)
+        for a in range(0, len(slots), int(batch)):
+            b = min(a + int(batch), len(slots))
+            self._integrate_views(maps, slots[a:b], sizes[a:b], cams[a:b], None if masks is None else masks[a:b],
+                                  None if images is None or self.rgb is None else images[a:b])
+
+
+class TsdfVolume(_Volume):
     """nx x ny x nz samples, sample (i,j,k) at origin + (i,j,k) * voxel (world units); planes tsdf (1), weight (0) and, with
     ``color``, rgb and cweight (0), all float32 on ``device``."""
 
     def __init__(self, origin, voxel: float, dims: Sequence[int], trunc: float, device, color: bool = True) -> None:
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise PmnError(f"TsdfVolume: device {device} is not a ROCm GPU (no CPU fallback)")
+        self._place(origin, voxel, trunc, device)
         nx, ny, nz = (int(d) for d in dims)
         if min(nx, ny, nz) < 2 or nz > 65535 or nx * ny * nz > 2 ** 31 - 1:
             raise PmnError(f"TsdfVolume: dims {nx} x {ny} x {nz} must be >= 2 per axis, nz <= 65535, fewer than 2^31 samples")
-        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
-        self.voxel, self.trunc, self.dims, self.device = float(np.float32(voxel)), float(np.float32(trunc)), (nx, ny, nz), device
-        if not (np.isfinite(self.origin).all() and np.isfinite(self.voxel) and self.voxel > 0 and np.isfinite(self.trunc) and self.trunc > 0):
-            raise PmnError("TsdfVolume: origin must be finite, voxel and trunc positive and finite")
+        self.dims, device = (nx, ny, nz), self.device
         self.tsdf = torch.ones((nz, ny, nx), dtype=torch.float32, device=device)
         self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device)
         self.rgb = torch.zeros((3, nz, ny, nx), dtype=torch.float32, device=device) if color else None
         self.cweight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device) if color else None
 
-    def integrate(self, maps: torch.Tensor, slots: Sequence[int], sizes: Sequence[Tuple[int, int]], cams, masks=None, images=None,
-                  batch: int = 8) -> None:
-        """Folds the views in, ``batch`` per launch, in the given order (see ops.tsdf_integrate for the arguments; any batch size
-        leaves the same bits)."""
-        if not 1 <= int(batch) <= _lib.TSDF_MAX_VIEWS:
-            raise PmnError(f"TsdfVolume.integrate: batch must be 1 .. {_lib.TSDF_MAX_VIEWS}")
-        cams = np.asarray(cams, np.float32).reshape(len(slots), 21)
-        for a in range(0, len(slots), int(batch)):
-            b = min(a + int(batch), len(slots))
-            ops.tsdf_integrate(self.tsdf, self.weight, self.rgb, self.cweight, self.origin, self.voxel, self.trunc, maps, slots[a:b],
-                               sizes[a:b], cams[a:b], None if masks is None else masks[a:b],
-                               None if images is None or self.rgb is None else images[a:b])
+    def _integrate_views(self, maps, slots, sizes, cams, masks, images) -> None:
+        ops.tsdf_integrate(self.tsdf, self.weight, self.rgb, self.cweight, self.origin, self.voxel, self.trunc, maps, slots, sizes, cams,
+                           masks, images)
 
     def extract(self, min_weight: float = 1.0, normals: bool = True):
         """(vertices [Nv,3] float32, faces [Nt,3] int32, colors [Nv,3] uint8 | None, normals [Nv,3] float32 | None) on the device."""
         return ops.mt_extract(self.tsdf, self.weight, self.origin, self.voxel, min_weight, self.rgb, self.cweight, normals)
 
 
-class SparseTsdfVolume:
+class SparseTsdfVolume(_Volume):
     """The lattice of TsdfVolume (``dims`` = nx x ny x nz VIRTUAL samples) of which only the 8 x 8 x 8 blocks near some view's surface
     exist.  ``allocate`` builds, from the views that will be integrated, ``blocks`` (int32 [B]: the linear block
     index of every slot, ascending), ``table`` (int32 [nbz,nby,nbx]: slot or -1) and the pool planes tsdf (1), weight (0) [B,8,8,8] and,
@@ -65,17 +83,11 @@ class SparseTsdfVolume:
 
     def __init__(self, origin, voxel: float, dims: Sequence[int], trunc: float, device, color: bool = True,
                  max_blocks: int = MAX_BLOCKS) -> None:
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise PmnError(f"SparseTsdfVolume: device {device} is not a ROCm GPU (no CPU fallback)")
+        self._place(origin, voxel, trunc, device)
         self.dims = tuple(int(d) for d in dims)
         self.nblocks = ops.sparse_blocks(self.dims)  # (nbx, nby, nbz)
         if not 1 <= int(max_blocks) <= ops.SPARSE_MAX_BLOCKS:
             raise PmnError(f"SparseTsdfVolume: max_blocks must be 1 .. {ops.SPARSE_MAX_BLOCKS}")
-        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
-        self.voxel, self.trunc, self.device = float(np.float32(voxel)), float(np.float32(trunc)), device
-        if not (np.isfinite(self.origin).all() and np.isfinite(self.voxel) and self.voxel > 0 and np.isfinite(self.trunc) and self.trunc > 0):
-            raise PmnError("SparseTsdfVolume: origin must be finite, voxel and trunc positive and finite")
         self.color, self.max_blocks = bool(color), int(max_blocks)
         self.blocks = self.table = self.tsdf = self.weight = self.rgb = self.cweight = None
         self.marked = self.needed = 0  # blocks the views marked; blocks after the dilation (set even when allocate raises)
@@ -130,19 +142,9 @@ class SparseTsdfVolume:
         if self.blocks is None:
             raise PmnError(f"SparseTsdfVolume.{what}: call allocate() first")
 
-    def integrate(self, maps: torch.Tensor, slots: Sequence[int], sizes: Sequence[Tuple[int, int]], cams, masks=None, images=None,
-                  batch: int = 8) -> None:
-        """TsdfVolume.integrate on the allocated blocks (the views should be those ``allocate`` saw: a surface outside the allocated
-        band is not integrated)."""
-        self._allocated("integrate")
-        if not 1 <= int(batch) <= _lib.TSDF_MAX_VIEWS:
-            raise PmnError(f"SparseTsdfVolume.integrate: batch must be 1 .. {_lib.TSDF_MAX_VIEWS}")
-        cams = np.asarray(cams, np.float32).reshape(len(slots), 21)
-        for a in range(0, len(slots), int(batch)):
-            b = min(a + int(batch), len(slots))
-            ops.tsdf_integrate_blocks(self.tsdf, self.weight, self.rgb, self.cweight, self.blocks, self.dims, self.origin, self.voxel,
-                                      self.trunc, maps, slots[a:b], sizes[a:b], cams[a:b], None if masks is None else masks[a:b],
-                                      None if images is None or self.rgb is None else images[a:b])
+    def _integrate_views(self, maps, slots, sizes, cams, masks, images) -> None:
+        ops.tsdf_integrate_blocks(self.tsdf, self.weight, self.rgb, self.cweight, self.blocks, self.dims, self.origin, self.voxel,
+                                  self.trunc, maps, slots, sizes, cams, masks, images)
 
     def extract(self, min_weight: float = 1.0, normals: bool = True):
         """What TsdfVolume.extract returns, in pool order: the same triangles, vertex for vertex the same bits."""

@@ -44,14 +44,10 @@ def timed(fn, repeats):
     return float(np.median(ms)), float(min(ms)), float(max(ms)), out
 
 
-def sparse_grid(say, args, tsdf, dev, dims, origin, voxel, trunc, maps, sizes, cam21, masks, imgs):
+def time_integrate(say, args, vol, label, plane_bytes, share_of_peak, maps, sizes, cam21, masks, imgs):
+    """Times vol.integrate of all views per batch size of --views_per_launch, from cleared planes.  ``plane_bytes`` = the bytes of the
+    volume's planes (read and written once per launch); the maps, masks and images move once per launch set."""
     V = len(sizes)
-    slots = list(range(V))
-    vol = tsdf.SparseTsdfVolume(origin, voxel, dims, trunc, dev, color=True, max_blocks=2 ** 21)
-    med, lo, hi, B = timed(lambda: vol.allocate(maps, slots, sizes, cam21, masks), args.repeats)
-    nb = vol.nblocks[0] * vol.nblocks[1] * vol.nblocks[2]
-    say("  sparse allocate (mark %d views, dilate, list, table, pool): median %.2f ms (min %.2f, max %.2f); %d blocks marked, %d "
-        "allocated = %.3f %% of %d, pool %.3f GB with colour" % (V, med, lo, hi, vol.marked, B, 100.0 * B / nb, nb, 24 * 512 * B / 1e9))
     for b in (int(x) for x in args.views_per_launch.split(",")):
         def run():
             vol.tsdf.fill_(1)
@@ -60,7 +56,7 @@ def sparse_grid(say, args, tsdf, dev, dims, origin, voxel, trunc, maps, sizes, c
             vol.cweight.zero_()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            vol.integrate(maps, slots, sizes, cam21, masks, imgs, batch=b)
+            vol.integrate(maps, list(range(V)), sizes, cam21, masks, imgs, batch=b)
             e1.record()
             return e0, e1
         ms = []
@@ -70,9 +66,25 @@ def sparse_grid(say, args, tsdf, dev, dims, origin, voxel, trunc, maps, sizes, c
             if r:
                 ms.append(e0.elapsed_time(e1))
         launches = -(-V // b)
-        must = launches * 2 * 24 * 512 * B + V * sizes[0][0] * sizes[0][1] * (4 + 1 + 3)
-        say("  sparse integrate %2d views/launch (%2d launches): median %.2f ms (min %.2f, max %.2f, n=%d); must move %.1f GB -> %.0f GB/s"
-            % (b, launches, float(np.median(ms)), min(ms), max(ms), len(ms), must / 1e9, must / float(np.median(ms)) / 1e6))
+        must = launches * 2 * plane_bytes + V * sizes[0][0] * sizes[0][1] * (4 + 1 + 3)
+        med = float(np.median(ms))
+        line = "  %s %2d views/launch (%2d launches): median %.2f ms (min %.2f, max %.2f, n=%d); must move %.1f GB -> %.0f GB/s" % (
+            label, b, launches, med, min(ms), max(ms), len(ms), must / 1e9, must / med / 1e6)
+        if share_of_peak:
+            line += " = %.0f %% of the 6.3 TB/s achievable, %.0f %% of the 8.0 TB/s peak" % (
+                100 * must / med / 1e-3 / HBM_ACHIEVABLE, 100 * must / med / 1e-3 / HBM_PEAK)
+        say(line)
+
+
+def sparse_grid(say, args, tsdf, dev, dims, origin, voxel, trunc, maps, sizes, cam21, masks, imgs):
+    V = len(sizes)
+    slots = list(range(V))
+    vol = tsdf.SparseTsdfVolume(origin, voxel, dims, trunc, dev, color=True, max_blocks=2 ** 21)
+    med, lo, hi, B = timed(lambda: vol.allocate(maps, slots, sizes, cam21, masks), args.repeats)
+    nb = vol.nblocks[0] * vol.nblocks[1] * vol.nblocks[2]
+    say("  sparse allocate (mark %d views, dilate, list, table, pool): median %.2f ms (min %.2f, max %.2f); %d blocks marked, %d "
+        "allocated = %.3f %% of %d, pool %.3f GB with colour" % (V, med, lo, hi, vol.marked, B, 100.0 * B / nb, nb, 24 * 512 * B / 1e9))
+    time_integrate(say, args, vol, "sparse integrate", 24 * 512 * B, False, maps, sizes, cam21, masks, imgs)
     med, lo, hi, out = timed(lambda: vol.extract(1.0, normals=True), args.repeats)
     say("  sparse extract: %d vertices, %d faces; median %.2f ms (min %.2f, max %.2f)" % (out[0].shape[0], out[1].shape[0], med, lo, hi))
     del out, vol
@@ -126,30 +138,7 @@ def main(argv=None):
             say("  dense: the lattice does not fit a dense volume")
             continue
         vol = tsdf.TsdfVolume(origin, voxel, dims, trunc, dev, color=True)
-        for b in (int(x) for x in args.views_per_launch.split(",")):
-            def run():
-                vol.tsdf.fill_(1)
-                vol.weight.zero_()
-                vol.rgb.zero_()
-                vol.cweight.zero_()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                vol.integrate(maps, list(range(V)), [(H, W)] * V, cam21, masks, imgs, batch=b)
-                e1.record()
-                return e0, e1
-            ms = []
-            for r in range(args.repeats + 1):
-                e0, e1 = run()
-                torch.cuda.synchronize()
-                if r:
-                    ms.append(e0.elapsed_time(e1))
-            launches = -(-V // b)
-            must = launches * 2 * 24 * n + V * H * W * (4 + 1 + 3)
-            med = float(np.median(ms))
-            say("  integrate %2d views/launch (%2d launches): median %.2f ms (min %.2f, max %.2f, n=%d); must move %.1f GB -> %.0f GB/s "
-                "= %.0f %% of the 6.3 TB/s achievable, %.0f %% of the 8.0 TB/s peak" % (
-                    b, launches, med, min(ms), max(ms), len(ms), must / 1e9, must / med / 1e6, 100 * must / med / 1e-3 / HBM_ACHIEVABLE,
-                    100 * must / med / 1e-3 / HBM_PEAK))
+        time_integrate(say, args, vol, "integrate", 24 * n, True, maps, [(H, W)] * V, cam21, masks, imgs)
         med, lo, hi, out = timed(lambda: vol.extract(1.0, normals=True), args.repeats)
         nv, nt = out[0].shape[0], out[1].shape[0]
         del out
