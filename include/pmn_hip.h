@@ -365,8 +365,35 @@ int pmn_check_f16_domain(const float *x, long long n, int *flag, void *stream);
  * The plan holds the DEVICE addresses that were passed while recording: the caller keeps those buffers alive and in place for the
  * life of the plan and feeds new inputs by writing into them (or into the device address tables of pmn_warp_correlate_views /
  * pmn_stem_f16s_views) before each launch, on the same stream.  One recording per thread at a time; a plan is recorded once.
- * pmn_plan_count = number of recorded launches; pmn_plan_kernel_name(plan, i) = the i-th kernel's symbol name (diagnostics).
- * Like every entry point, none of these synchronises, allocates device memory or copies. */
+ * pmn_plan_count = number of recorded entries; pmn_plan_kernel_name(plan, i) = the i-th kernel's symbol name (diagnostics).
+ * Like every entry point, none of these synchronises, allocates device memory or copies.
+ *
+ * Added under ABI 25 (purely additive: tests of the existing suite pin the number).  ONE fork/join region per plan -- a stretch of the
+ * recording whose launches fall into two branches that do not depend on each other, so that a replay may run them side by side:
+ *
+ *   pmn_plan_fork(plan)            opens the region; launches are tagged main (0) until switched
+ *   pmn_plan_switch(plan, branch)  0 = main, 1 = side: the tag of the launches recorded from here on
+ *   pmn_plan_join(plan)            closes the region; everything recorded afterwards depends on both branches
+ *
+ * All three are valid only while the calling thread records that plan and return PMN_ERR_ARG for a join without a fork, a nested or
+ * second fork, a switch outside the region and a branch other than 0 / 1; pmn_plan_end with the region still open fails too (and
+ * the plan is then unusable).  Fork and join are recorded as marker entries: they count in pmn_plan_count, pmn_plan_kernel_name
+ * gives "<fork>" / "<join>" for them, and pmn_plan_entry_branch(plan, i) is the i-th entry's tag (markers: 0).
+ *
+ * pmn_plan_launch replays a plan with a region exactly as one without: every launch, in recorded order, on `stream` -- correct, no
+ * overlap.  pmn_plan_launch_part(plan, part, stream) enqueues ONE part, in recorded order, on `stream`: PMN_PLAN_PART_PRE the launches
+ * before the fork (all of them in a plan without a region), _SIDE / _MAIN the region's two branches, _POST those after the join.  The
+ * ordering BETWEEN streams is the caller's, because no entry point of this library creates a stream or waits for an event:
+ *
+ *   launch_part(PRE, s);  record e0 on s;  make `side` wait for e0;  launch_part(SIDE, side);  launch_part(MAIN, s);
+ *   record e1 on side;  make s wait for e1;  launch_part(POST, s)
+ *
+ * (patchmatchnet_amd/graph.py: PlannedForward._replay).  Two replays of one plan stay ordered on `s`: replay n+1's e0 is recorded
+ * behind replay n's wait for e1. */
+#define PMN_PLAN_PART_PRE 0
+#define PMN_PLAN_PART_SIDE 1
+#define PMN_PLAN_PART_MAIN 2
+#define PMN_PLAN_PART_POST 3
 int pmn_plan_create(void **plan_out);
 int pmn_plan_begin(void *plan);
 int pmn_plan_end(void *plan);
@@ -374,6 +401,11 @@ int pmn_plan_count(const void *plan);
 const char *pmn_plan_kernel_name(const void *plan, int index);
 int pmn_plan_launch(const void *plan, void *stream);
 int pmn_plan_destroy(void *plan);
+int pmn_plan_fork(void *plan);
+int pmn_plan_switch(void *plan, int branch);
+int pmn_plan_join(void *plan);
+int pmn_plan_entry_branch(const void *plan, int index);
+int pmn_plan_launch_part(const void *plan, int part, void *stream);
 
 /* ABI 23.  View selection of the COLMAP import (reference colmap_input.py:336-366): the full N x N float64 score matrix of every
  * image pair, score[i][j] = score[j][i] = sum over the observations of image min(i,j), in that image's order, of the points also

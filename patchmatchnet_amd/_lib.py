@@ -79,6 +79,11 @@ SIGNATURES = {
     "pmn_plan_kernel_name": [_hp, _i],
     "pmn_plan_launch": [_hp, _s],
     "pmn_plan_destroy": [_hp],
+    "pmn_plan_fork": [_hp],
+    "pmn_plan_switch": [_hp, _i],
+    "pmn_plan_join": [_hp],
+    "pmn_plan_entry_branch": [_hp, _i],
+    "pmn_plan_launch_part": [_hp, _i, _s],
     "pmn_view_scores": [_fp] * 6 + [_i, _i, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_double] * 3 + [_fp, _s],
     "pmn_depth_metrics": [_fp, _fp, _hp, _hp, _hp, _i, _hp, _i, _i, _i, _i, _fp, ctypes.c_longlong, _fp, _s],
     "pmn_nn_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, ctypes.c_double, _fp, _ip,
@@ -104,6 +109,8 @@ SIGNATURES = {
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)
+PLAN_PART_PRE, PLAN_PART_SIDE, PLAN_PART_MAIN, PLAN_PART_POST = 0, 1, 2, 3  # pmn_plan_launch_part (PMN_PLAN_PART_*)
+
 METRICS_MAX_STAGES = 4
 METRICS_MAX_ITERS = 5
 METRICS_MAX_THRESHOLDS = 8

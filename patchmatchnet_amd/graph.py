@@ -294,7 +294,14 @@ class _LibraryLaunchesOnly(torch.utils._python_dispatch.TorchDispatchMode):
             raise PmnError(f"PlannedForward: the forward dispatched {func} while it was being recorded -- an operator outside "
                            "libpmn_hip.so cannot be part of a launch plan (it would run once, on uninitialised data, and never "
                            "again); this input signature has to run eagerly or through a path that only calls the library")
-        return func(*args, **(kwargs or {}))
+        out = func(*args, **(kwargs or {}))
+        # (inside the plan's fork/join region every allocation is held until the join: ops.PlanRegion)
+        from . import ops
+        ops._hold(out, fresh=not getattr(func, "is_view", False) and str(func).startswith("aten.") and
+                  (str(func) + ".").startswith(self._FRESH))
+        return out
+
+    _FRESH = ("aten.empty.", "aten.empty_strided.", "aten.empty_like.", "aten.new_empty.", "aten.new_empty_strided.")
 
 
 class PlannedForward(GraphedForward):
@@ -312,10 +319,17 @@ class PlannedForward(GraphedForward):
 
     What a plan needs from the forward: every launch comes from libpmn_hip.so (the recording pass raises on any other ATen operator,
     see _LibraryLaunchesOnly) and every buffer it touches stays in place: the pass allocates from a private torch memory pool that
-    lives as long as the plan, exactly like a graph's private pool."""
+    lives as long as the plan, exactly like a graph's private pool.
 
-    def __init__(self, model, max_graphs: int = 8, inputs_in_place: bool = False) -> None:
+    The forward marks one fork/join region (net.PatchmatchNet.forward: the FPN's 1/4 and 1/2 levels and the offset heads and
+    FeatureWeightNet of stages 2 and 1 depend on nothing stage 3 computes).  A replay puts that side branch on a stream of the plan's
+    own, between an event recorded on the caller's stream at the fork and one the caller's stream waits for at the join
+    (pmn_plan_launch_part; the library itself creates no stream and waits for no event): HBM- and MFMA-bound work beside stage 3's
+    gather- and VALU-bound chain, in every replay.  ``fork=False`` replays the same plan on the caller's stream alone."""
+
+    def __init__(self, model, max_graphs: int = 8, inputs_in_place: bool = False, fork: bool = True) -> None:
         super().__init__(model, max_graphs=max_graphs, inputs_in_place=inputs_in_place)
+        self.fork = fork
 
     def _record(self, run, dev):
         import ctypes
@@ -327,14 +341,18 @@ class PlannedForward(GraphedForward):
             plan = ctypes.c_void_p()
             _lib.check(L.pmn_plan_create(ctypes.byref(plan)), "pmn_plan_create")
             handle = _Plan(plan, pool)
+            from . import ops
             with torch.cuda.use_mem_pool(pool, device=dev):
                 _lib.check(L.pmn_plan_begin(plan), "pmn_plan_begin")
+                region = ops.begin_plan_recording(plan)
                 try:
                     with _LibraryLaunchesOnly():
                         depth, confidence, _ = run()
                 finally:
+                    ops.end_plan_recording()
                     rc = L.pmn_plan_end(plan)
                 _lib.check(rc, "pmn_plan_end")
+            handle.forked, handle.held_bytes = region.forked, region.held_bytes
         handle.count = L.pmn_plan_count(plan)
         if handle.count <= 0:
             raise PmnError("PlannedForward: the recording pass recorded no launch")
@@ -344,8 +362,23 @@ class PlannedForward(GraphedForward):
 
     def _replay(self, handle, dev) -> None:
         from . import _lib
+        L = _lib.lib()
         with torch.cuda.device(dev):  # (plain launches go to the CURRENT device's context: a rank whose device is not the process default)
-            _lib.check(_lib.lib().pmn_plan_launch(handle.plan, torch.cuda.current_stream(dev).cuda_stream), "pmn_plan_launch")
+            cur = torch.cuda.current_stream(dev)
+            if not (handle.forked and self.fork):
+                _lib.check(L.pmn_plan_launch(handle.plan, cur.cuda_stream), "pmn_plan_launch")
+                return
+            if handle.side is None:  # the plan's own stream and events, on its device (timing off: they only order)
+                handle.side, handle.at_fork, handle.at_join = torch.cuda.Stream(dev), torch.cuda.Event(), torch.cuda.Event()
+            side = handle.side
+            _lib.check(L.pmn_plan_launch_part(handle.plan, _lib.PLAN_PART_PRE, cur.cuda_stream), "pmn_plan_launch_part")
+            handle.at_fork.record(cur)
+            side.wait_event(handle.at_fork)
+            _lib.check(L.pmn_plan_launch_part(handle.plan, _lib.PLAN_PART_SIDE, side.cuda_stream), "pmn_plan_launch_part")
+            _lib.check(L.pmn_plan_launch_part(handle.plan, _lib.PLAN_PART_MAIN, cur.cuda_stream), "pmn_plan_launch_part")
+            handle.at_join.record(side)
+            cur.wait_event(handle.at_join)  # (replay n+1's fork event is recorded behind this wait: replays of one plan stay ordered)
+            _lib.check(L.pmn_plan_launch_part(handle.plan, _lib.PLAN_PART_POST, cur.cuda_stream), "pmn_plan_launch_part")
 
 
 class PlannedValidationForward(PlannedForward):
@@ -399,11 +432,19 @@ class _Plan:
 
     def __init__(self, plan, pool) -> None:
         self.plan, self.pool, self.count = plan, pool, 0
+        self.forked, self.held_bytes = False, 0  # a fork/join region was recorded; bytes its allocations held until the join
+        self.side = self.at_fork = self.at_join = None  # made by the first forked replay (PlannedForward._replay)
 
     def kernel_names(self) -> List[str]:
         from . import _lib
         L = _lib.lib()
         return [(L.pmn_plan_kernel_name(self.plan, i) or b"?").decode() for i in range(self.count)]
+
+    def entry_branches(self) -> List[int]:
+        """Per entry 0 (main) or 1 (side); the "<fork>" / "<join>" markers of kernel_names() are 0."""
+        from . import _lib
+        L = _lib.lib()
+        return [L.pmn_plan_entry_branch(self.plan, i) for i in range(self.count)]
 
     def __del__(self):
         try:

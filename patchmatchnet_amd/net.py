@@ -112,11 +112,15 @@ class FeatureNet(nn.Module):
             self._pack, self._pack_key = pk, key
         return self._pack
 
-    def forward_hip(self, x, image_table: Optional["ops.SourceTable"] = None) -> Dict[int, torch.Tensor]:
+    def forward_hip(self, x, image_table: Optional["ops.SourceTable"] = None, pending: Optional[dict] = None
+                    ) -> Dict[int, torch.Tensor]:
         """x [N,3,H,W], or a list of same-size [B,3,H,W] images (stacked view-major without a torch.cat copy: the first
         layer writes each image's output into its slice) -> {3: [N,H/8,W/8,64], 2: [N,H/4,W/4,32], 1: [N,H/2,W/2,16]}
         CHANNELS-LAST (inference only).  ``image_table`` (ops.SourceTable of shape (views, B, 3, H, W)): the images are read through
-        a device table of addresses instead of ``x`` (one launch; graph.GraphedForward(inputs_in_place=True))."""
+        a device table of addresses instead of ``x`` (one launch; graph.GraphedForward(inputs_in_place=True)).
+        ``pending`` (an empty dict): stop after the 1/8 level and return {3: ...} alone; the dict receives what ``finish_hip`` needs to
+        run the 1/4 and 1/2 levels later (PatchmatchNet.forward: beside stage 3, which reads the 1/8 level only).  Left empty where
+        the head is not folded (fold_fpn = False): then all three levels are returned as usual."""
         pk = self._packed()
         imgs = list(x) if isinstance(x, (list, tuple)) else [x]
         B, _, H, W = imgs[0].shape
@@ -159,15 +163,23 @@ class FeatureNet(nn.Module):
                 f3, u8 = ops.fpn_level(eighth, None, *pk["fpn8"], ca=64)
             else:  # 64 -> 112 channels: a GEMM, on the fp32 matrix cores (pmn_conv2d_mfma's 1x1 form)
                 f3, u8 = ops.pointwise_split_mfma(eighth, *pk["fpn8_mfma"], cout=112, ca=64)
-            f2, u4 = ops.fpn_level(quarter, u8, *pk["fpn4"], ca=32)
-            f1, _ = ops.fpn_level(half, u4, *pk["fpn2"], ca=16)
-            return {3: f3, 2: f2, 1: f1}
+            if pending is not None:
+                pending.update(half=half, quarter=quarter, u8=u8)
+                return {3: f3}
+            return {3: f3, **self.finish_hip(dict(half=half, quarter=quarter, u8=u8))}
         out = {3: ops.conv2d(eighth, *pk["output1"], 64, 1)}
         top = ops.conv2d(quarter, *pk["inner1"], 64, 1, up=eighth)       # upsample(conv10) + inner1(conv7)
         out[2] = ops.conv2d(top, *pk["output2"], 32, 1)
         # output3(upsample(intra) + inner2(conv4)) in one kernel: the 64-channel half-resolution map stays in registers
         out[1] = ops.fpn_tail(half, top, pk["inner2"][0], pk["inner2"][1], pk["output3"][0])
         return out
+
+    def finish_hip(self, pending: dict) -> Dict[int, torch.Tensor]:
+        """The folded head's 1/4 and 1/2 levels from what ``forward_hip(pending=...)`` left: {2: [N,H/4,W/4,32], 1: [N,H/2,W/2,16]}."""
+        pk = self._packed()
+        f2, u4 = ops.fpn_level(pending["quarter"], pending["u8"], *pk["fpn4"], ca=32)
+        f1, _ = ops.fpn_level(pending["half"], u4, *pk["fpn2"], ca=16)
+        return {2: f2, 1: f1}
 
     def forward(self, x: torch.Tensor) -> Dict[int, torch.Tensor]:
         half = self.conv4(self.conv3(self.conv2(self.conv1(self.conv0(x)))))
@@ -332,15 +344,18 @@ class PatchmatchNet(nn.Module):
         return model
 
     def extract_features(self, images: List[torch.Tensor], stacked: Optional[dict] = None,
-                         image_table: Optional["ops.SourceTable"] = None) -> List[Dict[int, torch.Tensor]]:
+                         image_table: Optional["ops.SourceTable"] = None, pending: Optional[dict] = None
+                         ) -> List[Dict[int, torch.Tensor]]:
         """Per-view feature pyramids.  ``stacked`` (a dict) additionally receives {stage: [V*B,C,h,w]} when all views
-        went through FeatureNet as one batch (view-major), so the caller can change layout in one pass."""
+        went through FeatureNet as one batch (view-major), so the caller can change layout in one pass.  ``pending`` (an empty dict,
+        FeatureNet.forward_hip): where the HIP FeatureNet can stop after the 1/8 level it does, the pyramids hold stage 3 only and
+        ``finish_features`` adds the other two."""
         same = all(im.shape == images[0].shape for im in images)
         B = images[0].shape[0]
         if image_table is not None and not (self.hip_feature_net and same and images[0].is_cuda and self.feature.f16_split):
             raise PmnError("image_table needs the HIP FeatureNet (f16_split) and same-size images on a ROCm device")
         if self.hip_feature_net and same and images[0].is_cuda:
-            f = self.feature.forward_hip(images, image_table=image_table)
+            f = self.feature.forward_hip(images, image_table=image_table, pending=pending)
             if stacked is not None:
                 stacked.update({("nhwc", s): t for s, t in f.items()})
             # per-view NCHW-shaped views over the channels-last storage (no copy)
@@ -354,6 +369,14 @@ class PatchmatchNet(nn.Module):
                 stacked.update(f)
             return [{s: t[i * B:(i + 1) * B] for s, t in f.items()} for i in range(len(images))]
         return [self.feature(im) for im in images]
+
+    def finish_features(self, features: List[Dict[int, torch.Tensor]], stacked: dict, pending: dict) -> None:
+        """The 1/4 and 1/2 levels ``extract_features(pending=...)`` left out, added to ``features`` and ``stacked`` in place."""
+        f = self.feature.finish_hip(pending)
+        B = f[2].shape[0] // len(features)
+        stacked.update({("nhwc", s): t for s, t in f.items()})
+        for i, view in enumerate(features):
+            view.update({s: t[i * B:(i + 1) * B].permute(0, 3, 1, 2) for s, t in f.items()})
 
     def forward(self, images: List[torch.Tensor], intrinsics: torch.Tensor, extrinsics: torch.Tensor,
                 depth_min: torch.Tensor, depth_max: torch.Tensor, noise: Optional[torch.Tensor] = None,
@@ -382,8 +405,9 @@ class PatchmatchNet(nn.Module):
         _, _, ref_height, ref_width = ref_image.size()
 
         stacked: Dict[int, torch.Tensor] = {}
+        pending: dict = {}  # the FPN's 1/4 and 1/2 levels, where FeatureNet could stop after the 1/8 level stage 3 reads
         if features is None:
-            features = self.extract_features(images, stacked, image_table)
+            features = self.extract_features(images, stacked, image_table, pending)
         elif features_nhwc is not None:
             stacked.update({("nhwc", st): t for st, t in features_nhwc.items()})
         ref_feature, src_features = features[0], features[1:]
@@ -401,7 +425,39 @@ class PatchmatchNet(nn.Module):
         depth_shift, vw_shift = 0, 0
         # relative projections of all stages in one launch (replaces ~40 tiny ATen kernels per forward)
         rel_all = ops.stage_projections(intrinsics, extrinsics, self.stages - 1, scale) if self.hip_projections else None
+
+
+        def stage_maps(stage):
+            """(ref_nhwc, src_nhwc) of a stage where the caller or FeatureNet already has channels-last maps, else (None, None)."""
+            if source_tables is not None:
+                return ref_nhwc_maps[stage], source_tables[stage]
+            if ("nhwc", stage) in stacked:  # HIP FeatureNet: already channels-last
+                allv = stacked[("nhwc", stage)]
+            elif stage in stacked:  # one layout pass for all views of the stage
+                allv = stacked[("nhwc", stage)] = ops.nchw_to_nhwc(stacked[stage].contiguous())
+            else:
+                return None, None
+            return allv[:batch], allv[batch:].view(len(features) - 1, batch, *allv.shape[1:])
+
+        # What stages 2 and 1 compute from the reference features alone -- and the FPN levels that make those features -- depends on
+        # nothing stage 3 computes: it is issued first, as the SIDE branch of a fork, and stage 3 as the main branch.  While a launch
+        # plan is recorded (graph.PlannedForward) the marks tag its entries and a replay runs the side branch on a stream of its own,
+        # HBM- and MFMA-bound work beside stage 3's gathers; anywhere else they do nothing and this is the same launches in another
+        # order on one stream, with the same bits.
+        precomputed: Dict[int, dict] = {}
+        ops.plan_fork()
+        ops.plan_switch(1)
+        if pending:
+            self.finish_features(features, stacked, pending)
+        for stage in range(self.stages - 2, 0, -1):
+            precomputed[stage] = getattr(self, f"patchmatch_{stage}").prepare(features[0][stage], stage_maps(stage)[0])
+        ops.plan_switch(0)
         for stage in range(self.stages - 1, 0, -1):
+            if stage == self.stages - 2:
+                # both branches are done before stage 2's first launch.  (``pending`` holds FeatureNet's conv4 / conv7 maps up to
+                # here: a block freed inside the fork could be handed to the other branch, which a replay runs concurrently)
+                ops.plan_join()
+                pending.clear()
             # stage projection matrices (reference models/net.py:225-231): the reference's op sequence is only run when
             # hip_projections is off; otherwise PatchMatch receives rel_proj and never reads ref_proj / src_projs
             if rel_all is None:
@@ -417,24 +473,13 @@ class PatchmatchNet(nn.Module):
 
             dbg = [] if debug is not None else None
             pm: PatchMatch = getattr(self, f"patchmatch_{stage}")
-            ref_nhwc = src_nhwc = None
-            if ("nhwc", stage) in stacked:  # HIP FeatureNet: already channels-last
-                allv = stacked[("nhwc", stage)]
-            elif stage in stacked:  # one layout pass for all views of the stage
-                allv = ops.nchw_to_nhwc(stacked[stage].contiguous())
-            else:
-                allv = None
-            if source_tables is not None:
-                ref_nhwc, src_nhwc = ref_nhwc_maps[stage], source_tables[stage]
-            elif allv is not None:
-                ref_nhwc = allv[:batch]
-                src_nhwc = allv[batch:].view(len(src_features), batch, *allv.shape[1:])
+            ref_nhwc, src_nhwc = stage_maps(stage)
             depths, score, view_weights = pm(
                 ref_feature=ref_feature[stage], src_features=[f[stage] for f in src_features], ref_proj=ref_proj,
                 src_projs=list(src_proj), depth_min=depth_min, depth_max=depth_max, depth=depth,
                 view_weights=view_weights, depth_shift=depth_shift, vw_shift=vw_shift,
                 noise=noise if stage == self.stages - 1 else None, debug=dbg, ref_nhwc=ref_nhwc, src_nhwc=src_nhwc,
-                rel_proj=None if rel_all is None else rel_all[self.stages - 1 - stage])
+                rel_proj=None if rel_all is None else rel_all[self.stages - 1 - stage], precomputed=precomputed.get(stage))
             if debug is not None:
                 debug[stage] = dbg
             depth_patchmatch[stage] = depths

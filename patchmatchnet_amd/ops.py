@@ -6,6 +6,7 @@ float32, contiguous tensors on a ROCm device and raises otherwise -- there is no
 from __future__ import annotations
 
 import ctypes
+import threading
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -134,6 +135,110 @@ def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+# ---- the fork / join region of a launch plan that is being recorded (include/pmn_hip.h: pmn_plan_fork; graph.PlannedForward) -------------
+# PatchmatchNet.forward marks the stretch whose launches fall into two independent branches with plan_fork / plan_switch / plan_join.
+# Outside a plan recording the three are no-ops: eager launches and HIP-graph capture stay on one stream, in the same order.  While
+# a plan is recorded they tag its entries, and -- because the recording pass runs the branches one after the other while a replay
+# runs them side by side -- guard the one thing sequential recording hides: the caching allocator handing a block that one branch
+# freed to the other branch (DESIGN_LESSONS.md).  Every tensor allocated inside the region is held until the join, so no block is
+# reused inside it, and what each branch's calls read and write is collected and checked for overlap at the join (host only).
+_RECORDING = threading.local()
+
+
+class PlanRegion:
+    """Per-recording state: ``plan`` (the pmn_plan handle), the open region's branch, the tensors held until the join, and per branch
+    the (address, bytes) ranges its calls read / wrote / allocated."""
+
+    def __init__(self, plan) -> None:
+        self.plan, self.open, self.branch, self.forked = plan, False, 0, False
+        self.held: List[torch.Tensor] = []
+        self.reads = {0: [], 1: []}
+        self.writes = {0: [], 1: []}
+        self.allocated = {0: [], 1: []}
+        self.held_bytes = 0
+
+
+def begin_plan_recording(plan) -> PlanRegion:
+    """graph.PlannedForward: this thread records ``plan`` from now on (until end_plan_recording)."""
+    _RECORDING.region = PlanRegion(plan)
+    return _RECORDING.region
+
+
+def end_plan_recording() -> None:
+    _RECORDING.region = None
+
+
+def _region() -> Optional[PlanRegion]:
+    return getattr(_RECORDING, "region", None)
+
+
+def plan_fork() -> None:
+    r = _region()
+    if r is not None:
+        check(_lib.lib().pmn_plan_fork(r.plan), "pmn_plan_fork")
+        r.open, r.branch, r.forked = True, 0, True
+
+
+def plan_switch(branch: int) -> None:
+    """0 = main, 1 = side: the branch of the launches that follow."""
+    r = _region()
+    if r is not None:
+        check(_lib.lib().pmn_plan_switch(r.plan, int(branch)), "pmn_plan_switch")
+        r.branch = int(branch)
+
+
+def plan_join() -> None:
+    r = _region()
+    if r is not None:
+        for b in (0, 1):  # every block the region allocated is the output of a call that declared it
+            for rng in r.allocated[b]:
+                if not any(_ranges_overlap(rng, w) for w in r.writes[b]):
+                    raise PmnError("plan_join: a tensor allocated between fork and join is not among the outputs its branch's calls "
+                                   "declared (ops._note): the overlap check would not see it")
+        check_branch_overlap(r.reads[0], r.writes[0], r.reads[1], r.writes[1])
+        check(_lib.lib().pmn_plan_join(r.plan), "pmn_plan_join")
+        r.open, r.branch = False, 0
+        r.held.clear()
+
+
+def _range(t: torch.Tensor) -> Tuple[int, int]:
+    return (t.data_ptr(), t.numel() * t.element_size())  # (every tensor the kernels see is dense, possibly permuted)
+
+
+def _ranges_overlap(a: Tuple[int, int], b: Tuple[int, int]) -> bool:
+    return a[1] > 0 and b[1] > 0 and a[0] < b[0] + b[1] and b[0] < a[0] + a[1]
+
+
+def check_branch_overlap(main_reads, main_writes, side_reads, side_writes) -> None:
+    """(address, bytes) ranges of what the two branches of a fork read and write: raises PmnError when one branch writes what the
+    other reads or writes (on replay the branches run concurrently).  Host arithmetic only."""
+    for who, writes, others in (("main", main_writes, list(side_reads) + list(side_writes)),
+                                ("side", side_writes, list(main_reads) + list(main_writes))):
+        for w in writes:
+            for o in others:
+                if _ranges_overlap(w, o):
+                    raise PmnError(f"plan fork: the {who} branch writes [{w[0]:#x}, +{w[1]}) which the other branch touches at "
+                                   f"[{o[0]:#x}, +{o[1]}): the branches run concurrently on replay and must not share a buffer")
+
+
+def _hold(t, fresh: bool) -> None:
+    """graph._LibraryLaunchesOnly: a tensor the recording pass just allocated (``fresh``) or derived."""
+    r = _region()
+    if r is not None and r.open and isinstance(t, torch.Tensor) and t.is_cuda:
+        r.held.append(t)
+        if fresh and t.numel():
+            r.allocated[r.branch].append(_range(t))
+            r.held_bytes += t.numel() * t.element_size()
+
+
+def _note(reads, writes) -> None:
+    """What the call being issued reads and writes (tensors; None entries are skipped), for the open region's overlap check."""
+    r = _region()
+    if r is not None and r.open:
+        r.reads[r.branch] += [_range(t) for t in reads if t is not None]
+        r.writes[r.branch] += [_range(t) for t in writes if t is not None]
+
+
 def _host_f32(a: np.ndarray, n: int, name: str):
     a = np.ascontiguousarray(a, np.float32)
     if a.size != n:
@@ -164,6 +269,7 @@ def nchw_to_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
         _dev(out, "out")
         if tuple(out.shape) != (B, h, w, C):
             raise PmnError("nchw_to_nhwc: bad output shape")
+    _note((x,), (out,))
     with torch.cuda.device(x.device):
         check(_lib.lib().pmn_nchw_to_nhwc(x.data_ptr(), out.data_ptr(), B, C, h, w, _stream(x)), "pmn_nchw_to_nhwc")
     return out
@@ -242,6 +348,7 @@ def feature_weight(ref_nhwc: torch.Tensor, eval_offsets: torch.Tensor, table: np
     tab, tab_p = _host_i32(table, 2 * K, "table")
     _mlp_dev(mlp, "mlp")
     out = torch.empty((B, K, h, w), dtype=torch.float32, device=ref_nhwc.device)
+    _note((ref_nhwc, eval_offsets, mlp), (out,))
     with torch.cuda.device(ref_nhwc.device):
         check(_lib.lib().pmn_feature_weight(ref_nhwc.data_ptr(), eval_offsets.data_ptr(), tab_p, mlp.data_ptr(), B, C, G,
                                             K, h, w,
@@ -285,6 +392,7 @@ def init_hypotheses(noise: Optional[torch.Tensor], depth: Optional[torch.Tensor]
     D = D0 + K
     ds = torch.empty((B, D, h, w), dtype=torch.float32, device=dev)
     xn = torch.empty((B, h, w, D), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+    _note((noise, depth if noise is None else None, depth_min, depth_max, propa_offsets), (ds, xn))
     with torch.cuda.device(dev):
         check(_lib.lib().pmn_init_hypotheses(_ptr(noise), _ptr(depth) if noise is None else None, depth_shift,
                                              depth_min.data_ptr(), depth_max.data_ptr(), num_sample,
@@ -355,6 +463,8 @@ def warp_correlate(ref_nhwc: torch.Tensor, src_nhwc, rel_proj: torch.Tensor, dep
             argmax = torch.empty((B, N, h, w), dtype=torch.int32, device=dev)
     cost = torch.empty((B, h, w, D), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)  # hypothesis-last storage
     sim = torch.empty((B, G, D, h, w), dtype=torch.float32, device=dev) if want_similarity else None
+    _note((ref_nhwc, src_nhwc if table is None else table.table, rel_proj, depth_sample, view_weights, similarity_mlp, pixelwise_mlp),
+          (cost, vw_out, argmax, sim))
     with torch.cuda.device(dev):
         if _TIMING is not None and _TIMING_ON:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -386,6 +496,7 @@ def aggregate_regress(cost: torch.Tensor, depth_sample: torch.Tensor, xnorm: tor
     tab, tab_p = _host_i32(table, 2 * K, "table")
     score = torch.empty((B, D, h, w), dtype=torch.float32, device=cost.device)
     depth = torch.empty((B, h, w), dtype=torch.float32, device=cost.device)
+    _note((cost, depth_sample, xnorm, feature_weight_, eval_offsets), (score, depth))
     with torch.cuda.device(cost.device):
         check(_lib.lib().pmn_aggregate_regress(cost.data_ptr(), depth_sample.data_ptr(), xnorm.data_ptr(),
                                                feature_weight_.data_ptr(), eval_offsets.data_ptr(), tab_p, K,
@@ -488,6 +599,7 @@ def conv2d(x: torch.Tensor, weights: torch.Tensor, shift: torch.Tensor, cout: in
         if tuple(up.shape) != (N, Ho // 2, Wo // 2, cout) or Ho % 2 or Wo % 2:
             raise PmnError("conv2d: `up` must be [N,Ho/2,Wo/2,cout]")
         up_h, up_w = up.shape[1], up.shape[2]
+    _note((x, weights, shift, up), (out,))
     with torch.cuda.device(x.device):
         check(_lib.lib().pmn_conv2d(x.data_ptr(), weights.data_ptr(), shift.data_ptr(), _ptr(up), out.data_ptr(), N, H, W,
                                     cin, cout, K, stride, pad, dil, 1 if relu else 0, 1 if in_nchw else 0,
@@ -673,6 +785,7 @@ def offset_heads_f16s(x: torch.Tensor, weights: torch.Tensor, shift: torch.Tenso
         raise PmnError("offset_heads_f16s: weights are not in pack_offset_heads_f16s layout for this input")
     out_a = torch.empty((N, ca, H, W), dtype=torch.float32, device=x.device)
     out_b = torch.empty((N, cout - ca, H, W), dtype=torch.float32, device=x.device) if ca < cout else None
+    _note((x, weights, shift), (out_a, out_b))
     with torch.cuda.device(x.device):
         check(_lib.lib().pmn_offset_heads_f16s(x.data_ptr(), weights.data_ptr(), shift.data_ptr(), out_a.data_ptr(), _ptr(out_b), N,
                                                H, W, cin, cout, ca, dil, _stream(x)), "pmn_offset_heads_f16s")
@@ -695,6 +808,7 @@ def fpn_level(x: torch.Tensor, u: Optional[torch.Tensor], w: torch.Tensor, b: to
             raise PmnError("fpn_level: `u` must be [N,H/2,W/2,cout]")
     out_a = torch.empty((N, H, W, ca), dtype=torch.float32, device=x.device)
     out_b = torch.empty((N, H, W, cout - ca), dtype=torch.float32, device=x.device) if ca < cout else None
+    _note((x, u, w, b), (out_a, out_b))
     with torch.cuda.device(x.device):
         check(_lib.lib().pmn_fpn_level(x.data_ptr(), _ptr(u), w.data_ptr(), b.data_ptr(), out_a.data_ptr(), _ptr(out_b),
                                        N, H, W, cin, cout, ca, _stream(x)), "pmn_fpn_level")

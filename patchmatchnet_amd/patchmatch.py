@@ -277,27 +277,12 @@ class PatchMatch(nn.Module):
             self._heads, self._heads_key = pk, key
         return self._heads
 
-    def forward(self, ref_feature: torch.Tensor, src_features: List[torch.Tensor], ref_proj: torch.Tensor,
-                src_projs: List[torch.Tensor], depth_min: torch.Tensor, depth_max: torch.Tensor, depth: torch.Tensor,
-                view_weights: torch.Tensor, depth_shift: int = 0, vw_shift: int = 0, noise: Optional[torch.Tensor] = None,
-                debug: Optional[list] = None, ref_nhwc: Optional[torch.Tensor] = None,
-                src_nhwc: Optional[torch.Tensor] = None, rel_proj: Optional[torch.Tensor] = None
-                ) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
-        """Reference arguments, plus optional extras that default to reference behaviour:
-        ``depth_shift`` / ``vw_shift`` = 1 read ``depth`` / ``view_weights`` given at half resolution through the
-        nearest x2 up-sampling (skips materialising F.interpolate; the ``view_weights`` RETURNED are then the tensor that was
-        passed in, still at its coarser resolution -- the reference returns them up-sampled); ``noise`` pins the stage-3 random draw;
-        ``debug`` (a list) receives one dict of intermediates per iteration; ``ref_nhwc`` [B,h,w,C] / ``src_nhwc``
-        [N,B,h,w,C] hand over channels-last copies the caller already made (one layout pass for all views); ``rel_proj``
-        [B,N,4,4] hands over src_proj @ inverse(ref_proj) when the caller already has it (then ref_proj / src_projs are
-        not read)."""
-        if len(src_features) != len(src_projs):
-            raise AssertionError("Patchmatch Evaluation: Different number of images and projection matrices")
+    def prepare(self, ref_feature: torch.Tensor, ref_nhwc: Optional[torch.Tensor] = None) -> dict:
+        """The part of a stage that depends on the reference feature map alone: both offset heads and FeatureWeightNet ->
+        {ref_nhwc, propa_offsets, eval_offsets, feature_weight}, what ``forward`` takes as ``precomputed``.  PatchmatchNet.forward
+        issues it for stages 2 and 1 before stage 3 runs (the side branch of its launch plan's fork)."""
         if not ref_feature.is_cuda:
             raise PmnError("patchmatchnet_amd.PatchMatch runs on a ROCm GPU only (no CPU fallback)")
-        device = ref_feature.device
-        batch, _, height, width = ref_feature.size()
-
         propagate_any = self.propagate_neighbors > 0 and not (self.stage == 1 and self.patchmatch_iteration == 1)
         if ref_nhwc is None:
             ref_nhwc = ops.nchw_to_nhwc(ref_feature.detach())
@@ -320,6 +305,35 @@ class PatchMatch(nn.Module):
             ref_feature = ref_feature.contiguous()
             propa_offsets = self.propa_conv(ref_feature).contiguous() if propagate_any else None
             eval_offsets = self.eval_conv(ref_feature).contiguous()
+        feature_weight = self.feature_weight_net(ref_nhwc, eval_offsets, self._etable)
+        return dict(ref_nhwc=ref_nhwc, propa_offsets=propa_offsets, eval_offsets=eval_offsets, feature_weight=feature_weight)
+
+    def forward(self, ref_feature: torch.Tensor, src_features: List[torch.Tensor], ref_proj: torch.Tensor,
+                src_projs: List[torch.Tensor], depth_min: torch.Tensor, depth_max: torch.Tensor, depth: torch.Tensor,
+                view_weights: torch.Tensor, depth_shift: int = 0, vw_shift: int = 0, noise: Optional[torch.Tensor] = None,
+                debug: Optional[list] = None, ref_nhwc: Optional[torch.Tensor] = None,
+                src_nhwc: Optional[torch.Tensor] = None, rel_proj: Optional[torch.Tensor] = None,
+                precomputed: Optional[dict] = None) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
+        """Reference arguments, plus optional extras that default to reference behaviour:
+        ``depth_shift`` / ``vw_shift`` = 1 read ``depth`` / ``view_weights`` given at half resolution through the
+        nearest x2 up-sampling (skips materialising F.interpolate; the ``view_weights`` RETURNED are then the tensor that was
+        passed in, still at its coarser resolution -- the reference returns them up-sampled); ``noise`` pins the stage-3 random draw;
+        ``debug`` (a list) receives one dict of intermediates per iteration; ``ref_nhwc`` [B,h,w,C] / ``src_nhwc``
+        [N,B,h,w,C] hand over channels-last copies the caller already made (one layout pass for all views); ``rel_proj``
+        [B,N,4,4] hands over src_proj @ inverse(ref_proj) when the caller already has it (then ref_proj / src_projs are
+        not read); ``precomputed`` = what ``prepare`` returned for this stage's reference map (the offset heads and FeatureWeightNet
+        are then not run again)."""
+        if len(src_features) != len(src_projs):
+            raise AssertionError("Patchmatch Evaluation: Different number of images and projection matrices")
+        if not ref_feature.is_cuda:
+            raise PmnError("patchmatchnet_amd.PatchMatch runs on a ROCm GPU only (no CPU fallback)")
+        device = ref_feature.device
+        batch, _, height, width = ref_feature.size()
+
+        if precomputed is None:
+            precomputed = self.prepare(ref_feature, ref_nhwc)
+        ref_nhwc, propa_offsets = precomputed["ref_nhwc"], precomputed["propa_offsets"]
+        eval_offsets, feature_weight = precomputed["eval_offsets"], precomputed["feature_weight"]
         if rel_proj is None:
             rel_proj = ops.relative_projection(src_projs, ref_proj)
         if src_nhwc is None:  # source views of different sizes (legal in the reference): zero-padded + projection rows rescaled
@@ -328,8 +342,6 @@ class PatchMatch(nn.Module):
         rel_proj = rel_proj.contiguous()
         depth_min = depth_min.float().contiguous()
         depth_max = depth_max.float().contiguous()
-
-        feature_weight = self.feature_weight_net(ref_nhwc, eval_offsets, self._etable)
 
         depth_sample = depth
         cur_shift = depth_shift
