@@ -26,21 +26,13 @@
 //      L2-resident, one k-step ahead in registers
 //   D  lane holds column n = lane&15 (output channel) of rows 4 (lane>>4) + r (pixels of the tile): two accumulators per tile,
 //      main (hi*hi) and low (hi*lo + lo*hi); epilogue: main + low/2048 + shift (folded BatchNorm), ReLU, channels-last store.
-#include "pmn_common.hpp"
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+#include "conv_common.hpp"
 
 struct F16sArgs {
     int N, H, W, Ho, Wo, relu;
     int cout, ca;   // OUTMODE 1 / 2: valid output channels (the operands are padded to COUT = a multiple of 16), channels of `out`
     float* out_b;   // OUTMODE 1 / 2: channels [ca, cout) go here
 };
-
-#define PMN_F16S_LO_SCALE 2048.0f
 
 // DIL = dilation (padding DIL * (KS / 2)); OUTMODE 0: out [N,Ho,Wo,COUT] channels-last; 1: planar, split: out [N,ca,Ho,Wo] | out_b
 // [N,cout-ca,Ho,Wo] (the offset heads of a PatchMatch stage: propa_conv rows, then eval_conv rows); 2: channels-last, split.
@@ -118,12 +110,8 @@ __global__ __launch_bounds__(256, WPS) void conv_f16s_kernel(const float* __rest
 #pragma unroll
                 for (int k = 0; k < SB; ++k) {
                     if (k0 + k < NL && tid < TOT - (k0 + k) * NTHR) {
-                        const f32x2_t x01 = {v[k].x, v[k].y}, x23 = {v[k].z, v[k].w};
-                        const f16x2_t h01 = __builtin_convertvector(x01, f16x2_t), h23 = __builtin_convertvector(x23, f16x2_t);  // RNE
-                        // x - hi is exact in fp32
-                        const f16x2_t l01 = __builtin_convertvector((x01 - __builtin_convertvector(h01, f32x2_t)) * PMN_F16S_LO_SCALE, f16x2_t);
-                        const f16x2_t l23 = __builtin_convertvector((x23 - __builtin_convertvector(h23, f32x2_t)) * PMN_F16S_LO_SCALE, f16x2_t);
-                        const f16x4 hi = {h01[0], h01[1], h23[0], h23[1]}, lo = {l01[0], l01[1], l23[0], l23[1]};
+                        f16x4 hi, lo;
+                        f16s_split4(v[k], hi, lo);
                         *reinterpret_cast<f16x4*>(Phi + lds_first + (k0 + k) * DPIX * CCP) = hi;
                         *reinterpret_cast<f16x4*>(Plo + lds_first + (k0 + k) * DPIX * CCP) = lo;
                     }
@@ -135,8 +123,6 @@ __global__ __launch_bounds__(256, WPS) void conv_f16s_kernel(const float* __rest
         // ---- k loop of the chunk (fully unrolled; the fences keep hipcc from hoisting every B load to the top) ---------------
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
-            constexpr int dummy = 0;
-            (void)dummy;
             const int cur = ks & 1, nxt = cur ^ 1;
             // next k-step's B operands (runs on into the next chunk; the very last step re-reads itself)
             {
@@ -208,8 +194,8 @@ __global__ __launch_bounds__(256, WPS) void conv_f16s_kernel(const float* __rest
                 if (oyw + t < a.Ho) {
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
-                        f32x4_t v = accM[t][nt] + accL[t][nt] * (1.0f / PMN_F16S_LO_SCALE) + sh[nt];
-                        if (a.relu) v = __builtin_elementwise_max(v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+                        f32x4_t v = f16s_epilogue(accM[t][nt], accL[t][nt], sh[nt]);
+                        if (a.relu) v = f16s_relu(v);
                         *reinterpret_cast<f32x4_t*>(po + t * rs + 16 * nt) = v;
                     }
                 }
@@ -228,7 +214,7 @@ __global__ __launch_bounds__(256, WPS) void conv_f16s_kernel(const float* __rest
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                v[r] = accM[t][nt][r] + accL[t][nt][r] * (1.0f / PMN_F16S_LO_SCALE) + sh;
+                v[r] = f16s_epilogue(accM[t][nt][r], accL[t][nt][r], sh);
                 if (a.relu) v[r] = fmaxf(v[r], 0.0f);
             }
             if constexpr (OUTMODE == 0) {
@@ -363,11 +349,8 @@ __global__ __launch_bounds__(256, WPS) void conv_f16s_pair16_kernel(const float*
         for (int k = 0; k < NL; ++k) {
             const int idx = tid + k * 256, pix = idx / QP, q = idx - pix * QP;
             if (idx < TOT) {
-                const f32x2_t x01 = {v[k].x, v[k].y}, x23 = {v[k].z, v[k].w};
-                const f16x2_t h01 = __builtin_convertvector(x01, f16x2_t), h23 = __builtin_convertvector(x23, f16x2_t);  // RNE
-                const f16x2_t l01 = __builtin_convertvector((x01 - __builtin_convertvector(h01, f32x2_t)) * PMN_F16S_LO_SCALE, f16x2_t);
-                const f16x2_t l23 = __builtin_convertvector((x23 - __builtin_convertvector(h23, f32x2_t)) * PMN_F16S_LO_SCALE, f16x2_t);
-                const f16x4 hi = {h01[0], h01[1], h23[0], h23[1]}, lo = {l01[0], l01[1], l23[0], l23[1]};
+                f16x4 hi, lo;
+                f16s_split4(v[k], hi, lo);
                 *reinterpret_cast<f16x4*>(Phi + pix * CCP + 4 * q) = hi;
                 *reinterpret_cast<f16x4*>(Plo + pix * CCP + 4 * q) = lo;
             }
@@ -424,15 +407,10 @@ __global__ __launch_bounds__(256, WPS) void conv_f16s_pair16_kernel(const float*
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int gy = oy0 - 1 + wave * 4 + t;
-            f32x4_t v = accM[t] + accL[t] * (1.0f / PMN_F16S_LO_SCALE) + sh;
-            if (a.relu) v = __builtin_elementwise_max(v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+            f32x4_t v = f16s_epilogue(accM[t], accL[t], sh);
+            if (a.relu) v = f16s_relu(v);
             if (!((unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W)) v = f32x4_t{0.f, 0.f, 0.f, 0.f};  // layer B's zero padding
-            const f32x2_t x01 = {v[0], v[1]}, x23 = {v[2], v[3]};
-            const f16x2_t h01 = __builtin_convertvector(x01, f16x2_t), h23 = __builtin_convertvector(x23, f16x2_t);
-            const f16x2_t l01 = __builtin_convertvector((x01 - __builtin_convertvector(h01, f32x2_t)) * PMN_F16S_LO_SCALE, f16x2_t);
-            const f16x2_t l23 = __builtin_convertvector((x23 - __builtin_convertvector(h23, f32x2_t)) * PMN_F16S_LO_SCALE, f16x2_t);
-            rh[t] = f16x4{h01[0], h01[1], h23[0], h23[1]};
-            rl[t] = f16x4{l01[0], l01[1], l23[0], l23[1]};
+            f16s_split4(v, rh[t], rl[t]);
         }
     }
     __syncthreads();  // every wave is done reading the input patch: the region takes its place
@@ -455,8 +433,8 @@ __global__ __launch_bounds__(256, WPS) void conv_f16s_pair16_kernel(const float*
             for (int t = 0; t < 4; ++t) {
                 const int r = wave * 4 + t, oy = oy0 + r;
                 if (r < TO && oy < a.H) {
-                    f32x4_t v = accM[t] + accL[t] * (1.0f / PMN_F16S_LO_SCALE) + sh;
-                    if (a.relu) v = __builtin_elementwise_max(v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+                    f32x4_t v = f16s_epilogue(accM[t], accL[t], sh);
+                    if (a.relu) v = f16s_relu(v);
                     *reinterpret_cast<f32x4_t*>(out + (((size_t)n * a.H + oy) * a.W + ox) * C + 4 * kb) = v;
                 }
             }
@@ -630,9 +608,7 @@ __global__ __launch_bounds__(256, 4) void stem_f16s_kernel(const float* __restri
 #pragma unroll
             for (int c = 0; c < 8; c += 2) {
                 const f32x2_t x = {fmaxf(acc[c] + cs0[c], 0.0f), fmaxf(acc[c + 1] + cs0[c + 1], 0.0f)};
-                const f16x2_t h = __builtin_convertvector(x, f16x2_t);
-                const f32x2_t d = (x - __builtin_convertvector(h, f32x2_t)) * PMN_F16S_LO_SCALE;
-                const f16x2_t l = __builtin_convertvector(d, f16x2_t);
+                const f16x2_t h = f16s_hi2(x), l = f16s_lo2(x, h);
                 hi[c] = h[0];
                 hi[c + 1] = h[1];
                 lo[c] = l[0];
@@ -682,13 +658,23 @@ __global__ __launch_bounds__(256, 4) void stem_f16s_kernel(const float* __restri
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (oyw + t < H) {
-                f32x4_t v = accM[t] + accL[t] * (1.0f / PMN_F16S_LO_SCALE) + sh;
-                v = __builtin_elementwise_max(v, f32x4_t{0.f, 0.f, 0.f, 0.f});
-                *reinterpret_cast<f32x4_t*>(po + t * rs) = v;
+                *reinterpret_cast<f32x4_t*>(po + t * rs) = f16s_relu(f16s_epilogue(accM[t], accL[t], sh));
             }
         }
     }
     }
+}
+
+// One launch for both entry points: image n is a slice of `img` [N,3,H,W], or (img_table) batch element n % B of view n / B.
+// vec4: aligned float4 staging, which needs 16-byte aligned image rows.
+static int launch_stem_f16s(const float* img, const float* const* img_table, int B, bool vec4, const float* w0, const float* s0,
+                            const void* w1a, const float* s1, float* out, int N, int H, int W, void* stream) {
+    constexpr int TS = 16, TH = PMN_STEM_TH;
+    const int blocks = N * ((W + TS - 1) / TS) * ((H + TH - 1) / TH);
+    PMN_LAUNCH((vec4 ? stem_f16s_kernel<true, PMN_STEM_TH> : stem_f16s_kernel<false, PMN_STEM_TH>), dim3(blocks), dim3(256), 0,
+               (hipStream_t)stream, img, w0, s0, reinterpret_cast<const f16x8*>(w1a), s1, out, N, H, W, img_table, B);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
 }
 
 // img [N,3,H,W] planar; w0 [3][3][3][8] / s0 [8] (pack_conv layout, fp32); w1a DEVICE fp16 [3][2][64][8] (params.pack_stem_conv1_f16s:
@@ -696,17 +682,8 @@ __global__ __launch_bounds__(256, 4) void stem_f16s_kernel(const float* __restri
 extern "C" int pmn_stem_f16s(const float* img, const float* w0, const float* s0, const void* w1a, const float* s1, float* out,
                              int N, int H, int W, void* stream) {
     if (!img || !w0 || !s0 || !w1a || !s1 || !out || N < 1 || H < 1 || W < 1) return PMN_ERR_ARG;
-    constexpr int TS = 16, TH = PMN_STEM_TH;
-    const int blocks = N * ((W + TS - 1) / TS) * ((H + TH - 1) / TH);
-    // aligned float4 staging needs 16-byte aligned image rows: W % 4 == 0 and a 16-byte aligned base
-    if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0)
-        PMN_LAUNCH((stem_f16s_kernel<true, PMN_STEM_TH>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, img, w0, s0,
-                           reinterpret_cast<const f16x8*>(w1a), s1, out, N, H, W, nullptr, 1);
-    else
-        PMN_LAUNCH((stem_f16s_kernel<false, PMN_STEM_TH>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, img, w0, s0,
-                           reinterpret_cast<const f16x8*>(w1a), s1, out, N, H, W, nullptr, 1);
-    PMN_CHECK_LAUNCH();
-    return PMN_OK;
+    const bool vec4 = W % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0;
+    return launch_stem_f16s(img, nullptr, 1, vec4, w0, s0, w1a, s1, out, N, H, W, stream);
 }
 
 // The same for `views` separately allocated images of one size: img_table DEVICE array of `views` addresses, entry v = a dense
@@ -717,15 +694,5 @@ extern "C" int pmn_stem_f16s(const float* img, const float* w0, const float* s0,
 extern "C" int pmn_stem_f16s_views(const float* const* img_table, int views, const float* w0, const float* s0, const void* w1a,
                                    const float* s1, float* out, int B, int H, int W, void* stream) {
     if (!img_table || !w0 || !s0 || !w1a || !s1 || !out || views < 1 || B < 1 || H < 1 || W < 1) return PMN_ERR_ARG;
-    constexpr int TS = 16, TH = PMN_STEM_TH;
-    const int N = views * B;
-    const int blocks = N * ((W + TS - 1) / TS) * ((H + TH - 1) / TH);
-    if (W % 4 == 0)
-        PMN_LAUNCH((stem_f16s_kernel<true, PMN_STEM_TH>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, nullptr, w0, s0,
-                           reinterpret_cast<const f16x8*>(w1a), s1, out, N, H, W, img_table, B);
-    else
-        PMN_LAUNCH((stem_f16s_kernel<false, PMN_STEM_TH>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, nullptr, w0, s0,
-                           reinterpret_cast<const f16x8*>(w1a), s1, out, N, H, W, img_table, B);
-    PMN_CHECK_LAUNCH();
-    return PMN_OK;
+    return launch_stem_f16s(nullptr, img_table, B, W % 4 == 0, w0, s0, w1a, s1, out, views * B, H, W, stream);
 }

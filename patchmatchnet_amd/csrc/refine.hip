@@ -6,7 +6,7 @@
 //   pmn_refine_tail    depth = (nearest_x2(d) + res(conv3(x16))) * span + min                    [B,H,W,16] -> [B,1,H,W]
 // Both own a 16x16 tile of output pixels per 256-thread workgroup, stage what they read in LDS with every load of a thread
 // in flight at once, and feed the FMAs wave-uniform SGPR weights ([ky][kx][ci][co] layouts of params.pack_conv / pack_deconv).
-#include "pmn_common.hpp"
+#include "conv_common.hpp"
 
 typedef const float __attribute__((address_space(4))) cfloat;
 
@@ -259,12 +259,6 @@ extern "C" int pmn_refine_tail(const float* x16, const float* w3, const float* s
 // (scripts/experiments/refine_fused/ab.py).  conv3 carries the split-fp16 error (2-4e-7 of its output scale: both forms are 1.1e-6 of
 // the depth span from a float64 evaluation); everything else is the arithmetic of the two kernels it replaces.
 // =================================================================================================================================
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-#define RF_LO_SCALE 2048.0f
-
 template <bool VEC4>
 __global__ __launch_bounds__(PMN_BLOCK, 3) void refine_fused_kernel(
     const float* __restrict__ img, const float* __restrict__ t2, const float* __restrict__ w0, const float* __restrict__ s0,
@@ -401,9 +395,8 @@ __global__ __launch_bounds__(PMN_BLOCK, 3) void refine_fused_kernel(
                 for (int c = 0; c < 8; c += 2) {
                     const f32x2_t a = {fmaxf(up[c] + csd[c], 0.0f), fmaxf(up[c + 1] + csd[c + 1], 0.0f)};
                     const f32x2_t b = {fmaxf(f[c] + cs0[c], 0.0f), fmaxf(f[c + 1] + cs0[c + 1], 0.0f)};
-                    const f16x2_t ah = __builtin_convertvector(a, f16x2_t), bh = __builtin_convertvector(b, f16x2_t);
-                    const f16x2_t al = __builtin_convertvector((a - __builtin_convertvector(ah, f32x2_t)) * RF_LO_SCALE, f16x2_t);
-                    const f16x2_t bl = __builtin_convertvector((b - __builtin_convertvector(bh, f32x2_t)) * RF_LO_SCALE, f16x2_t);
+                    const f16x2_t ah = f16s_hi2(a), bh = f16s_hi2(b);
+                    const f16x2_t al = f16s_lo2(a, ah), bl = f16s_lo2(b, bh);
                     h0[c] = ah[0]; h0[c + 1] = ah[1]; l0[c] = al[0]; l0[c + 1] = al[1];
                     h1[c] = bh[0]; h1[c + 1] = bh[1]; l1[c] = bl[0]; l1[c + 1] = bl[1];
                 }
@@ -465,8 +458,7 @@ __global__ __launch_bounds__(PMN_BLOCK, 3) void refine_fused_kernel(
                         const int gy = oy0 - 1 + r, gx = ox0 - 1 + q;
                         f32x4_t v = f32x4_t{0.f, 0.f, 0.f, 0.f};
                         if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
-                            v = accM[j] + accL[j] * (1.0f / RF_LO_SCALE) + sh;
-                            v = __builtin_elementwise_max(v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+                            v = f16s_relu(f16s_epilogue(accM[j], accL[j], sh));
                         }
                         *reinterpret_cast<f32x4_t*>(mid + r * MRP + q * MP + 4 * kb) = v;
                     }
@@ -511,14 +503,10 @@ extern "C" int pmn_refine_fused(const float* img, const float* t2, const float* 
     const size_t lds = (size_t)2 * 20 * 26 * 16 * sizeof(_Float16) + (size_t)18 * 256 * sizeof(float);  // 33,280 + 18,432 B
     const int blocks = B * ((W + 15) / 16) * ((H + 15) / 16);
     const bool vec4 = W % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0;
-    const void* kern = vec4 ? reinterpret_cast<const void*>(refine_fused_kernel<true>) : reinterpret_cast<const void*>(refine_fused_kernel<false>);
-    if (pmn_raise_dynamic_lds(kern, lds) != PMN_OK) return PMN_ERR_LAUNCH;
-    if (vec4)
-        PMN_LAUNCH(refine_fused_kernel<true>, dim3(blocks), dim3(PMN_BLOCK), lds, (hipStream_t)stream, img, t2, w0, s0, wd, sd,
-                           reinterpret_cast<const f16x8*>(w3a), s3, wr, dnorm, depth_min, depth_max, out, B, H, W);
-    else
-        PMN_LAUNCH(refine_fused_kernel<false>, dim3(blocks), dim3(PMN_BLOCK), lds, (hipStream_t)stream, img, t2, w0, s0, wd, sd,
-                           reinterpret_cast<const f16x8*>(w3a), s3, wr, dnorm, depth_min, depth_max, out, B, H, W);
+    const auto kern = vec4 ? refine_fused_kernel<true> : refine_fused_kernel<false>;
+    if (pmn_raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds) != PMN_OK) return PMN_ERR_LAUNCH;
+    PMN_LAUNCH(kern, dim3(blocks), dim3(PMN_BLOCK), lds, (hipStream_t)stream, img, t2, w0, s0, wd, sd,
+               reinterpret_cast<const f16x8*>(w3a), s3, wr, dnorm, depth_min, depth_max, out, B, H, W);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }

@@ -692,8 +692,7 @@ def conv2d_f16s(x: torch.Tensor, weights: torch.Tensor, shift: torch.Tensor, k: 
     _dev(x, "x")
     _f16_domain_probe(x)
     _dev(shift, "shift")
-    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dtype != torch.float16 or not weights.is_contiguous():
-        raise PmnError("conv2d_f16s: weights must be a contiguous float16 tensor on a ROCm GPU (params.pack_conv_f16s)")
+    _dev_as(weights, "conv2d_f16s: weights (params.pack_conv_f16s)", torch.float16)
     N, H, W, cin = x.shape
     cout = shift.shape[0]
     if (k, stride, cin, cout) not in F16S_SHAPES:
@@ -719,9 +718,9 @@ def conv2d_f16s_pair(x: torch.Tensor, weights_a: torch.Tensor, shift_a: torch.Te
     N, H, W, C = x.shape
     for w_, s_ in ((weights_a, shift_a), (weights_b, shift_b)):
         _dev(s_, "shift")
-        if not isinstance(w_, torch.Tensor) or not w_.is_cuda or w_.dtype != torch.float16 or not w_.is_contiguous() or \
-                tuple(w_.shape) != (1, 5, 1, 2, 64, 8) or s_.numel() != 16:
-            raise PmnError("conv2d_f16s_pair: weights must be params.pack_conv_f16s of a (3, 1, 16, 16) layer on a ROCm GPU")
+        _dev_as(w_, "conv2d_f16s_pair: weights", torch.float16)
+        if tuple(w_.shape) != (1, 5, 1, 2, 64, 8) or s_.numel() != 16:
+            raise PmnError("conv2d_f16s_pair: weights must be params.pack_conv_f16s of a (3, 1, 16, 16) layer")
     if C != 16:
         raise PmnError("conv2d_f16s_pair: 16-channel layers only")
     out = torch.empty((N, H, W, 16), dtype=torch.float32, device=x.device)
@@ -779,8 +778,8 @@ def offset_heads_f16s(x: torch.Tensor, weights: torch.Tensor, shift: torch.Tenso
     _dev(shift, "shift")
     N, H, W, cin = x.shape
     coutp = shift.shape[0]
-    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dtype != torch.float16 or not weights.is_contiguous() \
-            or tuple(weights.shape) != (cin // 16, (9 * 2 + 3) // 4, coutp // 16, 2, 64, 8) or not 0 < ca <= cout <= coutp \
+    _dev_as(weights, "offset_heads_f16s: weights", torch.float16)
+    if tuple(weights.shape) != (cin // 16, (9 * 2 + 3) // 4, coutp // 16, 2, 64, 8) or not 0 < ca <= cout <= coutp \
             or coutp != (cout + 15) // 16 * 16:
         raise PmnError("offset_heads_f16s: weights are not in pack_offset_heads_f16s layout for this input")
     out_a = torch.empty((N, ca, H, W), dtype=torch.float32, device=x.device)
@@ -860,9 +859,8 @@ def refine_fused(img: torch.Tensor, t2: torch.Tensor, w0: torch.Tensor, s0: torc
     for n_, t_ in (("img", img), ("t2", t2), ("w0", w0), ("s0", s0), ("wd", wd), ("sd", sd), ("s3", s3), ("wr", wr), ("dnorm", dnorm),
                    ("depth_min", depth_min), ("depth_max", depth_max)):
         _dev(t_, n_)
-    if not isinstance(w3a, torch.Tensor) or not w3a.is_cuda or w3a.dtype != torch.float16 or tuple(w3a.shape) != (5, 2, 64, 8) \
-            or not w3a.is_contiguous():
-        raise PmnError("refine_fused: w3a must be the float16 [5,2,64,8] tensor of params.pack_refine_conv3_f16s on a ROCm GPU")
+    if tuple(_dev_as(w3a, "refine_fused: w3a", torch.float16).shape) != (5, 2, 64, 8):
+        raise PmnError("refine_fused: w3a must be the float16 [5,2,64,8] tensor of params.pack_refine_conv3_f16s")
     B, c, H, W = img.shape
     if c != 3 or H % 2 or W % 2 or tuple(t2.shape) != (B, H // 2, W // 2, 8) or tuple(dnorm.shape) != (B, 1, H // 2, W // 2) or \
             tuple(w0.shape) != (3, 3, 3, 8) or tuple(wd.shape) != (3, 3, 8, 8) or tuple(wr.shape) != (3, 3, 8) or s3.numel() != 8 or \
@@ -917,9 +915,8 @@ def stem_f16s(img: torch.Tensor, w0: torch.Tensor, s0: torch.Tensor, w1a: torch.
     (optionally into ``out``); w1a = params.pack_stem_conv1_f16s (float16 [3,2,64,8])."""
     for n_, t_ in (("img", img), ("w0", w0), ("s0", s0), ("s1", s1)):
         _dev(t_, n_)
-    if not isinstance(w1a, torch.Tensor) or not w1a.is_cuda or w1a.dtype != torch.float16 or tuple(w1a.shape) != (3, 2, 64, 8) \
-            or not w1a.is_contiguous():
-        raise PmnError("stem_f16s: w1a must be the float16 [3,2,64,8] tensor of params.pack_stem_conv1_f16s on a ROCm GPU")
+    if tuple(_dev_as(w1a, "stem_f16s: w1a", torch.float16).shape) != (3, 2, 64, 8):
+        raise PmnError("stem_f16s: w1a must be the float16 [3,2,64,8] tensor of params.pack_stem_conv1_f16s")
     N, c, H, W = img.shape
     if c != 3 or tuple(w0.shape) != (3, 3, 3, 8):
         raise PmnError("stem_f16s: expects a 3-channel image and 3->8 conv0 weights")
@@ -944,8 +941,7 @@ def stem_f16s_views(images: "SourceTable", w0: torch.Tensor, s0: torch.Tensor, w
         _dev(t_, n_)
     if not isinstance(images, SourceTable) or len(images.shape) != 5 or images.shape[2] != 3:
         raise PmnError("stem_f16s_views: a SourceTable of shape (views, B, 3, H, W)")
-    if not isinstance(w1a, torch.Tensor) or not w1a.is_cuda or w1a.dtype != torch.float16 or tuple(w1a.shape) != (3, 2, 64, 8) \
-            or not w1a.is_contiguous() or tuple(w0.shape) != (3, 3, 3, 8):
+    if tuple(_dev_as(w1a, "stem_f16s_views: w1a", torch.float16).shape) != (3, 2, 64, 8) or tuple(w0.shape) != (3, 3, 3, 8):
         raise PmnError("stem_f16s_views: 3->8 conv0 weights and the float16 [3,2,64,8] tensor of params.pack_stem_conv1_f16s")
     V, B, _, H, W = images.shape
     out = torch.empty((V * B, H, W, 8), dtype=torch.float32, device=images.device)
