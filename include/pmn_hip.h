@@ -722,6 +722,25 @@ int pmn_mesh_sample(const float *vertices, int n_vertices, const int *faces, int
                     const long long *sample_scan, long long n_samples, unsigned long long seed, float *points, int *face,
                     unsigned char *out_colors, void *stream);
 
+/* Added under ABI 25.  Image undistortion of the COLMAP import (colmap_input.py --undistort): resamples a
+ * distorted picture into an ideal pinhole camera.  src [Hs][Ws][channels] uint8 and dst [Hd][Wd][channels] uint8 are DEVICE,
+ * contiguous, channels 1 or 3, each below 2^31 bytes.  model is COLMAP's camera model id and src_params_host its parameters in
+ * COLMAP's order (HOST float64): 0 SIMPLE_PINHOLE (f cx cy), 1 PINHOLE (fx fy cx cy), 2 SIMPLE_RADIAL (f cx cy k), 3 RADIAL
+ * (f cx cy k1 k2), 4 OPENCV (fx fy cx cy k1 k2 p1 p2), 5 OPENCV_FISHEYE (fx fy cx cy k1 k2 k3 k4), 6 FULL_OPENCV (fx fy cx cy k1 k2
+ * p1 p2 k3 k4 k5 k6), 8 SIMPLE_RADIAL_FISHEYE (f cx cy k), 9 RADIAL_FISHEYE (f cx cy k1 k2); 7 (FOV), 10 (THIN_PRISM_FISHEYE) and
+ * every other id are PMN_ERR_ARG.  dst_pinhole_host: HOST float64 fx' fy' cx' cy' of the output camera.  All parameters travel by
+ * value in the kernel arguments.  Per output pixel (x, y), in float64, IEEE, without contraction, in this order:
+ *   u = ((x + 0.5) - cx') / fx', v = ((y + 0.5) - cy') / fy';  (ud, vd) = the model's distortion of (u, v);
+ *   sx = (fx * ud + cx) - 0.5, sy = (fy * vd + cy) - 0.5;  x0 = floor(sx), y0 = floor(sy), ax = sx - x0, ay = sy - y0;
+ *   val = (1 - ay) * ((1 - ax) * s00 + ax * s01) + ay * ((1 - ax) * s10 + ax * s11) per channel, s.. = src[y0 + ..][x0 + ..];
+ *   dst = floor(val + 0.5).
+ * The pixel is valid iff x0 >= 0, y0 >= 0, x0 + 1 <= Ws - 1 and y0 + 1 <= Hs - 1, tested on the doubles so that NaN and infinity
+ * fail; an invalid pixel is 0 in every channel and reads nothing.  valid (DEVICE uint8 [Hd][Wd], 1 / 0) and coords (DEVICE float64
+ * [Hd][Wd][2] = (sx, sy) of every pixel, valid or not) may each be NULL.  Every byte of dst / valid / coords is written.  One launch. */
+int pmn_undistort_image(const unsigned char *src, int Hs, int Ws, int channels, int model, const double *src_params_host,
+                        const double *dst_pinhole_host, int Hd, int Wd, unsigned char *dst, unsigned char *valid, double *coords,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

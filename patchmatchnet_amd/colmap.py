@@ -5,7 +5,8 @@ colmap_output.py).
     import_model(input, output, ...)        cams/%08d_cam.txt, pair.txt, images/%08d.jpg: what eval.py reads
     export_workspace(input, results, out)   images/, stereo/{depth,confidence}_maps/*.geometric.bin, stereo/*.cfg, sparse/*.txt
 
-Host geometry is numpy float64 with the reference's semantics (intrinsics from its per-model parameter table, distortion ignored;
+Host geometry is numpy float64 with the reference's semantics (intrinsics from its per-model parameter table, distortion ignored
+unless import_model(undistort=True) / colmap_input.py --undistort resamples the pictures into pinhole cameras first: undistort.py;
 extrinsics from qvec / tvec; depth range = the 1 % / 99 % order statistics of the camera-space z of every observation).  The one hot
 path, the pairwise view-selection scores, runs on the GPU (pmn_view_scores through ops.view_scores); there is no CPU fallback.
 """
@@ -19,7 +20,8 @@ from typing import Dict, List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 
-# COLMAP's camera models: id -> (name, parameter names).  Only f / fx / fy / cx / cy are used (the reference ignores distortion).
+# COLMAP's camera models: id -> (name, parameter names).  Only f / fx / fy / cx / cy are used (the reference ignores distortion)
+# unless the import undistorts (undistort.py reads the rest).
 CAMERA_MODELS: Dict[int, Tuple[str, Tuple[str, ...]]] = {
     0: ("SIMPLE_PINHOLE", ("f", "cx", "cy")),
     1: ("PINHOLE", ("fx", "fy", "cx", "cy")),
@@ -168,7 +170,8 @@ def read_model(sparse_dir: str) -> Model:
 # ---- host geometry ------------------------------------------------------------------------------------------------------------
 
 def intrinsic_matrix(cam: Camera) -> np.ndarray:
-    """3x3 float64 K from the model's f / fx / fy / cx / cy (distortion parameters are ignored, as in the reference)."""
+    """3x3 float64 K from the model's f / fx / fy / cx / cy (distortion parameters are ignored, as in the reference, unless the import runs
+    with undistort=True: it then passes the undistorted PINHOLE camera here)."""
     p = dict(zip(CAMERA_MODELS[CAMERA_MODEL_IDS[cam.model]][1], cam.params))
     fx, fy = (p["f"], p["f"]) if "f" in p else (p["fx"], p["fy"])
     return np.array([[fx, 0, p["cx"]], [0, fy, p["cy"]], [0, 0, 1]])
@@ -284,10 +287,73 @@ def copy_images(image_dir: str, out_dir: str, names: Sequence[str], convert_form
         os.replace(t, os.path.join(out_dir, "%08d.jpg" % i))
 
 
+def undistort_images(image_dir: str, out_dir: str, names: Sequence[str], cameras: Sequence[Camera], dst_cameras: Sequence[Camera],
+                     device) -> float:
+    """images/<name> -> out_dir/%08d.jpg, each picture resampled from cameras[i] into dst_cameras[i] on the GPU (ops.undistort_image)
+    and written as JPEG quality 95 through PIL, with copy_images' temporary-name protocol.  Decoding and encoding run on a small
+    thread pool; every GPU call is made from this thread.  Returns the device time of the resampling in seconds, summed over the
+    images."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image as PilImage
+    from . import ops
+    os.makedirs(out_dir, exist_ok=True)
+
+    def decode(i: int) -> np.ndarray:
+        with PilImage.open(os.path.join(image_dir, names[i])) as im:
+            arr = np.array(im.convert("RGB"), dtype=np.uint8)  # (a copy: PIL's buffer is read-only)
+        cam = cameras[i]
+        if arr.shape[:2] != (cam.height, cam.width):
+            raise ColmapFormatError(f"image {names[i]} is {arr.shape[1]} x {arr.shape[0]} but its camera (camera_id {cam.id}) is "
+                                    f"{cam.width} x {cam.height}: it cannot be undistorted with that camera")
+        return arr
+
+    def encode(i: int, arr: np.ndarray) -> str:
+        t = os.path.join(out_dir, ".pmn_import_%08d.tmp" % i)
+        PilImage.fromarray(arr).save(t, "JPEG", quality=95)
+        return t
+
+    n, ahead, device_ms, tmp = len(names), 4, 0.0, []
+    with ThreadPoolExecutor(max_workers=min(8, max(1, os.cpu_count() or 1))) as pool, torch.cuda.device(device):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        decoded = {i: pool.submit(decode, i) for i in range(min(ahead, n))}
+        for i in range(n):
+            arr = decoded.pop(i).result()
+            if i + ahead < n:
+                decoded[i + ahead] = pool.submit(decode, i + ahead)
+            img = torch.from_numpy(arr).to(device)
+            start.record()
+            out = ops.undistort_image(img, cameras[i], dst_cameras[i])
+            stop.record()
+            host = out.cpu().numpy()  # (synchronises: the events are complete)
+            device_ms += start.elapsed_time(stop)
+            tmp.append(pool.submit(encode, i, host))
+        tmp = [t.result() for t in tmp]
+    for i, t in enumerate(tmp):
+        os.replace(t, os.path.join(out_dir, "%08d.jpg" % i))
+    return device_ms / 1e3
+
+
+def _warn_ignored_distortion(model: Model) -> None:
+    from . import undistort as U
+    names = sorted({cam.model for cam in model.cameras.values() if U.has_distortion(cam)})
+    if names:
+        import sys
+        print(f"colmap import: the model has cameras with non-zero distortion parameters ({', '.join(names)}) and they are ignored: "
+              "the pictures must already be undistorted, or pass --undistort", file=sys.stderr)
+
+
 def import_model(input_folder: str, output_folder: str = "", num_src_images: int = -1, theta0: float = 5, sigma1: float = 1,
-                 sigma2: float = 10, convert_format: bool = False, device: str = "cuda:0") -> Dict[str, float]:
+                 sigma2: float = 10, convert_format: bool = False, device: str = "cuda:0", undistort: bool = False,
+                 blank_pixels: float = 0.0, min_scale: float = 0.2, max_scale: float = 2.0, max_image_size: int = -1) -> Dict[str, float]:
     """<input>/sparse + <input>/images -> <output>/cams, <output>/pair.txt, <output>/images.  Returns the wall time of each phase
-    in seconds (read, prepare, view_scores = device time of pmn_view_scores, write)."""
+    in seconds (read, prepare, view_scores = device time of pmn_view_scores, write).
+
+    ``undistort``: for a raw model (cameras with distortion, pictures as taken).  One ideal PINHOLE camera is computed per COLMAP
+    camera (undistort.undistorted_camera with blank_pixels / min_scale / max_scale / max_image_size), every picture is resampled into
+    it on the GPU and written as JPEG quality 95, and the cam files carry the undistorted intrinsics; extrinsics, depth ranges and
+    pair.txt do not depend on the intrinsics.  The result gains "undistort", the device time of the resampling summed over the images.
+    Without it the distortion parameters are ignored, as in the reference (one line on stderr says so when any is non-zero)."""
     import torch
     from . import ops
     output_folder = output_folder or input_folder
@@ -301,7 +367,13 @@ def import_model(input_folder: str, output_folder: str = "", num_src_images: int
     times["read"] = time.perf_counter() - t
 
     t = time.perf_counter()
-    intr = {cid: intrinsic_matrix(cam) for cid, cam in model.cameras.items()}
+    if undistort:
+        from . import undistort as U
+        und = {cid: U.undistorted_camera(cam, blank_pixels, min_scale, max_scale, max_image_size) for cid, cam in model.cameras.items()}
+        intr = {cid: intrinsic_matrix(cam) for cid, cam in und.items()}
+    else:
+        intr = {cid: intrinsic_matrix(cam) for cid, cam in model.cameras.items()}
+        _warn_ignored_distortion(model)
     extr = [extrinsic_matrix(im) for im in model.images]
     ranges = depth_ranges(model, extr)
     centers = np.stack([camera_center(e) for e in extr]) if extr else np.zeros((0, 3))
@@ -330,8 +402,13 @@ def import_model(input_folder: str, output_folder: str = "", num_src_images: int
     for i, im in enumerate(model.images):
         write_cam_file(os.path.join(cam_dir, "%08d_cam.txt" % i), extr[i], intr[im.camera_id], *ranges[i])
     write_pair_file(os.path.join(output_folder, "pair.txt"), view_sel)
-    copy_images(os.path.join(input_folder, "images"), os.path.join(output_folder, "images"), [im.name for im in model.images],
-                convert_format)
+    if undistort:
+        times["undistort"] = undistort_images(os.path.join(input_folder, "images"), os.path.join(output_folder, "images"),
+                                              [im.name for im in model.images], [model.cameras[im.camera_id] for im in model.images],
+                                              [und[im.camera_id] for im in model.images], dev)
+    else:
+        copy_images(os.path.join(input_folder, "images"), os.path.join(output_folder, "images"), [im.name for im in model.images],
+                    convert_format)
     times["write"] = time.perf_counter() - t
     return times
 

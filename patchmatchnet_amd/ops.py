@@ -1554,6 +1554,68 @@ def view_scores(cam_centers: torch.Tensor, xyz: torch.Tensor, obs_ptr: torch.Ten
     return out
 
 
+def undistort_image(image_u8_hwc: torch.Tensor, camera, dst_camera, want_valid: bool = False, want_coords: bool = False,
+                    out: Optional[torch.Tensor] = None):
+    """pmn_undistort_image: a distorted picture resampled into an ideal pinhole camera.
+
+    image_u8_hwc: uint8 [H,W,3] or [H,W,1] or [H,W] on the GPU, contiguous, H x W = camera.height x camera.width.  ``camera`` is the
+    source colmap.Camera (any model but FOV / THIN_PRISM_FISHEYE), ``dst_camera`` the PINHOLE (or SIMPLE_PINHOLE) camera of the
+    output, usually undistort.undistorted_camera(camera).  Returns the uint8 image [H',W',C] (shaped like the input; ``out`` is
+    filled and returned when given) on the current stream; with want_valid / want_coords the tuple (image, valid uint8 [H',W'] or
+    None, coords float64 [H',W',2] = the sampling position (sx, sy) of every pixel, or None).  Every byte of the outputs is written.
+    A pinhole source whose output camera has the same size and intrinsics is copied, not resampled: every pixel is valid and its
+    position is itself."""
+    from . import undistort as U
+    t = image_u8_hwc
+    if not isinstance(t, torch.Tensor):
+        raise PmnError("undistort_image: expected a torch.Tensor")
+    if not t.is_cuda:
+        raise PmnError(f"undistort_image: tensor is on {t.device}; patchmatchnet_amd runs only on a ROCm GPU (no CPU fallback)")
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise PmnError("undistort_image: expected a contiguous uint8 tensor")
+    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] not in (1, 3)):
+        raise PmnError(f"undistort_image: expected [H,W], [H,W,1] or [H,W,3], got {tuple(t.shape)}")
+    C = 1 if t.dim() == 2 else int(t.shape[2])
+    Hs, Ws = int(t.shape[0]), int(t.shape[1])
+    if (Hs, Ws) != (int(camera.height), int(camera.width)):
+        raise PmnError(f"undistort_image: the image is {Ws} x {Hs} but camera {camera.id} is {camera.width} x {camera.height}")
+    try:
+        U.check_model(camera)
+    except U.UndistortError as e:
+        raise PmnError(f"undistort_image: {e}") from e
+    if dst_camera.model not in U.PINHOLE_MODELS:
+        raise PmnError(f"undistort_image: the output camera must be a pinhole, got {dst_camera.model}")
+    Hd, Wd = int(dst_camera.height), int(dst_camera.width)
+    if Hs < 1 or Ws < 1 or Hd < 1 or Wd < 1 or Hs * Ws * C >= 2 ** 31 or Hd * Wd * C >= 2 ** 31:
+        raise PmnError("undistort_image: an image must have at least one pixel and fewer than 2^31 bytes")
+    shape = (Hd, Wd) if t.dim() == 2 else (Hd, Wd, C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=t.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+              and tuple(out.shape) == shape and out.device == t.device):
+        raise PmnError(f"undistort_image: out must be a contiguous uint8 {shape} tensor on the image's device")
+    elif _ranges_overlap(_range(out), _range(t)):
+        raise PmnError("undistort_image: out must not overlap the image")
+    valid = torch.empty((Hd, Wd), dtype=torch.uint8, device=t.device) if want_valid else None
+    coords = torch.empty((Hd, Wd, 2), dtype=torch.float64, device=t.device) if want_coords else None
+    dst = U.focal_and_center(dst_camera)
+    if camera.model in U.PINHOLE_MODELS and (Hd, Wd) == (Hs, Ws) and dst == U.focal_and_center(camera):
+        out.copy_(t.view(shape))
+        if valid is not None:
+            valid.fill_(1)
+        if coords is not None:
+            coords[..., 0] = torch.arange(Wd, dtype=torch.float64, device=t.device)[None, :]
+            coords[..., 1] = torch.arange(Hd, dtype=torch.float64, device=t.device)[:, None]
+    else:
+        params = (ctypes.c_double * len(camera.params))(*[float(v) for v in camera.params])
+        pin = (ctypes.c_double * 4)(*dst)
+        with torch.cuda.device(t.device):
+            check(_lib.lib().pmn_undistort_image(t.data_ptr(), Hs, Ws, C, U.CAMERA_MODEL_IDS[camera.model],
+                                                 ctypes.cast(params, ctypes.c_void_p), ctypes.cast(pin, ctypes.c_void_p), Hd, Wd,
+                                                 out.data_ptr(), _ptr(valid), _ptr(coords), _stream(t)), "pmn_undistort_image")
+    return (out, valid, coords) if (want_valid or want_coords) else out
+
+
 def depth_metrics(depth_gt: torch.Tensor, depth_min: torch.Tensor, depth_patchmatch, thresholds: Sequence[float] = (1.0, 2.0, 4.0, 8.0),
                   out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pmn_depth_metrics: per sample one row of raw float64 sums and exact counts against the ground truth (train.py --mode test;
