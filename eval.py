@@ -728,6 +728,9 @@ def filter_depth(args, scan, produced, rank, world, device, fuser=None, scan_ima
             _fuse_scan_guarded(args, job, rank, world, device, torch.cuda.current_stream(device), pool, io_pool, {})
 
 
+_MERGE_NOTED = []
+
+
 def _fuse_scan_guarded(args, job, rank, world, device, stream, pool, io_pool, state):
     """_fuse_scan; with several ranks a failure leaves ``fused.ply.part<rank>.err`` next to the target so that rank 0, which polls for
     the parts, stops at once instead of waiting for its timeout."""
@@ -762,7 +765,12 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
         return u8 if u8 is not None else np.ascontiguousarray(read_image(path, args.image_max_dim)[0], np.float32)
 
     decoding = {ref: pool.submit(ref_image, ref) for ref, _ in my_pairs if job["images"].get(ref) is None}
-    fractions = {}
+    fractions, finals = {}, {}
+    merge = bool(getattr(args, "fuse_merge", 0))  # --fuse_merge 1: each surface point once
+    if merge and world > 1 and not _MERGE_NOTED:
+        _MERGE_NOTED.append(True)  # once per process
+        sys.stderr.write("--fuse_merge 1 with {} ranks: every rank merges inside its own block of reference views only; duplicates "
+                         "across block boundaries remain and fused.ply depends on the number of ranks\n".format(world))
 
     def write_masks(ref, pin, ev, h, w, ring):
         try:
@@ -772,6 +780,7 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
                 save_image(os.path.join(mask_dir, "{:0>8}_{}.png".format(ref, kind)), m)
             # count / size = the float64 mean of a bool array the reference prints (eval.py:262-265), without the float64 pass
             fractions[ref] = tuple(np.count_nonzero(m) / m.size for m in mk)
+            finals[ref] = int(np.count_nonzero(mk[2]))
         finally:
             ring.release(pin)
 
@@ -811,7 +820,7 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
                                                args.geo_depth_thres, args.geo_mask_thres, args.photo_thres, packer,
                                                sizes=sizes if job["mixed"] else None, normals=with_normals,
                                                normals_radius=getattr(args, "normals_radius", 2),
-                                               normals_depth_thres=getattr(args, "normals_depth_thres", 0.01)):
+                                               normals_depth_thres=getattr(args, "normals_depth_thres", 0.01), merge=merge):
             masks_dev.append((ref, m))
             images.pop(ref, None)
         t_enqueued = time.time()
@@ -900,6 +909,9 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
           "body chunks queued {:.3f}, body on disk {:.3f}, masks on disk {:.3f} s after the start)".format(
               len(my_pairs), scan or args.input_folder, time.time() - t_fuse, total, t_enqueued - t_fuse, t_counts - t_fuse,
               t_chunks - t_fuse, t_body - t_fuse, t_masks - t_fuse))
+    if merge:
+        print("fusion stage: --fuse_merge 1 wrote {} points of {} final pixels on this rank ({})".format(
+            total, sum(finals.values()), scan or args.input_folder))
 
 
 def build_parser():
@@ -957,6 +969,12 @@ def build_parser():
                    help="--output_type both|fusion: 1 writes an ORIENTED fused.ply (x y z nx ny nz red green blue, 27 B per point): "
                         "per reference view a surface-normal map from its estimated depth map (pmn_depth_normals), rotated to "
                         "the world frame; the points, masks and maps are those of a run without it")
+    p.add_argument("--fuse_merge", type=int, default=0, choices=(0, 1),
+                   help="--output_type both|fusion: 1 writes each surface point of fused.ply ONCE: a final pixel whose point an earlier "
+                        "reference view (pair.txt order) already wrote, seen consistently from there, is skipped "
+                        "(pmn_fuse_view_merged); the points that remain, their order, the masks and the maps are those of a run "
+                        "without it.  With several ranks every rank merges inside its own block of reference views only: "
+                        "duplicates across block boundaries remain and the file depends on the number of ranks")
     p.add_argument("--normals_radius", type=int, default=2, choices=(1, 2, 3), help="--normals 1: window radius of the plane fit")
     p.add_argument("--normals_depth_thres", type=float, default=0.01,
                    help="--normals 1: relative depth difference up to which a neighbour counts as the same surface")

@@ -299,6 +299,23 @@ int pmn_fuse_view(const float *maps, long long slot_stride, int ref_slot, const 
                   const int *src_hw_host, int n_src, const float *mats, int H, int W, float geo_pixel_thres, float geo_depth_thres, int geo_mask_thres,
                   float photo_thres, unsigned char *masks, float *xyz, double *depth_avg, int *geo_sum, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  pmn_fuse_view that writes each surface point once
+ * (DESIGN.md section 22): every argument of pmn_fuse_view with its meaning, and masks, xyz, depth_avg, geo_sum bit for bit what
+ * pmn_fuse_view writes (one kernel body, instantiated with and without the claims).  claimed: DEVICE bytes, one slot per map slot,
+ * claim_stride bytes apart (>= h*w of the largest view); slot v is view v's map [h_v][w_v] at its own size, 1 = a view fused
+ * earlier wrote a point that covers this pixel.  The caller zeroes it before a scan's first view and fuses the views on ONE stream.
+ * emit [H][W] bytes = final && !claimed[ref_slot]: the pixels whose points belong in the file.  Every FINAL pixel (emitted or not)
+ * then claims, in each source view s whose consistency test it passed, the pixel (rintf(xs), rintf(ys)) of its forward projection
+ * (the float32 coordinates that feed the bilinear sample), provided that pixel lies inside view s's map and view s's own depth d
+ * there agrees with the point's float32 depth z in that camera: fabsf(d - z) / z < geo_depth_thres.  A claim is a plain byte store
+ * of 1: the launch reads claimed[ref_slot] only and writes claimed[src_slots] only, so ref_slot inside src_slots_host is
+ * PMN_ERR_ARG, as are a null claimed or emit and a claim_stride below H*W or below a source view's h*w. */
+int pmn_fuse_view_merged(const float *maps, long long slot_stride, int ref_slot, const int *src_slots_host,
+                         const int *src_hw_host, int n_src, const float *mats, int H, int W, float geo_pixel_thres,
+                         float geo_depth_thres, int geo_mask_thres, float photo_thres, unsigned char *masks, float *xyz,
+                         double *depth_avg, int *geo_sum, unsigned char *claimed, long long claim_stride, unsigned char *emit,
+                         void *stream);
+
 /* ABI 19.  The point list of one fused reference view as PLY vertex records, packed on the device (reference eval.py:270-281: the
  * valid pixels' world points and colours, row-major; :283-297: plyfile's vertex element = x, y, z little-endian float32 + red,
  * green, blue uint8 = 15 bytes).  final_mask [H][W] bytes and xyz [H][W][3] are pmn_fuse_view's outputs; image_hwc [H][W][3] is

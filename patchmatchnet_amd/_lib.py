@@ -67,6 +67,8 @@ SIGNATURES = {
     "pmn_stem_f16s_views": [_fp, _i] + [_fp] * 5 + [_i] * 3 + [_s],
     "pmn_differentiable_warping": [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _s],
     "pmn_fuse_view": [_fp, ctypes.c_longlong, _i, _hp, _hp, _i, _fp, _i, _i, _f, _f, _i, _f, _fp, _fp, _fp, _ip, _s],
+    "pmn_fuse_view_merged": [_fp, ctypes.c_longlong, _i, _hp, _hp, _i, _fp, _i, _i, _f, _f, _i, _f, _fp, _fp, _fp, _ip, _fp,
+                             ctypes.c_longlong, _fp, _s],
     "pmn_pack_points": [_fp, _fp, _fp, _i, _i, _i, _fp, ctypes.c_longlong, _fp, _ip, _fp, _s],
     "pmn_pack_points_normals": [_fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _fp, ctypes.c_longlong, _fp, _ip, _fp, _s],
     "pmn_depth_normals": [_fp, _i, _i, _hp, _i, _f, _fp, _s],

@@ -29,6 +29,10 @@ struct FuseArgs {
     int src_slot[PMN_MAX_FUSE_SRC];
     int src_h[PMN_MAX_FUSE_SRC], src_w[PMN_MAX_FUSE_SRC];  // every source map at its OWN size (reference eval.py:236-237 reads
                                                            // each view's file as it is; cv2.remap samples it at that size)
+    // merged fusion only (pmn_fuse_view_merged); behind everything fuse_view_kernel<false> reads
+    unsigned char* claimed;   // slot v = [h_v][w_v] bytes at the start of the slot: 1 = an earlier view's point covers this pixel
+    long long claim_stride;   // bytes between slots (>= h*w of the largest view)
+    unsigned char* emit;      // [H][W]: final && !claimed[ref_slot]
 };
 
 // cv2.remap(src, x, y, INTER_LINEAR), float32 single channel, BORDER_CONSTANT 0
@@ -61,6 +65,24 @@ __device__ __forceinline__ double dot4(const float* __restrict__ m, double a, do
     return fma((double)m[3], d, fma((double)m[2], c, fma((double)m[1], b, (double)m[0] * a)));
 }
 
+// the reference point (rx, ry, rz) of the reference camera frame in source view M (one 64-float block of mats): the float64 pixel
+// (xs, ys) that feeds remap_linear_cv2 after its float32 cast, and the point's depth sz in the source camera
+struct SrcPixel {
+    double xs, ys, sz;
+};
+__device__ __forceinline__ SrcPixel project_to_source(const float* __restrict__ M, double rx, double ry, double rz) {
+    const float* T = M;          // E_src @ inverse(E_ref)   (float32 product, as numpy)
+    const float* Ks = M + 16;    // K_src
+    const double sx = dot4(T, rx, ry, rz, 1.0), sy = dot4(T + 4, rx, ry, rz, 1.0), sz = dot4(T + 8, rx, ry, rz, 1.0);
+    const double kx = dot3(Ks, sx, sy, sz), ky = dot3(Ks + 3, sx, sy, sz), kz = dot3(Ks + 6, sx, sy, sz);
+    return {kx / kz, ky / kz, sz};
+}
+
+// MERGE (pmn_fuse_view_merged): the same arithmetic, plus emit = final && !claimed[ref] and, from every final pixel, a claim on
+// the pixel of each source view that agreed with it -- so that view does not write the same surface point again when its turn
+// comes.  The per-source verdicts are kept as a 32-bit mask (PMN_MAX_FUSE_SRC = 32) and the claims are laid in a second walk
+// over the set bits that recomputes the forward projection: no per-thread array, nothing in scratch.
+template <bool MERGE>
 __global__ __launch_bounds__(256) void fuse_view_kernel(const FuseArgs a) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= a.W || y >= a.H) return;
@@ -76,17 +98,15 @@ __global__ __launch_bounds__(256) void fuse_view_kernel(const FuseArgs a) {
 
     int geo_sum = 0;
     float acc = 0.0f;
+    unsigned int agreed = 0;  // MERGE: bit s = source view s passed the consistency test
     for (int s = 0; s < a.n_src; ++s) {
         const float* M = a.mats + PMN_FUSE_REF_FLOATS + s * PMN_FUSE_SRC_FLOATS;
-        const float* T = M;          // E_src @ inverse(E_ref)   (float32 product, as numpy)
-        const float* Ks = M + 16;    // K_src
         const float* Ksi = M + 25;   // inverse(K_src)
         const float* T2 = M + 34;    // E_ref @ inverse(E_src)
         const float* src = a.maps + (size_t)a.src_slot[s] * a.slot_stride;
         // source 3-D point and pixel
-        const double sx = dot4(T, rx, ry, rz, 1.0), sy = dot4(T + 4, rx, ry, rz, 1.0), sz = dot4(T + 8, rx, ry, rz, 1.0);
-        const double kx = dot3(Ks, sx, sy, sz), ky = dot3(Ks + 3, sx, sy, sz), kz = dot3(Ks + 6, sx, sy, sz);
-        const double xs = kx / kz, ys = ky / kz;
+        const SrcPixel sp = project_to_source(M, rx, ry, rz);
+        const double xs = sp.xs, ys = sp.ys;
         const float sampled = remap_linear_cv2(src, a.src_h[s], a.src_w[s], (float)xs, (float)ys);
         // back-project with the SAMPLED source depth (float64 coordinates, as the reference)
         const double bx = xs * (double)sampled, by = ys * (double)sampled, bz = (double)sampled;
@@ -101,6 +121,7 @@ __global__ __launch_bounds__(256) void fuse_view_kernel(const FuseArgs a) {
         const bool m = dist < (double)a.geo_pixel_thres && rel < a.geo_depth_thres;
         geo_sum += m ? 1 : 0;
         acc = acc + (m ? depth_rep : 0.0f);
+        if (MERGE) agreed |= (m ? 1u : 0u) << s;
     }
     const float total = acc + d_ref;  // float32 sums, as python's sum() over float32 arrays
     const double avg = (double)total / (double)(geo_sum + 1);
@@ -116,15 +137,36 @@ __global__ __launch_bounds__(256) void fuse_view_kernel(const FuseArgs a) {
     a.xyz[3 * p + 0] = (float)dot4(Eri, cx, cy, cz, 1.0);
     a.xyz[3 * p + 1] = (float)dot4(Eri + 4, cx, cy, cz, 1.0);
     a.xyz[3 * p + 2] = (float)dot4(Eri + 8, cx, cy, cz, 1.0);
+    if (MERGE) {
+        a.emit[p] = fin && a.claimed[(size_t)a.ref_slot * a.claim_stride + p] == 0;
+        // Every final pixel lays its claims, claimed itself or not: which bytes get set then depends on the maps, the cameras and
+        // the thresholds alone, never on earlier claims.  This launch reads claimed[ref_slot] only and writes claimed[s], s !=
+        // ref_slot, only (the entry point refuses a reference slot in its own source list); many threads may store the same 1.
+        if (!fin) return;
+        for (int s = 0; s < a.n_src; ++s) {  // (s is wave-uniform: the per-source arguments stay scalar loads)
+            if (!((agreed >> s) & 1u)) continue;
+            const SrcPixel sp = project_to_source(a.mats + PMN_FUSE_REF_FLOATS + s * PMN_FUSE_SRC_FLOATS, rx, ry, rz);
+            const float fx = rintf((float)sp.xs), fy = rintf((float)sp.ys), z = (float)sp.sz;
+            const int h = a.src_h[s], w = a.src_w[s];
+            // (written so that a NaN or infinite coordinate fails the test; the comparison is made before the cast to int)
+            if (!(fx >= 0.0f && fx < (float)w && fy >= 0.0f && fy < (float)h)) continue;
+            const size_t q = (size_t)(int)fy * w + (int)fx;
+            // the source view's OWN depth there must agree with the point's: a depth edge does not claim the pixel on its other side
+            const float d_s = a.maps[(size_t)a.src_slot[s] * a.slot_stride + q];
+            if (!(fabsf(d_s - z) / z < a.geo_depth_thres)) continue;
+            a.claimed[(size_t)a.src_slot[s] * a.claim_stride + q] = 1;
+        }
+    }
 }
 
-extern "C" int pmn_fuse_view(const float* maps, long long slot_stride, int ref_slot, const int* src_slots_host,
-                             const int* src_hw_host, int n_src, const float* mats, int H, int W, float geo_pixel_thres, float geo_depth_thres, int geo_mask_thres,
-                             float photo_thres, unsigned char* masks, float* xyz, double* depth_avg, int* geo_sum,
-                             void* stream) {
+static int fuse_view_launch(const float* maps, long long slot_stride, int ref_slot, const int* src_slots_host, const int* src_hw_host,
+                            int n_src, const float* mats, int H, int W, float geo_pixel_thres, float geo_depth_thres,
+                            int geo_mask_thres, float photo_thres, unsigned char* masks, float* xyz, double* depth_avg, int* geo_sum,
+                            bool merge, unsigned char* claimed, long long claim_stride, unsigned char* emit, void* stream) {
     if (!maps || !mats || !masks || !xyz || (n_src > 0 && !src_slots_host)) return PMN_ERR_ARG;
     if (H < 1 || W < 1 || n_src < 0 || ref_slot < 0 || slot_stride < 2LL * H * W) return PMN_ERR_ARG;
     if (n_src > PMN_MAX_FUSE_SRC) return PMN_ERR_SHAPE;
+    if (merge && (!claimed || !emit || claim_stride < (long long)H * W)) return PMN_ERR_ARG;
     FuseArgs a;
     memset(&a, 0, sizeof(a));
     a.maps = maps;
@@ -142,16 +184,44 @@ extern "C" int pmn_fuse_view(const float* maps, long long slot_stride, int ref_s
     a.geo_pixel_thres = geo_pixel_thres;
     a.geo_depth_thres = geo_depth_thres;
     a.photo_thres = photo_thres;
+    a.claimed = claimed;
+    a.claim_stride = claim_stride;
+    a.emit = emit;
     for (int i = 0; i < n_src; ++i) {
         if (src_slots_host[i] < 0) return PMN_ERR_ARG;
         a.src_slot[i] = src_slots_host[i];
         a.src_h[i] = src_hw_host ? src_hw_host[2 * i] : H;
         a.src_w[i] = src_hw_host ? src_hw_host[2 * i + 1] : W;
         if (a.src_h[i] < 1 || a.src_w[i] < 1 || slot_stride < 2LL * a.src_h[i] * a.src_w[i]) return PMN_ERR_ARG;
+        // merged: the launch reads claimed[ref_slot] and writes claimed[src_slot]; they must be different slots, each large enough
+        if (merge && (a.src_slot[i] == ref_slot || claim_stride < (long long)a.src_h[i] * a.src_w[i])) return PMN_ERR_ARG;
     }
-    PMN_LAUNCH(fuse_view_kernel, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
+    const dim3 grid((W + 31) / 32, (H + 7) / 8);
+    if (merge)
+        PMN_LAUNCH(fuse_view_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else
+        PMN_LAUNCH(fuse_view_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
+}
+
+extern "C" int pmn_fuse_view(const float* maps, long long slot_stride, int ref_slot, const int* src_slots_host,
+                             const int* src_hw_host, int n_src, const float* mats, int H, int W, float geo_pixel_thres, float geo_depth_thres, int geo_mask_thres,
+                             float photo_thres, unsigned char* masks, float* xyz, double* depth_avg, int* geo_sum,
+                             void* stream) {
+    return fuse_view_launch(maps, slot_stride, ref_slot, src_slots_host, src_hw_host, n_src, mats, H, W, geo_pixel_thres,
+                            geo_depth_thres, geo_mask_thres, photo_thres, masks, xyz, depth_avg, geo_sum, false, nullptr, 0, nullptr,
+                            stream);
+}
+
+extern "C" int pmn_fuse_view_merged(const float* maps, long long slot_stride, int ref_slot, const int* src_slots_host,
+                                    const int* src_hw_host, int n_src, const float* mats, int H, int W, float geo_pixel_thres,
+                                    float geo_depth_thres, int geo_mask_thres, float photo_thres, unsigned char* masks, float* xyz,
+                                    double* depth_avg, int* geo_sum, unsigned char* claimed, long long claim_stride,
+                                    unsigned char* emit, void* stream) {
+    return fuse_view_launch(maps, slot_stride, ref_slot, src_slots_host, src_hw_host, n_src, mats, H, W, geo_pixel_thres,
+                            geo_depth_thres, geo_mask_thres, photo_thres, masks, xyz, depth_avg, geo_sum, true, claimed, claim_stride,
+                            emit, stream);
 }
 
 // ---- point packing (round 5) --------------------------------------------------------------------------------------------

@@ -39,10 +39,36 @@ def camera_block(K_ref: np.ndarray, E_ref: np.ndarray, srcs: Sequence[Tuple[np.n
     return out
 
 
+def _slot_sizes(maps, slot_of, sizes):
+    """``sizes`` by view id -> by slot (None: every slot is the [2,H,W] of ``maps``)."""
+    if sizes is None:
+        return None
+    slot_sizes = [(1, 1)] * maps.shape[0]
+    for vid, sl in slot_of.items():
+        slot_sizes[sl] = tuple(sizes[vid])
+    return slot_sizes
+
+
+def _new_claims(maps, slot_sizes):
+    """The zeroed ``claimed`` buffer of a merged fusion: one byte per pixel of every map slot (ops.fuse_view_merged)."""
+    room = maps.shape[2] * maps.shape[3] if slot_sizes is None else max(h * w for h, w in slot_sizes)
+    return torch.zeros((maps.shape[0], room), dtype=torch.uint8, device=maps.device)
+
+
+def _fuse_one(maps, ref_slot, src_slots, mats, geo_pixel_thres, geo_depth_thres, geo_mask_thres, photo_thres, slot_sizes, claimed):
+    """One reference view's launch: (masks, xyz, emit); emit is None without ``claimed`` (the points are the final pixels)."""
+    if claimed is None:
+        m, xyz, _, _ = ops.fuse_view(maps, ref_slot, src_slots, mats, geo_pixel_thres, geo_depth_thres, geo_mask_thres, photo_thres,
+                                     sizes=slot_sizes)
+        return m, xyz, None
+    return ops.fuse_view_merged(maps, ref_slot, src_slots, mats, geo_pixel_thres, geo_depth_thres, geo_mask_thres, photo_thres,
+                                claimed, sizes=slot_sizes)
+
+
 def fuse_views(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[int, Dict], images: Dict[int, np.ndarray],
                pairs: List[Tuple[int, List[int]]], geo_pixel_thres: float, geo_depth_thres: float, geo_mask_thres: int,
                photo_thres: float, sizes: Optional[Dict[int, Tuple[int, int]]] = None, pool=None, on_view=None,
-               as_records: bool = False):
+               as_records: bool = False, merge: bool = False):
     """Fuses the reference views listed in ``pairs`` (this rank's share of a scan).
 
     maps [V,2,H,W] device float32 (slot_of[view id] -> slot) -- or, for a scan whose views differ in size, [V,F] flat slots with
@@ -55,24 +81,26 @@ def fuse_views(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[int, Dict
     as soon as a view's masks are on the host, on the thread that finished the view (eval.py writes the mask PNGs there, while
     later views are still being fused).  ``as_records``: returns ([PLY vertex records of every view], None, masks) instead -- the
     records are packed on the finishing threads and ``write_ply_records`` streams them to the file, so a scan's points (1.4 GB for
-    49 fully consistent 1600x1200 views) are never concatenated or copied again on the launch thread."""
+    49 fully consistent 1600x1200 views) are never concatenated or copied again on the launch thread.
+    ``merge``: each surface point once (pmn_fuse_view_merged) -- a view keeps only the final pixels that no
+    view before it in ``pairs`` has claimed; the points that remain, their order and the returned masks (photo, geo, final) are
+    those of a call without it."""
     if not maps.is_cuda:
         raise PmnError("fusion runs on a ROCm GPU only (pmn_fuse_view); there is no CPU fallback")
-    slot_sizes = None
-    if sizes is not None:
-        slot_sizes = [(1, 1)] * maps.shape[0]
-        for vid, sl in slot_of.items():
-            slot_sizes[sl] = tuple(sizes[vid])
+    slot_sizes = _slot_sizes(maps, slot_of, sizes)
+    claimed = _new_claims(maps, slot_sizes) if merge else None
 
-    def finish(ref, m, xyz):
+    def finish(ref, m, xyz, emit=None):
         """Host half of one reference view: masks and the kept points leave the device, colours are picked from the reference image
         (eval.py:270-281).  Runs on ``pool`` when one is given: the copies and numpy's boolean indexing release the GIL, and at
         50-60 ms per 1600x1200 view this half, not the kernel, is what a scan's fusion takes."""
         with torch.cuda.device(m.device):  # a pool thread starts on device 0, whatever the rank's device is
-            final = m[2].bool()
-            v = xyz[final].cpu().numpy()
+            keep = (m[2] if emit is None else emit).bool()
+            v = xyz[keep].cpu().numpy()
             mk = m.cpu().numpy()
+            keep = mk[2] if emit is None else keep.cpu().numpy()
         mk = mk.view(bool) if mk.dtype == np.uint8 else mk.astype(bool)  # the kernel writes 0 / 1 bytes
+        keep = keep.view(bool) if keep.dtype == np.uint8 else keep.astype(bool)
         img = images[ref]
         if hasattr(img, "result"):  # a concurrent.futures.Future: eval.py decodes the reference images on a thread pool
             img = img.result()
@@ -80,9 +108,9 @@ def fuse_views(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[int, Dict
         if img.dtype == np.uint8:
             # the decoded bytes ARE the colours: the reference's float32 k / 255.0 (datasets/data_io.py:45) then (color * 255)
             # .astype(uint8) (eval.py:275) returns k for every byte value (tests/test_io_and_dist.py) -- no float image needed
-            c = img[mk[2]]
+            c = img[keep]
         else:
-            c = (img[mk[2]] * 255).astype(np.uint8)
+            c = (img[keep] * 255).astype(np.uint8)
         if on_view is not None:
             on_view(ref, (mk[0], mk[1], mk[2]))
         if as_records:
@@ -94,9 +122,9 @@ def fuse_views(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[int, Dict
         block = camera_block(cams[ref]["intrinsics"], cams[ref]["extrinsics"],
                              [(cams[s]["intrinsics"], cams[s]["extrinsics"]) for s in srcs])
         mats = torch.from_numpy(block).to(maps.device)
-        m, xyz, _, _ = ops.fuse_view(maps, slot_of[ref], [slot_of[s] for s in srcs], mats, geo_pixel_thres, geo_depth_thres,
-                                     geo_mask_thres, photo_thres, sizes=slot_sizes)
-        pending.append((ref, pool.submit(finish, ref, m, xyz) if pool is not None else finish(ref, m, xyz)))
+        m, xyz, emit = _fuse_one(maps, slot_of[ref], [slot_of[s] for s in srcs], mats, geo_pixel_thres, geo_depth_thres,
+                                 geo_mask_thres, photo_thres, slot_sizes, claimed)
+        pending.append((ref, pool.submit(finish, ref, m, xyz, emit) if pool is not None else finish(ref, m, xyz, emit)))
     verts, cols, masks = [], [], {}
     for ref, res in pending:
         v, c, mk = res.result() if hasattr(res, "result") else res
@@ -111,9 +139,9 @@ def fuse_views(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[int, Dict
 
 
 def fuse_scan(views: Dict[int, Dict], pairs: List[Tuple[int, List[int]]], geo_pixel_thres: float, geo_depth_thres: float,
-              geo_mask_thres: int, photo_thres: float, device: torch.device):
+              geo_mask_thres: int, photo_thres: float, device: torch.device, merge: bool = False):
     """Whole-scan convenience wrapper: views[id] = {depth [H,W], confidence [H,W], intrinsics, extrinsics, image [H,W,3]}
-    (numpy or torch) -> (vertices, colors, masks) as ``fuse_views``; reference eval.py:193-281."""
+    (numpy or torch) -> (vertices, colors, masks) as ``fuse_views``; reference eval.py:193-281.  ``merge``: see ``fuse_views``."""
     ids = sorted(views)
     sizes = {v: tuple(np.shape(views[v]["depth"])) for v in ids}
     flat = max(2 * h * w for h, w in sizes.values())
@@ -127,7 +155,7 @@ def fuse_scan(views: Dict[int, Dict], pairs: List[Tuple[int, List[int]]], geo_pi
                 "extrinsics": np.asarray(views[v]["extrinsics"], np.float32)} for v in ids}
     images = {r: views[r]["image"] for r, _ in pairs}
     return fuse_views(maps, {v: i for i, v in enumerate(ids)}, cams, images, pairs, geo_pixel_thres, geo_depth_thres,
-                      geo_mask_thres, photo_thres, sizes=sizes)
+                      geo_mask_thres, photo_thres, sizes=sizes, merge=merge)
 
 
 PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
@@ -193,7 +221,7 @@ def write_ply_records(filename: str, chunks, header: bool = True) -> int:
 def fuse_views_packed(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[int, Dict], images: Dict[int, torch.Tensor],
                       pairs: List[Tuple[int, List[int]]], geo_pixel_thres: float, geo_depth_thres: float, geo_mask_thres: int,
                       photo_thres: float, packer: "ops.PointPacker", sizes: Optional[Dict[int, Tuple[int, int]]] = None,
-                      normals: bool = False, normals_radius: int = 2, normals_depth_thres: float = 0.01):
+                      normals: bool = False, normals_radius: int = 2, normals_depth_thres: float = 0.01, merge: bool = False):
     """The device half of ``fuse_views`` and nothing else: per reference view of ``pairs`` one pmn_fuse_view launch and one
     pmn_pack_points (three small launches) on the CURRENT stream -- the kept points become PLY vertex records appended to
     ``packer.records`` in pair-file / row-major order (reference eval.py:270-297), nothing synchronises, nothing leaves the device.
@@ -202,20 +230,21 @@ def fuse_views_packed(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[in
     can queue its download behind the launches.  After the last view ``packer.counts()`` holds every view's number of points.
     ``normals`` (with a ``PointPacker(normals=True)``): one more launch per view, pmn_depth_normals on the view's ESTIMATED depth map
     in ``maps`` (not the averaged depth) with its intrinsics; the records carry inverse(E_ref)[:3,:3] . normal.
-    The masks and the points are those of a call without normals."""
+    The masks and the points are those of a call without normals.
+    ``merge``: each surface point once (pmn_fuse_view_merged): the records of a view are those of its final
+    pixels that no earlier view of ``pairs`` has claimed -- a subset of the unmerged records, in their order, byte for byte; the
+    yielded masks stay photo / geo / final.  The claims live in a buffer zeroed here, on the current stream, once per call."""
     if not maps.is_cuda:
         raise PmnError("fusion runs on a ROCm GPU only (pmn_fuse_view); there is no CPU fallback")
-    slot_sizes = None
-    if sizes is not None:
-        slot_sizes = [(1, 1)] * maps.shape[0]
-        for vid, sl in slot_of.items():
-            slot_sizes[sl] = tuple(sizes[vid])
+    slot_sizes = _slot_sizes(maps, slot_of, sizes)
+    claimed = _new_claims(maps, slot_sizes) if merge else None
     for ref, srcs in pairs:
         block = camera_block(cams[ref]["intrinsics"], cams[ref]["extrinsics"],
                              [(cams[s]["intrinsics"], cams[s]["extrinsics"]) for s in srcs])
         mats = torch.from_numpy(block).to(maps.device)
-        m, xyz, _, _ = ops.fuse_view(maps, slot_of[ref], [slot_of[s] for s in srcs], mats, geo_pixel_thres, geo_depth_thres,
-                                     geo_mask_thres, photo_thres, sizes=slot_sizes)
+        m, xyz, emit = _fuse_one(maps, slot_of[ref], [slot_of[s] for s in srcs], mats, geo_pixel_thres, geo_depth_thres,
+                                 geo_mask_thres, photo_thres, slot_sizes, claimed)
+        keep = m[2] if emit is None else emit
         if normals:
             sl = slot_of[ref]
             if slot_sizes is None:
@@ -224,9 +253,9 @@ def fuse_views_packed(maps: torch.Tensor, slot_of: Dict[int, int], cams: Dict[in
                 h, w = slot_sizes[sl]
                 depth = maps[sl, :h * w].view(h, w)
             nrm = ops.depth_normals(depth, cams[ref]["intrinsics"], normals_radius, normals_depth_thres)
-            packer.append(m[2], xyz, images[ref], nrm, mats[18:34].view(4, 4))  # the block camera_block put there: inverse(E_ref)
+            packer.append(keep, xyz, images[ref], nrm, mats[18:34].view(4, 4))  # the block camera_block put there: inverse(E_ref)
         else:
-            packer.append(m[2], xyz, images[ref])
+            packer.append(keep, xyz, images[ref])
         yield ref, m
 
 

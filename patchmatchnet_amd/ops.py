@@ -961,6 +961,33 @@ def fuse_view(maps: torch.Tensor, ref_slot: int, src_slots: Sequence[int], mats:
     start (F >= 2*h*w of the largest view).  mats = fusion.camera_block(...) (device float32).  Returns (masks [3,H,W] uint8 =
     photo / geo / final, xyz [H,W,3] float32 world points, depth_avg [H,W] float64 or None, geo_sum [H,W] int32 or None), H x W
     = the reference view's size."""
+    masks, xyz, davg, gsum, _ = _fuse_view(maps, ref_slot, src_slots, mats, geo_pixel_thres, geo_depth_thres, geo_mask_thres,
+                                           photo_thres, want_depth_avg, want_geo_sum, sizes, None)
+    return masks, xyz, davg, gsum
+
+
+def fuse_view_merged(maps: torch.Tensor, ref_slot: int, src_slots: Sequence[int], mats: torch.Tensor, geo_pixel_thres: float,
+                     geo_depth_thres: float, geo_mask_thres: int, photo_thres: float, claimed: torch.Tensor,
+                     sizes: Optional[Sequence[Tuple[int, int]]] = None):
+    """pmn_fuse_view_merged: ``fuse_view`` that writes each surface point once.  ``claimed``: device uint8
+    [V,S], contiguous, S >= h*w of the largest view -- slot v = view v's map at its own size, 1 = covered by a point of a view fused
+    earlier; zero it before a scan's first view and fuse the scan's views on one stream.  Returns (masks [3,H,W] and xyz [H,W,3]:
+    ``fuse_view``'s, bit for bit; emit [H,W] uint8 = final && !claimed[ref_slot]: the pixels whose points belong in the file).
+    The launch sets claimed[s] for the source views s that agreed with a final pixel; ``ref_slot`` must not be in ``src_slots``."""
+    if not isinstance(claimed, torch.Tensor) or claimed.dtype != torch.uint8 or claimed.dim() != 2 or not claimed.is_contiguous():
+        raise PmnError("fuse_view_merged: claimed must be a contiguous uint8 tensor [V,S], one slot per map slot")
+    if not isinstance(maps, torch.Tensor) or claimed.device != maps.device:
+        raise PmnError("fuse_view_merged: claimed must be on the maps' device (no CPU fallback)")
+    if ref_slot in src_slots:
+        raise PmnError("fuse_view_merged: the reference slot is in its own source list")
+    masks, xyz, _, _, emit = _fuse_view(maps, ref_slot, src_slots, mats, geo_pixel_thres, geo_depth_thres, geo_mask_thres,
+                                        photo_thres, False, False, sizes, claimed)
+    return masks, xyz, emit
+
+
+def _fuse_view(maps, ref_slot, src_slots, mats, geo_pixel_thres, geo_depth_thres, geo_mask_thres, photo_thres, want_depth_avg,
+               want_geo_sum, sizes, claimed):
+    """The checks and the call of ``fuse_view`` (claimed None) and ``fuse_view_merged``."""
     _dev(maps, "maps")
     _dev(mats, "mats")
     if sizes is None:
@@ -982,6 +1009,8 @@ def fuse_view(maps: torch.Tensor, ref_slot: int, src_slots: Sequence[int], mats:
         raise PmnError("fuse_view: slot out of range")
     if mats.numel() != 48 + 64 * n:
         raise PmnError("fuse_view: mats must hold 48 + 64 * n_src floats (fusion.camera_block)")
+    if claimed is not None and (claimed.shape[0] != V or any(h * w > claimed.shape[1] for h, w in sizes)):
+        raise PmnError("fuse_view_merged: claimed must have one slot per map slot, each with room for the largest view's h*w bytes")
     H, W = sizes[ref_slot]
     slots, slots_p = _host_i32(np.asarray(list(src_slots) if n else [0], np.int32), max(n, 1), "src_slots")
     hw, hw_p = _host_i32(np.asarray([x for s in src_slots for x in sizes[s]] if n else [0, 0], np.int32), max(2 * n, 2), "src_hw")
@@ -989,13 +1018,22 @@ def fuse_view(maps: torch.Tensor, ref_slot: int, src_slots: Sequence[int], mats:
     xyz = torch.empty((H, W, 3), dtype=torch.float32, device=maps.device)
     davg = torch.empty((H, W), dtype=torch.float64, device=maps.device) if want_depth_avg else None
     gsum = torch.empty((H, W), dtype=torch.int32, device=maps.device) if want_geo_sum else None
+    emit = None
     with torch.cuda.device(maps.device):
-        check(_lib.lib().pmn_fuse_view(maps.data_ptr(), int(stride), int(ref_slot), slots_p, hw_p, n, mats.data_ptr(), H, W,
-                                       float(geo_pixel_thres), float(geo_depth_thres), int(geo_mask_thres), float(photo_thres),
-                                       masks.data_ptr(), xyz.data_ptr(), _ptr(davg), _ptr(gsum), _stream(maps)),
-              "pmn_fuse_view")
+        if claimed is None:
+            check(_lib.lib().pmn_fuse_view(maps.data_ptr(), int(stride), int(ref_slot), slots_p, hw_p, n, mats.data_ptr(), H, W,
+                                           float(geo_pixel_thres), float(geo_depth_thres), int(geo_mask_thres), float(photo_thres),
+                                           masks.data_ptr(), xyz.data_ptr(), _ptr(davg), _ptr(gsum), _stream(maps)),
+                  "pmn_fuse_view")
+        else:
+            emit = torch.empty((H, W), dtype=torch.uint8, device=maps.device)
+            check(_lib.lib().pmn_fuse_view_merged(maps.data_ptr(), int(stride), int(ref_slot), slots_p, hw_p, n, mats.data_ptr(), H, W,
+                                                  float(geo_pixel_thres), float(geo_depth_thres), int(geo_mask_thres),
+                                                  float(photo_thres), masks.data_ptr(), xyz.data_ptr(), _ptr(davg), _ptr(gsum),
+                                                  claimed.data_ptr(), int(claimed.shape[1]), emit.data_ptr(), _stream(maps)),
+                  "pmn_fuse_view_merged")
     del slots, hw
-    return masks, xyz, davg, gsum
+    return masks, xyz, davg, gsum, emit
 
 
 def depth_normals(depth: torch.Tensor, intrinsics, radius: int = 2, rel_thres: float = 0.01) -> torch.Tensor:
