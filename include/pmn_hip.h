@@ -758,6 +758,29 @@ int pmn_undistort_image(const unsigned char *src, int Hs, int Ws, int channels, 
                         const double *dst_pinhole_host, int Hd, int Wd, unsigned char *dst, unsigned char *valid, double *coords,
                         void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  The two searches behind outlier removal on a point cloud
+ * (clean_cloud.py, pointcloud.statistical_outliers / radius_outliers; the reference has no counterpart).  Both
+ * take pmn_nn_distance's grid (first six arguments), query, order and n_from, walk the grid as pmn_nn_distance walks it, and keep its
+ * distance contract: squares dx*dx + dy*dy + dz*dz of the float32 coordinates widened to float64, x, y, z order, no contraction.
+ * same_cloud != 0 says "query i IS grid point i" (n_from == n_to, else PMN_ERR_ARG): a query is never reported as, or counted among,
+ * its own neighbours.  The exclusion is by index, never by distance: a duplicate at distance 0 is a neighbour.
+ *
+ * pmn_knn_distance: the k nearest grid points of every query, 1 <= k <= 32, max_dist positive and finite (else PMN_ERR_ARG).  Outputs,
+ * each may be NULL: d2 [n_from][k] float64, the squared distances ascending; index [n_from][k] int32, their positions IN THE SORTED
+ * ORDER, ties at equal d2 to the lower sorted index whatever the grid's cell; mean [n_from] float64 = (sum_j sqrt(d2_j)) / k, added
+ * smallest first in float64.  A slot for which no point lies nearer than max_dist (d < max_dist, as pmn_nn_distance) holds
+ * max_dist * max_dist and index -1, and enters the mean as max_dist itself.  A search ends when the walk's reach, slack included,
+ * passes the k-th best.  One lane per query; the k-best list lives in registers (kernels specialised on a capacity of 8, 16 or 32).
+ *
+ * pmn_radius_count: count [n_from] int32 = the number of grid points with sqrt(d2) <= radius (decided on the rooted value), radius
+ * finite and >= 0.  One launch each of ceil(n_from / 64) one-wave workgroups. */
+int pmn_knn_distance(const float *to_xyz, const long long *to_keys, long long n_to, const double *origin_host, double cell,
+                     const int *dims_host, const float *query, const int *order, long long n_from, int k, double max_dist,
+                     int same_cloud, double *d2, int *index, double *mean, void *stream);
+int pmn_radius_count(const float *to_xyz, const long long *to_keys, long long n_to, const double *origin_host, double cell,
+                     const int *dims_host, const float *query, const int *order, long long n_from, double radius, int same_cloud,
+                     int *count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

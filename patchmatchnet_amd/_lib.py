@@ -109,6 +109,10 @@ SIGNATURES = {
     "pmn_mesh_face_samples": [_fp, _i, _ip, _i, ctypes.c_double, ctypes.c_ulonglong, _ip, _ip, _s],
     "pmn_mesh_sample": [_fp, _i, _ip, _i, _ip, _ip, ctypes.c_longlong, ctypes.c_ulonglong, _fp, _ip, _ip, _s],
     "pmn_undistort_image": [_fp, _i, _i, _i, _i, _hp, _hp, _i, _i, _fp, _fp, _fp, _s],
+    "pmn_knn_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, _i, ctypes.c_double, _i,
+                         _fp, _ip, _fp, _s],
+    "pmn_radius_count": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, ctypes.c_double, _i, _ip,
+                         _s],
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)

@@ -1,5 +1,5 @@
-// pc_grid.hpp -- the uniform grid over sorted points and the nearest-neighbour shell walk over it, shared by pointcloud.hip (the DTU
-// score) and registration.hip (ICP).  Layout, arithmetic and the slack of the bounds: the comment at the top of pointcloud.hip.
+// pc_grid.hpp -- the uniform grid over sorted points and the shell walk over it (nearest, k nearest, count within a radius), shared by
+// pointcloud.hip (the DTU score, cloud cleaning) and registration.hip (ICP).  Layout, arithmetic and the slack of the bounds: the comment at the top of pointcloud.hip.
 #pragma once
 #include <cmath>
 
@@ -49,30 +49,39 @@ __device__ __forceinline__ double pc_dist2(const float* __restrict__ p, double q
     return dx * dx + dy * dy + dz * dz;
 }
 
+// ---- the shell walk: ONE rule over an accumulator ------------------------------------------------------------------------------------
+// An accumulator is offered (d2, sorted index) for every candidate the walk visits and tells the walk what can no longer matter:
+//   bool beyond(double g2) const   true when no candidate at squared distance >= g2 can change the result;
+//   void offer(double d2, int i)   one candidate.
+// g2 is always a LOWER bound (a gap to a cell, a row or a shell, shrunk by the slack), so beyond() may only err towards false.
+// The nearest neighbour (NnBest), the k nearest (KBest) and the count within a radius (RadiusCount) are its three instances.
+
 struct NnBest {
     double d2;
     int idx;
+    __device__ __forceinline__ bool beyond(double g2) const { return g2 >= d2; }
+    __device__ __forceinline__ void offer(double c, int i) {
+        if (c < d2) {
+            d2 = c;
+            idx = i;
+        }
+    }
 };
 
 // the points of cells [x0, x1] x {y} x {z} (already inside the grid)
-__device__ __forceinline__ void nn_scan_row(const GridArgs& g, int x0, int x1, int y, int z, double qx, double qy, double qz, NnBest& b) {
+template <class Acc>
+__device__ __forceinline__ void pc_scan_row(const GridArgs& g, int x0, int x1, int y, int z, double qx, double qy, double qz, Acc& b) {
     const long long base = ((long long)z * g.dims[1] + y) * g.dims[0];
     const int i0 = pc_lower_bound(g.keys, 0, g.n, base + x0);
     if (i0 >= g.n || g.keys[i0] > base + x1) return;
     const int i1 = pc_lower_bound(g.keys, i0 + 1, g.n, base + x1 + 1);
-    for (int i = i0; i < i1; ++i) {
-        const double d2 = pc_dist2(g.xyz + (size_t)i * 3, qx, qy, qz);
-        if (d2 < b.d2) {
-            b.d2 = d2;
-            b.idx = i;
-        }
-    }
+    for (int i = i0; i < i1; ++i) b.offer(pc_dist2(g.xyz + (size_t)i * 3, qx, qy, qz), i);
 }
 
-// The nearest grid point of a query at (qx, qy, qz), any position: the query's cell, then shells of growing Chebyshev radius, until the
-// best squared distance is no larger than the distance to the nearest face of the next shell or the shell lies beyond max_dist.
-// idx = -1 and d2 = max_dist * max_dist where no point is nearer than max_dist.
-__device__ __forceinline__ NnBest nn_search(const GridArgs& g, double qx, double qy, double qz, double max_dist) {
+// The walk of a query at (qx, qy, qz), any position: the query's cell, then shells of growing Chebyshev radius, until everything not
+// yet visited is beyond the accumulator's bound (the distance to the nearest face of the next shell) or the grid is exhausted.
+template <class Acc>
+__device__ __forceinline__ void pc_walk(const GridArgs& g, double qx, double qy, double qz, Acc& b) {
 #pragma clang fp contract(off)
     const int cx = pc_cell(qx, g.origin[0], g.cell), cy = pc_cell(qy, g.origin[1], g.cell), cz = pc_cell(qz, g.origin[2], g.cell);
     const int nx = g.dims[0], ny = g.dims[1], nz = g.dims[2];
@@ -86,43 +95,108 @@ __device__ __forceinline__ NnBest nn_search(const GridArgs& g, double qx, double
                  fz = qz - (g.origin[2] + (double)cz * g.cell);
     double face = fmin(fmin(fmin(fx, g.cell - fx), fmin(fy, g.cell - fy)), fmin(fz, g.cell - fz));
     face = fmax(face - g.cell * PMN_PC_SLACK, 0.0);
-    NnBest b;
-    b.d2 = max_dist * max_dist;  // a point at exactly max_dist or beyond never wins: the result is then max_dist itself
-    b.idx = -1;
     const int rmax = max(max(max(cx, nx - 1 - cx), max(cy, ny - 1 - cy)), max(cz, nz - 1 - cz));  // last shell that touches the grid
     for (; r <= rmax; ++r) {
         // everything not yet visited is at least (r - 1) * cell + face away
         if (r > 0) {
             const double reach = (double)(r - 1) * g.cell + face;
-            if (reach * reach >= b.d2) break;
+            if (b.beyond(reach * reach)) break;
         }
         const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
         const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
         for (int z = z0; z <= z1; ++z) {
             const double gz = pc_gap(qz, g.origin[2], g.cell, z, z);
-            if (gz * gz >= b.d2) continue;
+            if (b.beyond(gz * gz)) continue;
             const bool zface = z == cz - r || z == cz + r;
             for (int y = y0; y <= y1; ++y) {
                 const double gy = pc_gap(qy, g.origin[1], g.cell, y, y);
                 const double gyz = gy * gy + gz * gz;
-                if (gyz >= b.d2) continue;
+                if (b.beyond(gyz)) continue;
                 if (zface || y == cy - r || y == cy + r) {
-                    if (x0 <= x1) nn_scan_row(g, x0, x1, y, z, qx, qy, qz, b);
+                    if (x0 <= x1) pc_scan_row(g, x0, x1, y, z, qx, qy, qz, b);
                 } else {  // interior (y, z) of the shell: only its two end cells are new
                     if (cx - r >= 0 && cx - r < nx) {
                         const double gx = pc_gap(qx, g.origin[0], g.cell, cx - r, cx - r);
-                        if (gx * gx + gyz < b.d2) nn_scan_row(g, cx - r, cx - r, y, z, qx, qy, qz, b);
+                        if (!b.beyond(gx * gx + gyz)) pc_scan_row(g, cx - r, cx - r, y, z, qx, qy, qz, b);
                     }
                     if (cx + r >= 0 && cx + r < nx) {
                         const double gx = pc_gap(qx, g.origin[0], g.cell, cx + r, cx + r);
-                        if (gx * gx + gyz < b.d2) nn_scan_row(g, cx + r, cx + r, y, z, qx, qy, qz, b);
+                        if (!b.beyond(gx * gx + gyz)) pc_scan_row(g, cx + r, cx + r, y, z, qx, qy, qz, b);
                     }
                 }
             }
         }
     }
+}
+
+// The nearest grid point of a query: the walk's one-best instance.  The first candidate met wins among equals (the bound is then
+// ">= best").  idx = -1 and d2 = max_dist * max_dist where no point is nearer than max_dist.
+__device__ __forceinline__ NnBest nn_search(const GridArgs& g, double qx, double qy, double qz, double max_dist) {
+#pragma clang fp contract(off)
+    NnBest b;
+    b.d2 = max_dist * max_dist;  // a point at exactly max_dist or beyond never wins: the result is then max_dist itself
+    b.idx = -1;
+    pc_walk(g, qx, qy, qz, b);
     return b;
 }
+
+// The K nearest, K <= CAP, in registers: CAP (d2, idx) pairs kept in ascending (d2, idx) order and touched ONLY through indices the
+// compiler knows (every loop below is fully unrolled), because a per-lane array indexed by a run-time value lives in scratch memory.
+// The list is right-aligned: slots [0, CAP - k) hold a sentinel below every candidate (d2 = -1) that never moves, slots
+// [CAP - k, CAP) the k best so far, so that the k-th best -- the bound -- is always slot CAP - 1 whatever k is.  Empty slots hold
+// the cap (max_dist^2, index -1); a candidate enters only with d2 < cap.  Order is (d2, index) lexicographic: among equal squares
+// the lower sorted index wins whatever the visiting order, hence the bound is "> k-th best" (an equal candidate in a cell not yet
+// visited may still displace a higher index) once the list is full, and ">= cap" before.
+template <int CAP>
+struct KBest {
+    double d2[CAP];
+    int idx[CAP];
+    int self;  // sorted index never reported (the query itself under same_cloud), or -1
+
+    __device__ __forceinline__ void init(int k, double cap, int self_) {
+        self = self_;
+#pragma unroll
+        for (int s = 0; s < CAP; ++s) {
+            const bool live = s >= CAP - k;
+            d2[s] = live ? cap : -1.0;
+            idx[s] = live ? -1 : -2;
+        }
+    }
+    __device__ __forceinline__ bool beyond(double g2) const { return g2 > d2[CAP - 1] || (idx[CAP - 1] < 0 && g2 >= d2[CAP - 1]); }
+    __device__ __forceinline__ void offer(double c, int i) {
+        const double kth = d2[CAP - 1];
+        const int kidx = idx[CAP - 1];
+        if (!(c < kth || (c == kth && kidx >= 0 && i < kidx)) || i == self) return;
+        // the candidate replaces the k-th best and sinks to its place: one pass of compare-and-swap, all indices static
+        d2[CAP - 1] = c;
+        idx[CAP - 1] = i;
+        bool moving = true;
+#pragma unroll
+        for (int s = CAP - 1; s > 0; --s) {
+            moving = moving && (c < d2[s - 1] || (c == d2[s - 1] && i < idx[s - 1]));
+            d2[s] = moving ? d2[s - 1] : d2[s];
+            idx[s] = moving ? idx[s - 1] : idx[s];
+            d2[s - 1] = moving ? c : d2[s - 1];
+            idx[s - 1] = moving ? i : idx[s - 1];
+        }
+    }
+};
+
+// The number of grid points with sqrt(d2) <= radius (decided on the rooted value, as reduce_round_kernel decides "within dst").
+// The walk's bound is on squares and constant: radius^2 widened by far more than the last-bit difference between the two tests.
+struct RadiusCount {
+    double radius, bound;
+    int self, count;
+    __device__ __forceinline__ void init(double r, int self_) {
+#pragma clang fp contract(off)
+        radius = r;
+        bound = r * r * (1.0 + 1.0 / 1099511627776.0) + 2.2250738585072014e-308;
+        self = self_;
+        count = 0;
+    }
+    __device__ __forceinline__ bool beyond(double g2) const { return g2 > bound; }
+    __device__ __forceinline__ void offer(double c, int i) { count += (i != self && sqrt(c) <= radius) ? 1 : 0; }
+};
 
 static inline int grid_args(GridArgs& g, const float* xyz, const long long* keys, long long n, const double* origin_host, double cell,
                             const int* dims_host) {

@@ -1,5 +1,6 @@
 // pointcloud.hip -- the two searches behind the DTU score of a fused point cloud (reference evaluations/dtu/reducePts_haa.m and
-// MaxDistCP.m, which use MATLAB's KDTreeSearcher on the CPU): nearest-neighbour distance and one round of the greedy reduction.
+// MaxDistCP.m, which use MATLAB's KDTreeSearcher on the CPU): nearest-neighbour distance and one round of the greedy reduction; and
+// the two searches behind cloud cleaning (clean_cloud.py): the k nearest neighbours and the number of points within a radius.
 //
 // Spatial index (built by the caller, patchmatchnet_amd/pointcloud.py): a uniform grid over SORTED points.  A point's cell is
 // c = floor((double(p) - origin) / cell) per axis, 0 <= c < dims, its key (c.z * dims.y + c.y) * dims.x + c.x (< 2^63); the points
@@ -103,6 +104,114 @@ __global__ __launch_bounds__(256) void reduce_round_kernel(ReduceArgs a) {
     }
     const int cnt = __popcll(__ballot(undecided));  // one atomic per wave
     if ((threadIdx.x & 63) == 0 && cnt > 0) atomicAdd(a.counter, (unsigned int)cnt);
+}
+
+// ---- pmn_knn_distance / pmn_radius_count ------------------------------------------------------------------------------------------
+// The same walk with the k-best and the counting accumulator of pc_grid.hpp, launched as nn_distance_kernel is and for its reasons:
+// one lane per query, one wave per workgroup, queries in cell order.  The k-best list is register-resident, so the kernel is
+// specialised on its capacity (8 / 16 / 32, k rounded up): 3 VGPRs per slot, and a small k does not pay for 32 slots.
+struct KnnArgs {
+    GridArgs g;
+    const float* query;  // [n_from][3]
+    const int* order;    // [n_from] or null (identity)
+    int n_from;
+    int k;
+    int same_cloud;      // query i IS grid point i
+    double max_dist;
+    double* d2;          // [n_from][k] or null
+    int* index;          // [n_from][k] or null
+    double* mean;        // [n_from] or null
+};
+
+template <int CAP>
+__global__ __launch_bounds__(64) void knn_distance_kernel(KnnArgs a) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n_from) return;
+    const int q = a.order ? a.order[t] : t;
+    const double qx = (double)a.query[(size_t)q * 3], qy = (double)a.query[(size_t)q * 3 + 1], qz = (double)a.query[(size_t)q * 3 + 2];
+    KBest<CAP> b;
+    b.init(a.k, a.max_dist * a.max_dist, a.same_cloud ? q : -1);
+    pc_walk(a.g, qx, qy, qz, b);
+    const size_t row = (size_t)q * a.k;
+    double sum = 0.0;
+#pragma unroll
+    for (int s = 0; s < CAP; ++s) {  // slot s is rank j = s - (CAP - k): static register, run-time address
+        const int j = s - (CAP - a.k);
+        if (j < 0) continue;
+        sum += b.idx[s] < 0 ? a.max_dist : sqrt(b.d2[s]);  // smallest first
+        if (a.d2) a.d2[row + j] = b.d2[s];
+        if (a.index) a.index[row + j] = b.idx[s];
+    }
+    if (a.mean) a.mean[q] = sum / (double)a.k;
+}
+
+struct RadiusArgs {
+    GridArgs g;
+    const float* query;
+    const int* order;
+    int n_from;
+    int same_cloud;
+    double radius;
+    int* count;  // [n_from]
+};
+
+__global__ __launch_bounds__(64) void radius_count_kernel(RadiusArgs a) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n_from) return;
+    const int q = a.order ? a.order[t] : t;
+    const double qx = (double)a.query[(size_t)q * 3], qy = (double)a.query[(size_t)q * 3 + 1], qz = (double)a.query[(size_t)q * 3 + 2];
+    RadiusCount b;
+    b.init(a.radius, a.same_cloud ? q : -1);
+    pc_walk(a.g, qx, qy, qz, b);
+    a.count[q] = b.count;
+}
+
+extern "C" int pmn_knn_distance(const float* to_xyz, const long long* to_keys, long long n_to, const double* origin_host, double cell,
+                                const int* dims_host, const float* query, const int* order, long long n_from, int k, double max_dist,
+                                int same_cloud, double* d2, int* index, double* mean, void* stream) {
+    KnnArgs a;
+    const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
+    if (rc != PMN_OK) return rc;
+    if (!query || n_from < 1 || n_from >= (1LL << 31) - 64 || k < 1 || k > 32) return PMN_ERR_ARG;
+    if (!(max_dist > 0.0) || !std::isfinite(max_dist) || !std::isfinite(max_dist * max_dist)) return PMN_ERR_ARG;
+    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
+    a.query = query;
+    a.order = order;
+    a.n_from = (int)n_from;
+    a.k = k;
+    a.same_cloud = same_cloud ? 1 : 0;
+    a.max_dist = max_dist;
+    a.d2 = d2;
+    a.index = index;
+    a.mean = mean;
+    const dim3 grid((unsigned)((n_from + 63) / 64));
+    if (k <= 8) PMN_LAUNCH(knn_distance_kernel<8>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    else if (k <= 16) PMN_LAUNCH(knn_distance_kernel<16>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    else PMN_LAUNCH(knn_distance_kernel<32>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}
+
+extern "C" int pmn_radius_count(const float* to_xyz, const long long* to_keys, long long n_to, const double* origin_host, double cell,
+                                const int* dims_host, const float* query, const int* order, long long n_from, double radius,
+                                int same_cloud, int* count, void* stream) {
+    RadiusArgs a;
+    const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
+    if (rc != PMN_OK) return rc;
+    if (!query || !count || n_from < 1 || n_from >= (1LL << 31) - 64) return PMN_ERR_ARG;
+    if (!(radius >= 0.0) || !std::isfinite(radius) || !std::isfinite(radius * radius)) return PMN_ERR_ARG;
+    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
+    a.query = query;
+    a.order = order;
+    a.n_from = (int)n_from;
+    a.same_cloud = same_cloud ? 1 : 0;
+    a.radius = radius;
+    a.count = count;
+    PMN_LAUNCH(radius_count_kernel, dim3((unsigned)((n_from + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
 }
 
 extern "C" int pmn_nn_distance(const float* to_xyz, const long long* to_keys, long long n_to, const double* origin_host, double cell,

@@ -7,6 +7,9 @@ plumbing and uses torch on the device (cell coordinates -> 63-bit key -> torch.s
 from the ObsMask volume, a dot product, boolean selects, one sort for the median, float64 sums: a few elementwise launches per scan).
 There is no CPU path: the searches refuse host tensors.
 
+The same grid serves cloud cleaning (clean_cloud.py): pmn_knn_distance and pmn_radius_count are the k nearest
+neighbours and the number of points within a radius, and statistical_outliers / radius_outliers the two filters built on them.
+
 Semantics: every distance is sqrt(dx*dx + dy*dy + dz*dz) of the float32 PLY coordinates widened to float64; the visiting
 order of the reduction is an explicit, seeded permutation (the MATLAB draws an unseeded randperm), and for a given order the result is
 the sequential greedy set exactly; nn_distance returns min(d, max_dist) where MaxDistCP.m returns some value >= MaxDist (the one stated
@@ -29,6 +32,9 @@ from ._lib import PmnError, check
 NN_CELL = 2.0          # cell of the nearest-neighbour grids, in scene units (DTU: millimetres)
 REDUCE_CELL_RATIO = 2  # cell of the reduction's grid = REDUCE_CELL_RATIO * dst
 ROUNDS_PER_READ = 4    # rounds of the reduction enqueued between two reads of the undecided counters
+# defaults of the cleaning filters, chosen from the sweep recorded in DESIGN.md 23 (profiles/clean_cloud_measure.log)
+CLEAN_CELL_POINTS = 8.0      # default_cell: mean number of points per occupied cell at which the doubling stops
+CLEAN_MAX_DIST_CELLS = 16.0  # default max_dist of statistical_outliers, in cells
 
 
 # ---- files --------------------------------------------------------------------------------------------------------------------
@@ -204,10 +210,7 @@ def nn_distance(query: torch.Tensor, grid: Grid, max_dist: float, return_index: 
     if not (max_dist > 0.0 and np.isfinite(max_dist)):
         raise PmnError(f"nn_distance: max_dist must be positive and finite, got {max_dist}")
     n = int(query.shape[0])
-    # queries are taken in the order of their own cells: the lanes of a wave then walk the same cells
-    qc = _cells(query, grid.origin, grid.cell).clamp_(-1, max(grid.dims))
-    side = max(grid.dims) + 2
-    order = torch.argsort(((qc[:, 2] + 1) * side + (qc[:, 1] + 1)) * side + (qc[:, 0] + 1)).int()
+    order = _cell_order(query, grid)
     dist = torch.empty(n, dtype=torch.float64, device=query.device)
     index = torch.empty(n, dtype=torch.int32, device=query.device) if return_index else None
     with torch.cuda.device(query.device):
@@ -217,6 +220,146 @@ def nn_distance(query: torch.Tensor, grid: Grid, max_dist: float, return_index: 
         return dist
     idx = index.long()
     return dist, torch.where(idx >= 0, grid.perm[idx.clamp_min(0)], idx)
+
+
+def _cell_order(query: torch.Tensor, grid: Grid) -> torch.Tensor:
+    """int32 [n]: the queries in the order of their own cells (the lanes of a wave then walk the same cells)."""
+    qc = _cells(query, grid.origin, grid.cell).clamp_(-1, max(grid.dims))
+    side = max(grid.dims) + 2
+    return torch.argsort(((qc[:, 2] + 1) * side + (qc[:, 1] + 1)) * side + (qc[:, 0] + 1)).int()
+
+
+def _search_query(what: str, query: Optional[torch.Tensor], grid: Grid, same_cloud: bool):
+    """(query tensor, order or None) of a k-nearest / radius search.  ``same_cloud``: the grid's own sorted points in identity order
+    (they ARE in cell order), so that query i is grid point i as the kernels' flag states."""
+    if same_cloud:
+        if query is not None:
+            raise PmnError(f"{what}: same_cloud=True queries the grid's own points; pass query=None")
+        return grid.xyz, None
+    query = _points(query, "query")
+    if query.device != grid.xyz.device:
+        raise PmnError(f"{what}: query is on {query.device}, the grid on {grid.xyz.device}")
+    return query, _cell_order(query, grid)
+
+
+def _unsort(t: torch.Tensor, grid: Grid, same_cloud: bool) -> torch.Tensor:
+    """Rows of a same_cloud result (grid-sorted) back in the order of the points the grid was built from."""
+    if not same_cloud:
+        return t
+    out = torch.empty_like(t)
+    out[grid.perm] = t
+    return out
+
+
+def knn_distance(query: Optional[torch.Tensor], grid: Grid, k: int, max_dist: float, same_cloud: bool = False,
+                 return_d2: bool = False, return_index: bool = False):
+    """pmn_knn_distance: float64 [n], the mean distance from every query point to its ``k`` (1..32) nearest points of ``grid``; a
+    neighbour slot for which no point lies nearer than ``max_dist`` counts as ``max_dist`` (pmn_nn_distance's cap).
+    ``return_d2``: also float64 [n,k], the squared distances ascending (max_dist * max_dist in a capped slot); ``return_index``: also
+    int64 [n,k], indices into the points ``grid`` was built from (-1 in a capped slot; ties at equal d2 go to the point that comes
+    first in the grid's sorted order).  The lists cost 8 k n and 4 k n bytes: the cleaning filters ask for the mean alone.
+    ``same_cloud``: the queries are the grid's own points (``query`` must be None); a point is never its own neighbour (excluded by
+    index: an exact duplicate at distance 0 is a neighbour), and row i of every result belongs to point i of the original cloud."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
+        raise PmnError(f"knn_distance: k must be an integer in 1..32, got {k!r}")
+    if not (max_dist > 0.0 and np.isfinite(max_dist) and np.isfinite(float(max_dist) ** 2)):
+        raise PmnError(f"knn_distance: max_dist must be positive and finite, got {max_dist}")
+    query, order = _search_query("knn_distance", query, grid, same_cloud)
+    n, k, dev = int(query.shape[0]), int(k), query.device
+    mean = torch.empty(n, dtype=torch.float64, device=dev)
+    d2 = torch.empty((n, k), dtype=torch.float64, device=dev) if return_d2 else None
+    index = torch.empty((n, k), dtype=torch.int32, device=dev) if return_index else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_knn_distance(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n, k,
+                                          float(max_dist), int(bool(same_cloud)), d2.data_ptr() if return_d2 else None,
+                                          index.data_ptr() if return_index else None, mean.data_ptr(), _stream(query)),
+              "pmn_knn_distance")
+    out = [_unsort(mean, grid, same_cloud)]
+    if return_d2:
+        out.append(_unsort(d2, grid, same_cloud))
+    if return_index:
+        idx = index.long()
+        out.append(_unsort(torch.where(idx >= 0, grid.perm[idx.clamp_min(0)], idx), grid, same_cloud))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def radius_count(query: Optional[torch.Tensor], grid: Grid, radius: float, same_cloud: bool = False) -> torch.Tensor:
+    """pmn_radius_count: int32 [n], the number of points of ``grid`` within ``radius`` of every query point (sqrt(d2) <= radius on
+    the float64 distance).  ``same_cloud``: as knn_distance; the point itself is not counted."""
+    if not (radius >= 0.0 and np.isfinite(radius) and np.isfinite(float(radius) ** 2)):
+        raise PmnError(f"radius_count: radius must be finite and >= 0, got {radius}")
+    query, order = _search_query("radius_count", query, grid, same_cloud)
+    n = int(query.shape[0])
+    count = torch.empty(n, dtype=torch.int32, device=query.device)
+    with torch.cuda.device(query.device):
+        check(_lib.lib().pmn_radius_count(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n,
+                                          float(radius), int(bool(same_cloud)), count.data_ptr(), _stream(query)), "pmn_radius_count")
+    return _unsort(count, grid, same_cloud)
+
+
+def default_cell(points: torch.Tensor, target: float = CLEAN_CELL_POINTS) -> float:
+    """The cell of a cleaning grid: doubled from a small start until the occupied cells hold ``target`` points on average (occupied
+    cells counted with torch.unique on the keys).  Only the time of a search depends on it, never its result."""
+    points = _points(points, "points")
+    n = int(points.shape[0])
+    lo = points.min(0).values.double()
+    extent = float((points.max(0).values.double() - lo).max())
+    if not extent > 0.0:
+        return 1.0
+    # no arrangement of n points over this extent (not even a line) reaches the target below extent * target / n; 2^-20 of the extent
+    # keeps the key inside 63 bits
+    cell = extent * max(min(target / n, 1.0) / 2.0, 2.0 ** -20)
+    origin = lo.cpu().tolist()
+    while cell < extent:
+        c = _cells(points, origin, cell)
+        dims = (c.max(0).values + 1).cpu().tolist()
+        keys = (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
+        if n / int(torch.unique(keys).numel()) >= target:
+            break
+        cell *= 2.0
+    return cell
+
+
+def _clean_grid(points: torch.Tensor, cell: Optional[float]) -> Grid:
+    return build_grid(points, default_cell(points) if cell is None else cell)
+
+
+def statistical_outliers(points: torch.Tensor, k: int = 20, std_ratio: float = 2.0, max_dist: Optional[float] = None,
+                         cell: Optional[float] = None):
+    """Statistical outlier removal (PCL StatisticalOutlierRemoval, Open3D remove_statistical_outlier) on the device:
+    (keep bool [n], mean float64 [n], threshold float).  mean[i] is the mean distance from point i to its ``k`` nearest other points
+    (knn_distance, same_cloud); threshold = mu + std_ratio * sigma over the n means, sigma with n - 1 in the denominator as in both
+    libraries (0 for a single point), float64 on the device; keep = mean <= threshold.  That is PCL's rule; Open3D keeps mean <
+    threshold, which differs only for a mean exactly on the threshold.
+    Deviation: the search is capped at ``max_dist`` (default CLEAN_MAX_DIST_CELLS cells) so that a far outlier does not walk empty
+    shells for ever.  A point with fewer than k neighbours inside max_dist -- or a cloud of fewer than k + 1 points, where PCL and
+    Open3D average what there is -- has capped slots that count as max_dist each: its mean is a lower bound of the true one, still
+    far above any surface point's.  ``cell`` (default: default_cell) changes the time only."""
+    points = _points(points, "points")
+    if not np.isfinite(std_ratio):
+        raise PmnError(f"statistical_outliers: std_ratio must be finite, got {std_ratio}")
+    grid = _clean_grid(points, cell)
+    if max_dist is None:
+        max_dist = CLEAN_MAX_DIST_CELLS * grid.cell
+    mean = knn_distance(None, grid, k, max_dist, same_cloud=True)
+    sigma = mean.std(unbiased=True) if mean.numel() > 1 else mean.new_zeros(())
+    threshold = float(mean.mean() + float(std_ratio) * sigma)
+    return mean <= threshold, mean, threshold
+
+
+def radius_outliers(points: torch.Tensor, radius: float, min_neighbors: int, cell: Optional[float] = None):
+    """Radius outlier removal (PCL RadiusOutlierRemoval, Open3D remove_radius_outlier) on the device: (keep bool [n], count int32
+    [n]); count[i] is the number of OTHER points within ``radius`` (<=) of point i and keep = count >= min_neighbors.  ``cell``
+    (default: default_cell, but not below radius / 8 so that the walk stays within a few shells) changes the time only."""
+    points = _points(points, "points")
+    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or min_neighbors < 0:
+        raise PmnError(f"radius_outliers: min_neighbors must be an integer >= 0, got {min_neighbors!r}")
+    if not (radius >= 0.0 and np.isfinite(radius)):
+        raise PmnError(f"radius_outliers: radius must be finite and >= 0, got {radius}")
+    if cell is None:
+        cell = max(default_cell(points), float(radius) / 8.0)
+    count = radius_count(None, build_grid(points, cell), radius, same_cloud=True)
+    return count >= int(min_neighbors), count
 
 
 def reduce_points(points: torch.Tensor, dst: float, order=None, seed: int = 0, cell: Optional[float] = None,
