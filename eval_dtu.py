@@ -6,7 +6,8 @@ evaluations/dtu/BaseEvalMain_web.m + ComputeStat_web.m compute (patchmatchnet_am
 --data_path holds Points/stl/stl%03d_total.ply and ObsMask/{ObsMask<scan>_10,Plane<scan>}.mat (or .npz with the same field names).
 A scan's cloud is <ply_path>/<method>%03d_<light>.ply (the reference's naming) or, failing that, <ply_path>/scan<N>/fused.ply (what
 eval.py writes; --ply_name mesh.ply takes mesh.py's file instead).  With --sample_spacing S a file with faces is scored by points drawn on
-its triangles S apart (meshops.sample_surface), not by its vertices.  Scores go to <results_path>/dtu_scores.json; a scan already there is not recomputed unless --force.
+its triangles S apart (meshops.sample_surface), not by its vertices.  With --mesh_distance 1 completeness is
+the exact distance from the stl points to the triangles of that file.  Scores go to <results_path>/dtu_scores.json; a scan already there is not recomputed unless --force.
 """
 from __future__ import annotations
 
@@ -35,6 +36,9 @@ def parse_args(argv=None):
     p.add_argument("--sample_spacing", type=float, default=0.0,
                    help="score points drawn on the triangles of a mesh this far apart (0 = off: the file's vertices)")
     p.add_argument("--sample_seed", type=int, default=0, help="seed of --sample_spacing's points")
+    p.add_argument("--mesh_distance", type=int, default=0, choices=[0, 1],
+                   help="1: completeness is measured against the triangles of the method's mesh themselves (exact point-to-mesh "
+                        "distance), not against its vertices or samples; accuracy is unchanged")
     p.add_argument("--force", action="store_true", help="recompute scans already in dtu_scores.json")
     p.add_argument("--device", default="cuda:0")
     return p.parse_args(argv)
@@ -67,20 +71,27 @@ def score_scan(args, scan: int, files: Dict[str, str]) -> Dict:
 
     from patchmatchnet_amd import pointcloud as PC
     t0 = time.perf_counter()
-    if args.sample_spacing > 0:
+    mesh = None
+    if args.sample_spacing > 0 or args.mesh_distance:
         from patchmatchnet_amd import PmnError, meshops, render
         model = render.read_ply_model(files["ply"])
         if model["faces"] is None or len(model["faces"]) == 0:
-            raise PmnError(f"{files['ply']}: --sample_spacing needs a mesh, this file has no faces")
-        data = meshops.sample_surface(torch.from_numpy(model["vertices"]).to(args.device), torch.from_numpy(model["faces"]).to(args.device),
-                                      spacing=args.sample_spacing, seed=args.sample_seed)[0]
+            flag = "--sample_spacing" if args.sample_spacing > 0 else "--mesh_distance"
+            raise PmnError(f"{files['ply']}: {flag} needs a mesh, this file has no faces")
+        vertices = torch.from_numpy(model["vertices"]).to(args.device)
+        faces = torch.from_numpy(model["faces"]).to(args.device)
+        if args.mesh_distance:
+            mesh = (vertices.contiguous(), faces.contiguous())
+    if args.sample_spacing > 0:
+        data = meshops.sample_surface(vertices, faces, spacing=args.sample_spacing, seed=args.sample_seed)[0]
     else:
         data = torch.from_numpy(PC.read_ply_vertices(files["ply"])).to(args.device)
     stl = torch.from_numpy(PC.read_ply_vertices(files["stl"])).to(args.device)
     obs, bb, res = PC.load_obs_mask(files["obs_mask"])
     plane = PC.load_plane(files["plane"])
     t1 = time.perf_counter()
-    out = PC.dtu_score_scan(data, stl, obs, bb, res, plane, dst=args.dst, max_dist=args.max_dist, seed=args.seed)
+    out = PC.dtu_score_scan(data, stl, obs, bb, res, plane, dst=args.dst, max_dist=args.max_dist, seed=args.seed,
+                            **({"mesh": mesh} if mesh else {}))
     out["seconds"]["read"] = t1 - t0
     out["ply"] = files["ply"]
     if args.sample_spacing > 0:
@@ -99,7 +110,9 @@ def main(argv=None) -> int:
         raise SystemExit("eval_dtu.py: --sample_spacing must be >= 0")
     if args.sample_spacing > 0:  # only then: a plain run's file keeps its keys, and the two kinds of scores are never mixed
         settings.update({"sample_spacing": args.sample_spacing, "sample_seed": args.sample_seed})
-    sampling = ("sample_spacing", "sample_seed")
+    if args.mesh_distance:
+        settings["mesh_distance"] = True
+    sampling = ("sample_spacing", "sample_seed", "mesh_distance")
     scores: Dict[str, Dict] = {}
     if os.path.isfile(out_path) and not args.force:
         with open(out_path) as f:

@@ -7,6 +7,7 @@
 --dataset_dir holds <Scene>.ply (the ground truth), <Scene>.json (the crop volume), <Scene>_COLMAP_SfM.log (the reference trajectory)
 and <Scene>_trans.txt.  The reconstruction's cameras come from --trajectory LOG or from <mvs_folder>/cams/*_cam.txt; --init_transform
 FILE (a 4 x 4 matrix) replaces the trajectory alignment, --no_registration scores a cloud that already is in the ground truth's frame.
+With --mesh_distance 1 recall is the exact distance from the ground truth to the triangles of --ply_path.
 --ply_path may be a mesh: its vertices are read as a cloud or, with --sample_spacing S, points drawn on its triangles S apart
 (meshops.sample_surface) are scored: the surface, not the lattice its vertices sit on.  Scores go to
 <results_path>/tnt_scores.json.
@@ -44,6 +45,9 @@ def parse_args(argv=None):
     p.add_argument("--sample_spacing", type=float, default=0.0,
                    help="score points drawn on the triangles of --ply_path (a mesh) this far apart, in its own units (0 = off: the vertices)")
     p.add_argument("--sample_seed", type=int, default=0, help="seed of --sample_spacing's points")
+    p.add_argument("--mesh_distance", type=int, default=0, choices=[0, 1],
+                   help="1: recall is measured against the triangles of --ply_path themselves (exact point-to-mesh distance), not against "
+                        "its vertices or samples; precision is unchanged")
     p.add_argument("--device", default="cuda:0")
     args = p.parse_args(argv)
     if args.sample_spacing < 0:
@@ -95,13 +99,19 @@ def main(argv=None) -> int:
 
     from patchmatchnet_amd import _lib, pointcloud as PC, registration as RG
     t0 = time.perf_counter()
-    if args.sample_spacing > 0:
+    mesh = None
+    if args.sample_spacing > 0 or args.mesh_distance:
         from patchmatchnet_amd import meshops, render
         model = render.read_ply_model(args.ply_path)
         if model["faces"] is None or len(model["faces"]) == 0:
-            raise _lib.PmnError(f"{args.ply_path}: --sample_spacing needs a mesh, this file has no faces")
-        est = meshops.sample_surface(torch.from_numpy(model["vertices"]).to(args.device), torch.from_numpy(model["faces"]).to(args.device),
-                                     spacing=args.sample_spacing, seed=args.sample_seed)[0]
+            flag = "--sample_spacing" if args.sample_spacing > 0 else "--mesh_distance"
+            raise _lib.PmnError(f"{args.ply_path}: {flag} needs a mesh, this file has no faces")
+        vertices = torch.from_numpy(model["vertices"]).to(args.device)
+        faces = torch.from_numpy(model["faces"]).to(args.device)
+        if args.mesh_distance:
+            mesh = (vertices.contiguous(), faces.contiguous())
+    if args.sample_spacing > 0:
+        est = meshops.sample_surface(vertices, faces, spacing=args.sample_spacing, seed=args.sample_seed)[0]
         print("%s: %d points sampled on %d triangles" % (args.ply_path, est.shape[0], len(model["faces"])))
     else:
         est = torch.from_numpy(PC.read_ply_vertices(args.ply_path)).to(args.device)
@@ -111,7 +121,7 @@ def main(argv=None) -> int:
     t1 = time.perf_counter()
     out = RG.tnt_score(est, gt, volume, args.tau, init=init, register=not args.no_registration, round_a=tuple(args.round_a),
                        round_b=tuple(args.round_b), round_c_dist=args.round_c_dist, icp_iterations=args.icp_iterations,
-                       max_points=args.max_points, hist_max=args.hist_max, bins=args.hist_bins)
+                       max_points=args.max_points, hist_max=args.hist_max, bins=args.hist_bins, **({"mesh": mesh} if mesh else {}))
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     for r in out["rounds"]:
@@ -124,6 +134,8 @@ def main(argv=None) -> int:
                 "registration": not args.no_registration, "seconds": {"read": t1 - t0, "score": t2 - t1}})
     if args.sample_spacing > 0:
         out.update({"sample_spacing": args.sample_spacing, "sample_seed": args.sample_seed, "sampled_points": int(est.shape[0])})
+    if args.mesh_distance:
+        out["mesh_distance"] = True
     with open(os.path.join(args.results_path, "tnt_scores.json"), "w") as f:
         json.dump(out, f, indent=1)
     return 0

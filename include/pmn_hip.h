@@ -781,6 +781,36 @@ int pmn_radius_count(const float *to_xyz, const long long *to_keys, long long n_
                      const int *dims_host, const float *query, const int *order, long long n_from, double radius, int same_cloud,
                      int *count, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  The exact distance from points to a triangle mesh
+ * (patchmatchnet_amd/meshops.py build_face_grid / point_mesh_distance; tests/mesh_distance_ref.py is the numpy
+ * form; the reference has no counterpart).  vertices, faces, n_vertices, n_faces and invalid as in the mesh entry points above: a face
+ * with an index outside [0, n_vertices) is counted into *invalid by a launch of its own and belongs to no result.
+ *
+ * The first six arguments are pmn_nn_distance's grid, built over n_ref REFERENCE POINTS of the faces; entry_face [n_ref] (DEVICE int32,
+ * in the grid's sorted order) names the face each of them belongs to (a value outside [0, n_faces) is skipped), and radius (finite,
+ * >= 0) is a covering radius: the caller guarantees that every point of every face lies within `radius` of at least one of that face's
+ * reference points as stored.  Under that guarantee the result is the minimum over ALL faces (the argument: csrc/meshops.hip); nothing
+ * else about the reference points matters, a face may have any number of them.
+ *
+ * For each of the n_query points (query [n_query][3] float32, any finite position; order as pmn_nn_distance's, NULL = identity; 1 <=
+ * n_query < 2^31 - 64), in float64 from the float32 coordinates, no contraction, IEEE division and sqrt, sums of three products left to
+ * right in x, y, z order, with A, B, C the face's vertices in its order:
+ *   segment(P, Q): e = Q - P, w = q - P, l2 = e.e, t = l2 > 0 ? (w.e) / l2 : 0 clamped to [0, 1], c = P + t * e, d2 = |q - c|^2;
+ *   plane: e1 = B - A, e2 = C - A, n = e1 x e2, nn = n.n, w = q - A; only if nn > 0: u = ((e1 x w).n) / nn, v = ((w x e2).n) / nn; only
+ *   if u >= 0, v >= 0, u + v <= 1: c = q - ((w.n) / nn) * n, d2 = (w.n)(w.n) / nn;
+ *   the face's d2 = the least of segment(A, B), segment(B, C), segment(C, A), plane, in this order, the first among equals.
+ * Faces (a, a, b), (a, a, a) and collinear faces are thereby segments or points.  Among faces with bit-equal d2 the lower face index
+ * wins, so every output is a function of (mesh, query) alone, whatever the order of the faces, the reference points or the grid.
+ *   dist [n_query] float64 = sqrt(d2) of the nearest face; a face counts only with d2 < max_dist * max_dist (max_dist and its square
+ *   positive and finite), otherwise dist = max_dist itself (pmn_nn_distance's convention);
+ *   face [n_query] int32, may be NULL: the index into faces, -1 at the cap;
+ *   closest [n_query][3] float64, may be NULL: the point c of that face, NaN at the cap.
+ * Two launches: a thread per face for *invalid, then ceil(n_query / 64) one-wave workgroups, one lane per query, no scratch memory. */
+int pmn_mesh_distance(const float *ref_xyz, const long long *ref_keys, long long n_ref, const double *origin_host, double cell,
+                      const int *dims_host, const int *entry_face, double radius, const float *vertices, int n_vertices,
+                      const int *faces, int n_faces, const float *query, const int *order, long long n_query, double max_dist,
+                      double *dist, int *face, double *closest, int *invalid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

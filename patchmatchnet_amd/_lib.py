@@ -113,6 +113,8 @@ SIGNATURES = {
                          _fp, _ip, _fp, _s],
     "pmn_radius_count": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, ctypes.c_double, _i, _ip,
                          _s],
+    "pmn_mesh_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _ip, ctypes.c_double, _fp, _i, _ip, _i, _fp, _ip,
+                          ctypes.c_longlong, ctypes.c_double, _fp, _ip, _fp, _ip, _s],
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)

@@ -36,9 +36,30 @@
 //            s = sqrtf(r1);  b0 = 1 - s;  b1 = s * (1 - r2);  b2 = s * r2;  p = (b0 * A + b1 * B) + b2 * C per coordinate; a colour
 //            channel is the same blend of the three bytes as floats, floorf(c + 0.5f) clamped to 0..255 (as pmn_mt_emit rounds)
 // Samples are ordered by face, then k.
+//
+// Distance to the surface (pmn_mesh_distance).  For every query the minimum over ALL faces of the exact
+// point-triangle distance, the face that attains it and the nearest point on it.  Float64 from the float32 vertices, nothing contracted,
+// IEEE division and sqrt; A, B, C the face's vertices in its order, every sum of three products left to right in x, y, z order:
+//   segment(P, Q)  e = Q - P, w = q - P;  l2 = e.e;  t = l2 > 0 ? (w.e) / l2 : 0, clamped to [0, 1];  c = P + t * e;  d2 = |q - c|^2
+//   plane          e1 = B - A, e2 = C - A, n = e1 x e2, nn = n.n, w = q - A;  only if nn > 0:  u = ((e1 x w).n) / nn,
+//                  v = ((w x e2).n) / nn;  only if u >= 0, v >= 0 and u + v <= 1:  s = (w.n) / nn;  c = q - s * n;  d2 = (w.n)(w.n) / nn
+//   face           the least d2 of segment(A, B), segment(B, C), segment(C, A), plane, in this order, the first among equals
+// A face without area is thereby the union of its segments (a segment, or a point), never an error, and a face's value is a function of
+// (its three vertices, q) alone.  Among faces with bit-equal d2 the lower face index wins, so the result is a function of (mesh, query).
+//
+// Search.  The caller (meshops.build_face_grid) sorts REFERENCE POINTS of the faces into an ordinary grid (pc_grid.hpp) -- the centroids of
+// a face's conceptual 4^L midpoint split, every one labelled with the ORIGINAL face (entry_face) -- and states a covering radius R: every
+// point of every face lies within R of one of that face's reference points as stored (float32).  The shell walk runs over the reference
+// points with the accumulator MeshBest.  Why the result is the true minimum: let the walk end with best distance b, and suppose a face F
+// has a point p with |q - p| = d < b (or d = b bit-equal with a lower index).  Some reference point r of F has |p - r| <= R, hence
+// |q - r| <= d + R <= b + R.  The walk skips a region only when its lower bound g exceeds (sqrt(best) + R)(1 + 2^-20) for the best OF
+// THAT MOMENT, which is never below b; offer() skips r under the same test.  So r was offered, F evaluated, and F's value d compared with
+// the best -- a contradiction.  Skipping the face that already is the best is safe because a face's value does not depend on the entry.
+// One lane per query in the order of the queries' cells, one-wave workgroups (pointcloud.hip says why); the state of a lane is the best
+// d2, its face, three doubles of closest point and the bound: no array, no scratch.
 #include <cmath>
 
-#include "pmn_common.hpp"
+#include "pc_grid.hpp"
 
 #define MESH_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -250,6 +271,186 @@ extern "C" int pmn_mesh_sample(const float* vertices, int n_vertices, const int*
     a.face = face;
     a.out_colors = out_colors;
     PMN_LAUNCH(mesh_sample_kernel, dim3((unsigned)((n_samples + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}
+
+// ---- distance to the surface -----------------------------------------------------------------------------------------------------
+
+struct MeshDistArgs {
+    GridArgs g;              // the reference points, grid-sorted
+    const int* entry_face;   // [g.n] face of every sorted reference point
+    const float* vertices;   // [nv][3]
+    const int* faces;        // [nt][3]
+    int nv, nt;
+    double radius;           // R
+    const float* query;      // [n][3]
+    const int* order;        // [n] or null
+    int n;
+    double max_dist;
+    double* dist;            // [n]
+    int* face;               // [n] or null
+    double* closest;         // [n][3] or null
+};
+
+// one point-segment candidate: replaces (d2, c) when strictly nearer
+__device__ __forceinline__ void mesh_seg(const double px, const double py, const double pz, const double rx, const double ry,
+                                         const double rz, const double qx, const double qy, const double qz, double& d2, double& cx,
+                                         double& cy, double& cz) {
+#pragma clang fp contract(off)
+    const double ex = rx - px, ey = ry - py, ez = rz - pz;
+    const double wx = qx - px, wy = qy - py, wz = qz - pz;
+    const double l2 = ex * ex + ey * ey + ez * ez;
+    double t = l2 > 0.0 ? (wx * ex + wy * ey + wz * ez) / l2 : 0.0;
+    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    const double sx = px + t * ex, sy = py + t * ey, sz = pz + t * ez;
+    const double dx = qx - sx, dy = qy - sy, dz = qz - sz;
+    const double s2 = dx * dx + dy * dy + dz * dz;
+    if (s2 < d2) {
+        d2 = s2;
+        cx = sx;
+        cy = sy;
+        cz = sz;
+    }
+}
+
+// the exact squared distance from q to the triangle (A, B, C) and the nearest point: the formulation of the header comment
+__device__ __forceinline__ double mesh_point_triangle(const float* __restrict__ A, const float* __restrict__ B,
+                                                      const float* __restrict__ C, const double qx, const double qy, const double qz,
+                                                      double& cx, double& cy, double& cz) {
+#pragma clang fp contract(off)
+    const double ax = (double)A[0], ay = (double)A[1], az = (double)A[2];
+    const double bx = (double)B[0], by = (double)B[1], bz = (double)B[2];
+    const double gx = (double)C[0], gy = (double)C[1], gz = (double)C[2];
+    double d2 = __builtin_inf();
+    mesh_seg(ax, ay, az, bx, by, bz, qx, qy, qz, d2, cx, cy, cz);
+    mesh_seg(bx, by, bz, gx, gy, gz, qx, qy, qz, d2, cx, cy, cz);
+    mesh_seg(gx, gy, gz, ax, ay, az, qx, qy, qz, d2, cx, cy, cz);
+    const double e1x = bx - ax, e1y = by - ay, e1z = bz - az;
+    const double e2x = gx - ax, e2y = gy - ay, e2z = gz - az;
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const double nn = nx * nx + ny * ny + nz * nz;
+    if (nn > 0.0) {
+        const double wx = qx - ax, wy = qy - ay, wz = qz - az;
+        const double ux = e1y * wz - e1z * wy, uy = e1z * wx - e1x * wz, uz = e1x * wy - e1y * wx;  // e1 x w
+        const double vx = wy * e2z - wz * e2y, vy = wz * e2x - wx * e2z, vz = wx * e2y - wy * e2x;  // w x e2
+        const double u = (ux * nx + uy * ny + uz * nz) / nn, v = (vx * nx + vy * ny + vz * nz) / nn;
+        if (u >= 0.0 && v >= 0.0 && u + v <= 1.0) {
+            const double dp = wx * nx + wy * ny + wz * nz;
+            const double p2 = (dp * dp) / nn;
+            if (p2 < d2) {
+                const double s = dp / nn;
+                d2 = p2;
+                cx = qx - s * nx;
+                cy = qy - s * ny;
+                cz = qz - s * nz;
+            }
+        }
+    }
+    return d2;
+}
+
+// The walk's accumulator that turns it into a triangle search (pc_grid.hpp: "ONE rule over an accumulator").  reach2 is
+// ((sqrt(d2) + R)(1 + 2^-20))^2 of the current best: a reference point, or a region, whose squared distance exceeds it belongs to no face
+// that can beat or tie the best.  The slack errs towards visiting, as PMN_PC_SLACK does.
+struct MeshBest {
+    double d2, reach2, cx, cy, cz, qx, qy, qz, radius;
+    int face;
+    const int* entry_face;
+    const int* faces;
+    const float* vertices;
+    int nv, nt;
+
+    __device__ __forceinline__ void bound() {
+#pragma clang fp contract(off)
+        const double reach = (sqrt(d2) + radius) * (1.0 + PMN_PC_SLACK);
+        reach2 = reach * reach;
+    }
+    __device__ __forceinline__ bool beyond(double g2) const { return g2 > reach2; }
+    __device__ __forceinline__ void offer(double r2, int i) {
+        if (r2 > reach2) return;
+        const int f = entry_face[i];
+        if (f == face || !mesh_index_ok(f, nt)) return;
+        const int ia = faces[3 * (size_t)f], ib = faces[3 * (size_t)f + 1], ic = faces[3 * (size_t)f + 2];
+        if (!(mesh_index_ok(ia, nv) && mesh_index_ok(ib, nv) && mesh_index_ok(ic, nv))) return;  // (mesh_dist_check_kernel counts it)
+        double px, py, pz;
+        const double c = mesh_point_triangle(vertices + 3 * (size_t)ia, vertices + 3 * (size_t)ib, vertices + 3 * (size_t)ic, qx, qy, qz,
+                                             px, py, pz);
+        if (c < d2 || (c == d2 && face >= 0 && f < face)) {
+            d2 = c;
+            face = f;
+            cx = px;
+            cy = py;
+            cz = pz;
+            bound();
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void mesh_dist_check_kernel(const int* __restrict__ faces, int nt, int nv, int* invalid) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= nt) return;
+    const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
+    if (!(mesh_index_ok(a, nv) && mesh_index_ok(b, nv) && mesh_index_ok(c, nv))) atomicAdd(invalid, 1);
+}
+
+__global__ __launch_bounds__(64) void mesh_distance_kernel(const MeshDistArgs a) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n) return;
+    const int q = a.order ? a.order[t] : t;
+    MeshBest b;
+    b.qx = (double)a.query[(size_t)q * 3];
+    b.qy = (double)a.query[(size_t)q * 3 + 1];
+    b.qz = (double)a.query[(size_t)q * 3 + 2];
+    b.d2 = a.max_dist * a.max_dist;  // a face at exactly max_dist or beyond never wins (pmn_nn_distance's convention)
+    b.face = -1;
+    b.cx = b.cy = b.cz = __builtin_nan("");
+    b.radius = a.radius;
+    b.entry_face = a.entry_face;
+    b.faces = a.faces;
+    b.vertices = a.vertices;
+    b.nv = a.nv;
+    b.nt = a.nt;
+    b.bound();
+    pc_walk(a.g, b.qx, b.qy, b.qz, b);
+    a.dist[q] = b.face < 0 ? a.max_dist : sqrt(b.d2);
+    if (a.face) a.face[q] = b.face;
+    if (a.closest) {
+        a.closest[(size_t)q * 3] = b.cx;
+        a.closest[(size_t)q * 3 + 1] = b.cy;
+        a.closest[(size_t)q * 3 + 2] = b.cz;
+    }
+}
+
+extern "C" int pmn_mesh_distance(const float* ref_xyz, const long long* ref_keys, long long n_ref, const double* origin_host, double cell,
+                                 const int* dims_host, const int* entry_face, double radius, const float* vertices, int n_vertices,
+                                 const int* faces, int n_faces, const float* query, const int* order, long long n_query, double max_dist,
+                                 double* dist, int* face, double* closest, int* invalid, void* stream) {
+    MeshDistArgs a;
+    int rc = grid_args(a.g, ref_xyz, ref_keys, n_ref, origin_host, cell, dims_host);
+    if (rc != PMN_OK) return rc;
+    rc = mesh_check(vertices, n_vertices, faces, n_faces);
+    if (rc != PMN_OK) return rc;
+    if (!entry_face || !query || !dist || !invalid || n_query < 1 || n_query >= (1LL << 31) - 64) return PMN_ERR_ARG;
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return PMN_ERR_ARG;
+    if (!(max_dist > 0.0) || !std::isfinite(max_dist) || !std::isfinite(max_dist * max_dist)) return PMN_ERR_ARG;
+    a.entry_face = entry_face;
+    a.vertices = vertices;
+    a.faces = faces;
+    a.nv = n_vertices;
+    a.nt = n_faces;
+    a.radius = radius;
+    a.query = query;
+    a.order = order;
+    a.n = (int)n_query;
+    a.max_dist = max_dist;
+    a.dist = dist;
+    a.face = face;
+    a.closest = closest;
+    PMN_LAUNCH(mesh_dist_check_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces, n_faces,
+               n_vertices, invalid);
+    PMN_LAUNCH(mesh_distance_kernel, dim3((unsigned)((n_query + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }

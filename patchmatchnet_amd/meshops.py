@@ -2,18 +2,28 @@
 removal of small components -- the floaters of a TSDF mesh -- and points drawn on the triangles at a fixed density per unit area
 (pmn_mesh_face_samples / pmn_mesh_sample), which is what a surface is scored by.  A mesh is ``vertices`` [Nv,3] float32 and ``faces``
 [Nt,3] int32 on a ROCm GPU, as ops.mt_extract returns them.  There is no CPU path: everything that launches refuses a host tensor.
-tests/meshops_ref.py restates all of it in numpy."""
+tests/meshops_ref.py restates all of it in numpy.  build_face_grid / point_mesh_distance (pmn_mesh_distance) are
+the exact distance from points to the surface itself; tests/mesh_distance_ref.py is their numpy form."""
 from __future__ import annotations
 
-from typing import Optional
+import ctypes
+import math
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib
 from ._lib import PmnError, check
 from .ops import _dev_as, _ptr, _stream
+from .pointcloud import Grid, _cell_order, _points, _sort_into_grid
 
 INT32_MAX = 2 ** 31 - 1
+# settings of build_face_grid, chosen from the sweep recorded in DESIGN.md 25 (profiles/mesh_distance_bench.log); they change the time
+# of a search only, never its result
+FACE_CELL_EDGES = 2.0    # default cell = FACE_CELL_EDGES * the median over the faces of the longest edge
+FACE_COVER_CELLS = 1.0   # default cover = FACE_COVER_CELLS * cell
+FACE_MAX_LEVEL = 16      # a face is split (conceptually) at most into 4^16 parts
+FACE_ENTRY_LIMIT = 2 ** 31 - 64
 
 
 def _faces(faces: torch.Tensor, what: str) -> torch.Tensor:
@@ -172,3 +182,143 @@ def sample_surface(vertices: torch.Tensor, faces: torch.Tensor, density: Optiona
             check(L.pmn_mesh_sample(vertices.data_ptr(), nv, faces.data_ptr(), nt, _ptr(colors), scan.data_ptr(), total, seed,
                                     points.data_ptr(), face.data_ptr(), _ptr(out_colors), _stream(faces)), "pmn_mesh_sample")
     return points, face, out_colors
+
+
+# ---- distance to the surface -------------------------------------------------------------------------------------
+
+class FaceGrid(NamedTuple):
+    """The search structure of point_mesh_distance: a pointcloud.Grid over reference points of the faces (include/pmn_hip.h,
+    pmn_mesh_distance).  Every point of face f lies within ``radius`` of one of the reference points that ``entry_face`` maps to f."""
+    grid: Grid                # over the reference points (float32), sorted
+    entry_face: torch.Tensor  # [E] int32: the face of every sorted reference point
+    vertices: torch.Tensor    # [Nv,3] float32, the caller's
+    faces: torch.Tensor       # [Nt,3] int32, the caller's
+    levels: torch.Tensor      # [Nt] int64: face f has 4^levels[f] reference points
+    radius: float             # R, the float32 rounding of the reference points included
+    cover: float
+
+
+def _mesh_any_device(vertices: torch.Tensor, faces: torch.Tensor, what: str):
+    for t, name, dtype in ((vertices, "vertices", torch.float32), (faces, "faces", torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
+            raise PmnError(f"{what}: {name}: expected a contiguous {dtype} tensor")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise PmnError(f"{what}: {name} must be [n,3], got {tuple(t.shape)}")
+    if vertices.device != faces.device:
+        raise PmnError(f"{what}: vertices are on {vertices.device}, faces on {faces.device}")
+    if not 1 <= vertices.shape[0] <= INT32_MAX - 255 or not 1 <= faces.shape[0] <= INT32_MAX - 255:
+        raise PmnError(f"{what}: between 1 and 2^31 - 256 vertices and faces, got {vertices.shape[0]} and {faces.shape[0]}")
+
+
+def build_face_grid(vertices: torch.Tensor, faces: torch.Tensor, cell: Optional[float] = None,
+                    cover: Optional[float] = None) -> FaceGrid:
+    """Sorts reference points of the faces into a uniform grid of side ``cell`` and fixes the covering radius R of point_mesh_distance.
+    A face whose vertices all lie within ``cover`` of its centroid has one reference point, the centroid.  A larger face gets the 4^L
+    centroids of its conceptual L-fold midpoint split (the 2^L x 2^L lattice of similar triangles), L the smallest level at which a
+    part's vertices lie within ``cover`` of the part's centroid; they are computed in float64 from their barycentric weights
+    (3 i + 1 or 2) / (3 * 2^L) and all name the ORIGINAL face: no geometry is subdivided.  A part is convex, so each of its points is
+    within the part's radius of its centroid; R is the largest such radius plus sqrt(3) * 2^-23 * max |coordinate| for the rounding of
+    the reference points to float32 (twice its bound; the rest covers the float64 arithmetic).  Degenerate faces are faces like any
+    other; a face with an index outside 0..Nv-1 is placed by its clamped indices here and refused by point_mesh_distance.
+    Defaults: ``cell`` = FACE_CELL_EDGES * the median longest edge, ``cover`` = FACE_COVER_CELLS * cell; neither changes a result.
+    Torch on the tensors' device -- a host tensor works too (nothing launches) -- with no loop over faces; one host read for the
+    defaults and one for the sizes.  PmnError for vertices that are not finite, a cell or cover that is not positive and finite, and
+    for 2^31 - 64 reference points or more (it names the largest face and the cover)."""
+    what = "build_face_grid"
+    _mesh_any_device(vertices, faces, what)
+    nv, nt, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    bad = int((~torch.isfinite(vertices)).any(1).sum())
+    if bad:
+        raise PmnError(f"{what}: {bad} vertices have non-finite coordinates")
+    idx = faces.long().clamp(0, nv - 1)
+    v64 = vertices.double()
+    A, B, C = v64[idx[:, 0]], v64[idx[:, 1]], v64[idx[:, 2]]
+    longest = torch.stack(((B - A).norm(dim=1), (C - B).norm(dim=1), (A - C).norm(dim=1))).max(0).values
+    G = (A + B + C) / 3.0
+    rf = torch.stack(((A - G).norm(dim=1), (B - G).norm(dim=1), (C - G).norm(dim=1))).max(0).values
+    if cell is None:
+        med, top = float(longest.median()), float(longest.max())
+        cell = FACE_CELL_EDGES * (med if med > 0.0 else (top if top > 0.0 else 1.0))
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise PmnError(f"{what}: cell must be positive and finite, got {cell}")
+    cover = FACE_COVER_CELLS * cell if cover is None else float(cover)
+    if not (cover > 0.0 and math.isfinite(cover)):
+        raise PmnError(f"{what}: cover must be positive and finite, got {cover}")
+    # the level: the smallest L with rf * 2^-L <= cover (the parts are similar to the face at scale 2^-L, so is their radius)
+    levels = torch.ceil(torch.log2(rf / cover)).clamp(0, FACE_MAX_LEVEL).long()
+    levels = (levels + (rf / (torch.ones_like(levels) << levels).double() > cover).long()).clamp(max=FACE_MAX_LEVEL)
+    counts = torch.ones_like(levels) << (2 * levels)
+    total = int(counts.sum())
+    if total >= FACE_ENTRY_LIMIT:
+        f = int(rf.argmax())
+        raise PmnError(f"{what}: {total} reference points reach the limit of 2^31 - 64: face {f} (vertices within {float(rf[f]):.6g} of "
+                       f"its centroid) would need {int(counts[f])} at cover {cover:.6g}; use a larger cover")
+    part_radius = float((rf / (torch.ones_like(levels) << levels).double()).max())
+    # entry k of a face with N = 2^L: row i of the lattice holds 2 (N - i) - 1 parts (upright and inverted alternating), N^2 - k parts
+    # are left from k on, and (N - i)^2 from row i on
+    fid = torch.repeat_interleave(torch.arange(nt, device=dev), counts)
+    k = torch.arange(total, device=dev) - (torch.cumsum(counts, 0) - counts)[fid]
+    N = torch.ones_like(k) << levels[fid]
+    left = N * N - k
+    s = torch.ceil(torch.sqrt(left.double())).long()
+    s = s - ((s - 1) * (s - 1) >= left).long() + (s * s < left).long()  # the integer ceil(sqrt(left)), whatever the float one gave
+    i = N - s
+    t = k - (2 * N * i - i * i)
+    j, inverted = t >> 1, t & 1
+    den = (3 * N).double()
+    w0 = (3 * i + 1 + inverted).double() / den
+    w1 = (3 * j + 1 + inverted).double() / den
+    w2 = (3 * (N - 1 - inverted - i - j) + 1 + inverted).double() / den
+    ref = (w0[:, None] * A[fid] + w1[:, None] * B[fid] + w2[:, None] * C[fid]).float().contiguous()
+    radius = part_radius * (1.0 + 2.0 ** -40) + math.sqrt(3.0) * 2.0 ** -23 * float(vertices.abs().max())
+    grid = _sort_into_grid(ref, cell, what=what)
+    return FaceGrid(grid, fid[grid.perm].int().contiguous(), vertices, faces, levels, radius, cover)
+
+
+def point_mesh_distance(query: torch.Tensor, face_grid: FaceGrid, max_dist: float, return_face: bool = False,
+                        return_closest: bool = False):
+    """pmn_mesh_distance: float64 [n], the exact distance from every query point ([n,3] float32 on the device, any finite position) to
+    the nearest triangle of the mesh ``face_grid`` was built from, capped at ``max_dist`` with nn_distance's convention (a face counts
+    only when d < max_dist).  ``return_face``: also int64 [n], the index into the mesh's faces, the lower index among faces at
+    bit-equal distance, -1 at the cap; ``return_closest``: also float64 [n,3], the nearest point on that face, NaN at the cap.  A
+    function of (mesh, query) alone.  PmnError if a face names a vertex outside the mesh (none is dereferenced); one host read."""
+    what = "point_mesh_distance"
+    if not isinstance(face_grid, FaceGrid):
+        raise PmnError(f"{what}: face_grid must come from build_face_grid")
+    query = _points(query, "query")
+    g = face_grid.grid
+    for t, name in ((g.xyz, "grid"), (g.keys, "keys"), (face_grid.entry_face, "entry_face"), (face_grid.vertices, "vertices"),
+                    (face_grid.faces, "faces")):
+        if not isinstance(t, torch.Tensor) or t.device != query.device:
+            raise PmnError(f"{what}: query is on {query.device}, the face grid's {name} on {getattr(t, 'device', type(t).__name__)}")
+    # a FaceGrid is a plain tuple anyone can put together: what the kernel indexes is checked before raw pointers go to it
+    _mesh_any_device(face_grid.vertices, face_grid.faces, what)
+    n_ref = int(g.xyz.shape[0]) if g.xyz.dim() == 2 else -1
+    if g.xyz.dtype != torch.float32 or g.xyz.dim() != 2 or g.xyz.shape[1] != 3 or not g.xyz.is_contiguous() or n_ref < 1:
+        raise PmnError(f"{what}: the face grid's points must be a contiguous float32 [n,3] tensor, n >= 1")
+    for t, name, dtype in ((g.keys, "keys", torch.int64), (face_grid.entry_face, "entry_face", torch.int32)):
+        if t.dtype != dtype or tuple(t.shape) != (n_ref,) or not t.is_contiguous():
+            raise PmnError(f"{what}: the face grid's {name} must be a contiguous {dtype} [{n_ref}] tensor, got {t.dtype} {tuple(t.shape)}")
+    if not (isinstance(face_grid.radius, float) and face_grid.radius >= 0.0 and math.isfinite(face_grid.radius)):
+        raise PmnError(f"{what}: the face grid's radius must be finite and >= 0, got {face_grid.radius!r}")
+    if not (max_dist > 0.0 and math.isfinite(max_dist) and math.isfinite(float(max_dist) * float(max_dist))):
+        raise PmnError(f"{what}: max_dist must be positive and finite, got {max_dist}")
+    n, dev = int(query.shape[0]), query.device
+    order = _cell_order(query, g)
+    dist = torch.empty(n, dtype=torch.float64, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev) if return_face else None
+    closest = torch.empty((n, 3), dtype=torch.float64, device=dev) if return_closest else None
+    invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_mesh_distance(g.xyz.data_ptr(), g.keys.data_ptr(), int(g.xyz.shape[0]), (ctypes.c_double * 3)(*g.origin),
+                                           float(g.cell), (ctypes.c_int * 3)(*g.dims), face_grid.entry_face.data_ptr(),
+                                           float(face_grid.radius), face_grid.vertices.data_ptr(), int(face_grid.vertices.shape[0]),
+                                           face_grid.faces.data_ptr(), int(face_grid.faces.shape[0]), query.data_ptr(),
+                                           order.data_ptr(), n, float(max_dist), dist.data_ptr(), _ptr(face), _ptr(closest),
+                                           invalid.data_ptr(), _stream(query)), "pmn_mesh_distance")
+    bad = int(invalid.item())
+    if bad:
+        _raise_invalid(what, bad, int(face_grid.vertices.shape[0]))
+    out = (dist,) + ((face.long(),) if return_face else ()) + ((closest,) if return_closest else ())
+    return out[0] if len(out) == 1 else out

@@ -175,18 +175,23 @@ def _cells(points: torch.Tensor, origin, cell: float) -> torch.Tensor:
 def build_grid(points: torch.Tensor, cell: float, origin=None) -> Grid:
     """Sorts ``points`` ([n,3] float32 on the device) into the cells of a uniform grid of side ``cell`` whose corner is ``origin``
     (default: the per-axis minimum of the points; a given origin must not exceed it)."""
-    points = _points(points, "points")
+    return _sort_into_grid(_points(points, "points"), cell, origin)
+
+
+def _sort_into_grid(points: torch.Tensor, cell: float, origin=None, what: str = "build_grid") -> Grid:
+    """build_grid without the device check: meshops.build_face_grid also sorts host tensors (its cover property is tested there).
+    ``what`` names the caller in the errors."""
     cell = float(cell)
     if not (cell > 0.0 and np.isfinite(cell)):
-        raise PmnError(f"build_grid: cell must be positive and finite, got {cell}")
+        raise PmnError(f"{what}: cell must be positive and finite, got {cell}")
     lo = points.min(0).values.double().cpu().numpy()
     origin = lo if origin is None else np.asarray(origin, np.float64).reshape(3)
     if not np.isfinite(origin).all() or (origin > lo).any():
-        raise PmnError(f"build_grid: origin {origin.tolist()} must be finite and not above the points' minimum {lo.tolist()}")
+        raise PmnError(f"{what}: origin {origin.tolist()} must be finite and not above the points' minimum {lo.tolist()}")
     c = _cells(points, origin.tolist(), cell)
     dims = (c.max(0).values + 1).cpu().tolist()
     if max(dims) > 2 ** 30 or dims[0] * dims[1] * dims[2] >= 2 ** 62:
-        raise PmnError(f"build_grid: a grid of {dims} cells does not fit a 63-bit key (PMN_ERR_SHAPE); use a larger cell")
+        raise PmnError(f"{what}: a grid of {dims} cells does not fit a 63-bit key (PMN_ERR_SHAPE); use a larger cell")
     keys = (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
     keys, perm = torch.sort(keys)
     return Grid(points[perm].contiguous(), keys, perm, tuple(float(v) for v in origin), cell, tuple(int(d) for d in dims))
@@ -457,10 +462,14 @@ def _stats(d: torch.Tensor, prefix: str) -> Dict[str, float]:
 
 
 def dtu_score_scan(data_xyz: torch.Tensor, stl_xyz: torch.Tensor, obs_mask, bb, res: float, plane, dst: float = 0.2,
-                   max_dist: float = 20.0, search_dist: float = 60.0, seed: int = 0, nn_cell: Optional[float] = None) -> Dict:
+                   max_dist: float = 20.0, search_dist: float = 60.0, seed: int = 0, nn_cell: Optional[float] = None,
+                   mesh=None) -> Dict:
     """PointCompareMain.m + the statistics of BaseEvalMain_web.m / ComputeStat_web.m for one scan.  data_xyz / stl_xyz: [n,3] float32
     on the device (the vertices of the method's PLY and of stl%03d_total.ply); obs_mask, bb, res, plane: load_obs_mask / load_plane.
     ``max_dist``: the outlier threshold of the statistics (20); ``search_dist``: MaxDistCP's block size and cap (60).
+    ``mesh`` = (vertices, faces) of the method's surface: the stl -> data leg (completeness) is then the exact distance to that surface
+    (meshops.point_mesh_distance against the whole mesh), with the blocks and the ``search_dist`` cap unchanged; the
+    data -> stl leg is unchanged.
     Returns n_data_in, n_data_reduced, reduce_rounds, acc_n/mean/median/var, comp_n/mean/median/var and seconds per phase."""
     data_xyz = _points(data_xyz, "data_xyz")
     stl_xyz = _points(stl_xyz, "stl_xyz")
@@ -485,7 +494,12 @@ def dtu_score_scan(data_xyz: torch.Tensor, stl_xyz: torch.Tensor, obs_mask, bb, 
 
     d_data = blocked(qd, stl_xyz)
     t2 = clock()
-    d_stl = blocked(stl_xyz, qd)
+    if mesh is None:
+        d_stl = blocked(stl_xyz, qd)
+    else:
+        from . import meshops
+        d_stl = meshops.point_mesh_distance(stl_xyz, meshops.build_face_grid(mesh[0], mesh[1]), search_dist)
+        d_stl = torch.where(in_blocks(stl_xyz, bb, search_dist), d_stl, torch.full_like(d_stl, search_dist))
     t3 = clock()
     acc = d_data[data_in_mask(qd, obs, bb, res)]
     comp = d_stl[above_plane(stl_xyz, plane)]

@@ -342,10 +342,13 @@ def _keep(points: torch.Tensor, mask: torch.Tensor, what: str) -> torch.Tensor:
 def tnt_score(est: torch.Tensor, gt: torch.Tensor, volume: Optional[CropVolume], tau: float, init=None, register: bool = True,
               round_a=ROUND_A, round_b=ROUND_B, round_c_dist: float = ROUND_C_DIST, icp_iterations: int = ICP_ITERATIONS,
               max_points: int = MAX_POINTS, hist_max: Optional[float] = None, bins: int = HIST_BINS,
-              return_distances: bool = False):
+              return_distances: bool = False, mesh=None):
     """The Tanks and Temples protocol: from the 4 x 4 ``init`` (identity if None) three ICP rounds bring ``est`` into
     the frame of ``gt`` (skipped unless ``register``), then both clouds are cropped, voxel-downsampled at tau / 2 and cropped again, and
     the capped nearest-neighbour distances in both directions give precision, recall and F-score at ``tau``.  ``volume`` None: no crop.
+    ``mesh`` = (vertices, faces) of the reconstruction in ``est``'s frame: the ground-truth -> reconstruction leg (recall) is then the
+    exact distance to that surface (meshops.point_mesh_distance against the whole mesh, moved by the final pose) and not
+    the distance to the nearest point of ``est``; the other leg is unchanged.
     Returns f_score's dict plus pose and rounds (fitness, rmse, iterations per round); with ``return_distances`` also the two float64
     distance tensors."""
     est, gt = PC._points(est, "est"), PC._points(gt, "gt")
@@ -381,7 +384,11 @@ def tnt_score(est: torch.Tensor, gt: torch.Tensor, volume: Optional[CropVolume],
 
     est_s, gt_s = prepared(transform(est, pose), "the reconstruction"), prepared(gt, "the ground truth")
     d_est = PC.nn_distance(est_s, PC.build_grid(gt_s, tau), hist_max)
-    d_gt = PC.nn_distance(gt_s, PC.build_grid(est_s, tau), hist_max)
+    if mesh is None:
+        d_gt = PC.nn_distance(gt_s, PC.build_grid(est_s, tau), hist_max)
+    else:
+        from . import meshops
+        d_gt = meshops.point_mesh_distance(gt_s, meshops.build_face_grid(transform(mesh[0], pose), mesh[1]), hist_max)
     out = f_score(d_est, d_gt, tau, hist_max, bins)
     out.update({"tau": tau, "pose": pose.tolist(), "rounds": rounds})
     return (out, d_est, d_gt) if return_distances else out
