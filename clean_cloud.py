@@ -9,8 +9,8 @@ statistical: a point stays when the mean distance to its k nearest neighbours is
 cloud (PCL's StatisticalOutlierRemoval; Open3D's remove_statistical_outlier keeps "<").  radius: a point stays when at least
 min_neighbors other points lie within R of it.  Both searches are HIP kernels (pmn_knn_distance, pmn_radius_count) over the grid of
 patchmatchnet_amd/pointcloud.py; --cell changes the time only, --max_dist caps the k-nearest search (pointcloud.statistical_outliers).
-The cloud is read with render.read_ply_model (either kind of fused.ply, or any cloud with further scalar properties) and the kept
-points are written in their original order with fusion.write_ply: x y z [nx ny nz] red green blue, normals when the input had them,
+The cloud is read with ply.read_ply_model (either kind of fused.ply, or any cloud with further scalar properties) and the kept
+points are written in their original order with ply.write_ply: x y z [nx ny nz] red green blue, normals when the input had them,
 white where it had no colours; other properties are not carried over.  `eval_dtu.py --ply_name fused_clean.ply` and `eval_tnt.py
 --ply_path .../fused_clean.ply` read the result.  One process on one ROCm GPU; torchrun is not supported."""
 import argparse
@@ -48,10 +48,10 @@ def clean_file(src: str, dst: str, args, device):
     """Cleans one file; returns (its report entry, the device in use)."""
     import numpy as np
     import torch
-    from patchmatchnet_amd import fusion, pointcloud as PC, render
+    from patchmatchnet_amd import ply, pointcloud as PC
     from patchmatchnet_amd._lib import PmnError
 
-    model = render.read_ply_model(src)
+    model = ply.read_ply_model(src)
     if model["faces"] is not None:
         raise PmnError(f"{src}: a mesh ({len(model['faces'])} faces), not a cloud; drop a mesh's floaters with mesh.py "
                        f"--keep_components / --min_component_faces")
@@ -73,7 +73,7 @@ def clean_file(src: str, dst: str, args, device):
     keep = keep.cpu().numpy()
     out["seconds_search"] = time.perf_counter() - t0
     colors = model["colors"][keep] if model["colors"] is not None else np.full((int(keep.sum()), 3), 255, np.uint8)
-    fusion.write_ply(dst, model["vertices"][keep], colors, model["normals"][keep] if model["normals"] is not None else None)
+    ply.write_ply(dst, model["vertices"][keep], colors, model["normals"][keep] if model["normals"] is not None else None)
     out.update(kept=int(keep.sum()), removed=int(n - keep.sum()))
     print(f"{src}: {n} points read, {out['kept']} kept, {out['removed']} removed ({what}) -> {dst}")
     return out, device

@@ -788,7 +788,7 @@ def _fuse_scan(args, job, rank, world, device, stream, pool, io_pool, state):
         stream.wait_event(job["ready"])
         capacity = sum(sizes[ref][0] * sizes[ref][1] for ref, _ in my_pairs)
         with_normals = bool(getattr(args, "normals", 0))
-        rec_size = 27 if with_normals else 15  # --normals 1: x y z nx ny nz red green blue (fusion.PLY_VERTEX_NORMALS)
+        rec_size = (fusion.PLY_VERTEX_NORMALS if with_normals else fusion.PLY_VERTEX).itemsize  # 27 (--normals 1) or 15 bytes
         # (15 bytes per pixel of every reference view of the scan: 1.4 GB for 49 views of 1600x1200, 9 GB for 300 views of 1920x1080.
         #  A buffer up to --fuse_buffer_mb stays with the worker for the next scan; a larger one is released when its scan is done.)
         packer = state.get("packer")

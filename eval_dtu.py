@@ -69,12 +69,12 @@ def scan_inputs(args, scan: int) -> Dict[str, str]:
 def score_scan(args, scan: int, files: Dict[str, str]) -> Dict:
     import torch
 
-    from patchmatchnet_amd import pointcloud as PC
+    from patchmatchnet_amd import ply, pointcloud as PC
     t0 = time.perf_counter()
     mesh = None
     if args.sample_spacing > 0 or args.mesh_distance:
-        from patchmatchnet_amd import PmnError, meshops, render
-        model = render.read_ply_model(files["ply"])
+        from patchmatchnet_amd import PmnError, meshops
+        model = ply.read_ply_model(files["ply"])
         if model["faces"] is None or len(model["faces"]) == 0:
             flag = "--sample_spacing" if args.sample_spacing > 0 else "--mesh_distance"
             raise PmnError(f"{files['ply']}: {flag} needs a mesh, this file has no faces")
@@ -85,8 +85,8 @@ def score_scan(args, scan: int, files: Dict[str, str]) -> Dict:
     if args.sample_spacing > 0:
         data = meshops.sample_surface(vertices, faces, spacing=args.sample_spacing, seed=args.sample_seed)[0]
     else:
-        data = torch.from_numpy(PC.read_ply_vertices(files["ply"])).to(args.device)
-    stl = torch.from_numpy(PC.read_ply_vertices(files["stl"])).to(args.device)
+        data = torch.from_numpy(ply.read_ply_vertices(files["ply"])).to(args.device)
+    stl = torch.from_numpy(ply.read_ply_vertices(files["stl"])).to(args.device)
     obs, bb, res = PC.load_obs_mask(files["obs_mask"])
     plane = PC.load_plane(files["plane"])
     t1 = time.perf_counter()

@@ -97,12 +97,12 @@ def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
 
-    from patchmatchnet_amd import _lib, pointcloud as PC, registration as RG
+    from patchmatchnet_amd import _lib, ply, registration as RG
     t0 = time.perf_counter()
     mesh = None
     if args.sample_spacing > 0 or args.mesh_distance:
-        from patchmatchnet_amd import meshops, render
-        model = render.read_ply_model(args.ply_path)
+        from patchmatchnet_amd import meshops
+        model = ply.read_ply_model(args.ply_path)
         if model["faces"] is None or len(model["faces"]) == 0:
             flag = "--sample_spacing" if args.sample_spacing > 0 else "--mesh_distance"
             raise _lib.PmnError(f"{args.ply_path}: {flag} needs a mesh, this file has no faces")
@@ -114,8 +114,8 @@ def main(argv=None) -> int:
         est = meshops.sample_surface(vertices, faces, spacing=args.sample_spacing, seed=args.sample_seed)[0]
         print("%s: %d points sampled on %d triangles" % (args.ply_path, est.shape[0], len(model["faces"])))
     else:
-        est = torch.from_numpy(PC.read_ply_vertices(args.ply_path)).to(args.device)
-    gt = torch.from_numpy(PC.read_ply_vertices(os.path.join(args.dataset_dir, f"{args.scene}.ply"))).to(args.device)
+        est = torch.from_numpy(ply.read_ply_vertices(args.ply_path)).to(args.device)
+    gt = torch.from_numpy(ply.read_ply_vertices(os.path.join(args.dataset_dir, f"{args.scene}.ply"))).to(args.device)
     volume = None if args.no_crop else RG.read_crop_json(os.path.join(args.dataset_dir, f"{args.scene}.json"))
     init = initial_transform(args)
     t1 = time.perf_counter()

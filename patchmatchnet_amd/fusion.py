@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from ._lib import PmnError
+from .ply import PLY_VERTEX, PLY_VERTEX_NORMALS, ply_header, ply_records, write_ply, write_ply_records  # noqa: F401  (fused.ply)
 
 
 def camera_block(K_ref: np.ndarray, E_ref: np.ndarray, srcs: Sequence[Tuple[np.ndarray, np.ndarray]]) -> np.ndarray:
@@ -156,64 +157,6 @@ def fuse_scan(views: Dict[int, Dict], pairs: List[Tuple[int, List[int]]], geo_pi
     images = {r: views[r]["image"] for r, _ in pairs}
     return fuse_views(maps, {v: i for i, v in enumerate(ids)}, cams, images, pairs, geo_pixel_thres, geo_depth_thres,
                       geo_mask_thres, photo_thres, sizes=sizes, merge=merge)
-
-
-PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
-# the vertex of an ORIENTED cloud (eval.py --normals 1): the property order MeshLab, Open3D and COLMAP's own
-# fused.ply use, so Poisson meshers read the normals without a conversion
-PLY_VERTEX_NORMALS = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
-                               ("red", "u1"), ("green", "u1"), ("blue", "u1")])
-
-
-def ply_records(vertices: np.ndarray, colors: np.ndarray, normals: Optional[np.ndarray] = None) -> np.ndarray:
-    """The 15-byte vertex records of the PLY body (two strided byte copies: positions, colours); with ``normals`` [n,3] the 27-byte
-    records x y z nx ny nz red green blue."""
-    n = len(vertices)
-    if normals is None:
-        rec = np.empty(n, dtype=PLY_VERTEX)
-        if n:
-            raw = rec.view(np.uint8).reshape(n, 15)
-            raw[:, :12] = np.ascontiguousarray(vertices, "<f4").view(np.uint8).reshape(n, 12)
-            raw[:, 12:] = np.asarray(colors, np.uint8)
-        return rec
-    if len(normals) != n:
-        raise ValueError("ply_records: one normal per vertex")
-    rec = np.empty(n, dtype=PLY_VERTEX_NORMALS)
-    if n:
-        raw = rec.view(np.uint8).reshape(n, 27)
-        raw[:, :12] = np.ascontiguousarray(vertices, "<f4").view(np.uint8).reshape(n, 12)
-        raw[:, 12:24] = np.ascontiguousarray(normals, "<f4").view(np.uint8).reshape(n, 12)
-        raw[:, 24:] = np.asarray(colors, np.uint8)
-    return rec
-
-
-def ply_header(n: int, normals: bool = False) -> bytes:
-    extra = "property float nx\nproperty float ny\nproperty float nz\n" if normals else ""
-    return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-            "property float z\n%sproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % (n, extra)).encode("ascii")
-
-
-def write_ply(filename: str, vertices: np.ndarray, colors: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
-    """Binary little-endian PLY with x,y,z float32 + red,green,blue uint8 per vertex (what plyfile writes at reference
-    eval.py:283-297); with ``normals`` the oriented vertex x,y,z,nx,ny,nz,red,green,blue."""
-    rec = ply_records(vertices, colors, normals)
-    os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
-    with open(filename, "wb") as f:
-        f.write(ply_header(len(rec), normals is not None))
-        rec.tofile(f)
-
-
-def write_ply_records(filename: str, chunks, header: bool = True) -> int:
-    """The same file as ``write_ply`` from per-view record arrays (``fuse_views(as_records=True)``), streamed chunk by chunk;
-    ``header=False`` writes the bare records (eval.py's per-rank parts).  Returns the number of vertices."""
-    total = sum(len(c) for c in chunks)
-    os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
-    with open(filename, "wb") as f:
-        if header:
-            f.write(ply_header(total))
-        for c in chunks:
-            c.tofile(f)
-    return total
 
 
 # ---- round 5: the scan's PLY body packed on the device -----------------------------------------------------------------------

@@ -1484,7 +1484,7 @@ class PointPacker:
     def __init__(self, capacity: int, device, max_views: int = 1024, normals: bool = False) -> None:
         self.capacity = int(capacity)
         self.normals = bool(normals)
-        self.record_size = 27 if self.normals else 15  # x y z [nx ny nz] red green blue
+        self.record_size = 27 if self.normals else 15  # x y z [nx ny nz] red green blue: ply.vertex_dtype(True, normals)
         self.records = torch.empty((self.record_size * self.capacity,), dtype=torch.uint8, device=device)
         self.cursor = torch.zeros((1,), dtype=torch.int64, device=device)
         self.view_counts = torch.zeros((max_views,), dtype=torch.int32, device=device)

@@ -5,7 +5,7 @@ The two searches are HIP kernels (csrc/pointcloud.hip): pmn_reduce_round, the gr
 pmn_nn_distance, the nearest-neighbour distance in both directions.  Both read a uniform grid over sorted points; building it is
 plumbing and uses torch on the device (cell coordinates -> 63-bit key -> torch.sort), as are the masks and the statistics (a gather
 from the ObsMask volume, a dot product, boolean selects, one sort for the median, float64 sums: a few elementwise launches per scan).
-There is no CPU path: the searches refuse host tensors.
+There is no CPU path: the searches refuse host tensors.  The clouds come from ply.read_ply_vertices.
 
 The same grid serves cloud cleaning (clean_cloud.py): pmn_knn_distance and pmn_radius_count are the k nearest
 neighbours and the number of points within a radius, and statistical_outliers / radius_outliers the two filters built on them.
@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import PmnError, check
+from .ply import read_ply_vertices  # noqa: F401  (the clouds and meshes that are scored)
 
 # defaults chosen from the sweep recorded in DESIGN.md 13
 NN_CELL = 2.0          # cell of the nearest-neighbour grids, in scene units (DTU: millimetres)
@@ -37,66 +38,7 @@ CLEAN_CELL_POINTS = 8.0      # default_cell: mean number of points per occupied 
 CLEAN_MAX_DIST_CELLS = 16.0  # default max_dist of statistical_outliers, in cells
 
 
-# ---- files --------------------------------------------------------------------------------------------------------------------
-
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
-              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
-
-
-def read_ply_vertices(path: str) -> np.ndarray:
-    """The ``vertex`` element of a PLY as [n,3] float32 (x, y, z).  binary_little_endian, binary_big_endian or ascii; other scalar
-    vertex properties (colours, normals) are skipped; elements after ``vertex`` (faces) are ignored.  Reads what fusion.write_ply
-    writes and DTU's Points/stl/stl%03d_total.ply.  ValueError (naming the file) for a list property inside ``vertex``, a missing
-    x / y / z, or an element before ``vertex`` (its size would have to be parsed to find the vertices)."""
-    with open(path, "rb") as f:
-        if f.readline().strip() != b"ply":
-            raise ValueError(f"{path}: not a PLY file")
-        fmt, count, props, element, before = None, None, [], None, []
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError(f"{path}: PLY header has no end_header")
-            tok = line.decode("ascii", "replace").split()
-            if not tok or tok[0] in ("comment", "obj_info"):
-                continue
-            if tok[0] == "format":
-                fmt = tok[1]
-            elif tok[0] == "element":
-                element = tok[1]
-                if element == "vertex":
-                    count = int(tok[2])
-                elif count is None:
-                    before.append(element)
-            elif tok[0] == "property" and element == "vertex":
-                if tok[1] == "list":
-                    raise ValueError(f"{path}: list property {tok[-1]!r} inside the vertex element is not supported")
-                if tok[1] not in _PLY_TYPES:
-                    raise ValueError(f"{path}: unknown property type {tok[1]!r}")
-                props.append((tok[2], _PLY_TYPES[tok[1]]))
-            elif tok[0] == "end_header":
-                break
-        if count is None:
-            raise ValueError(f"{path}: no vertex element")
-        if before:
-            raise ValueError(f"{path}: element {before[0]!r} precedes vertex")
-        names = [p[0] for p in props]
-        for axis in "xyz":
-            if axis not in names:
-                raise ValueError(f"{path}: the vertex element has no property {axis!r}")
-        if fmt == "ascii":
-            cols = [names.index(a) for a in "xyz"]
-            rows = np.loadtxt(f, dtype=np.float64, max_rows=count, usecols=cols, ndmin=2) if count else np.zeros((0, 3))
-            if len(rows) != count:
-                raise ValueError(f"{path}: {len(rows)} vertices where the header says {count}")
-            return np.ascontiguousarray(rows, np.float32)
-        if fmt not in ("binary_little_endian", "binary_big_endian"):
-            raise ValueError(f"{path}: unknown PLY format {fmt!r}")
-        end = "<" if fmt == "binary_little_endian" else ">"
-        rec = np.fromfile(f, dtype=np.dtype([(n, end + t) for n, t in props]), count=count)
-        if len(rec) != count:
-            raise ValueError(f"{path}: {len(rec)} vertices where the header says {count}")
-    return np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32)
-
+# ---- mask files ---------------------------------------------------------------------------------------------------------------
 
 def _load_fields(path: str, fields) -> Dict[str, np.ndarray]:
     if not os.path.isfile(path):

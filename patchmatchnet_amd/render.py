@@ -1,6 +1,6 @@
 """A mesh or a point cloud drawn into a scan's cameras on the device: the z-buffered projection the rest of the
-pipeline lacks (pmn_raster_triangles / pmn_splat_points / pmn_raster_resolve), orbit cameras for a model without scan cameras, and a PLY
-reader for models this library did not write.  There is no CPU path: the renderer refuses a host device."""
+pipeline lacks (pmn_raster_triangles / pmn_splat_points / pmn_raster_resolve), orbit cameras for a model without scan cameras; the PLY
+reader for models this library did not write is ply.read_ply_model.  There is no CPU path: the renderer refuses a host device."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -8,8 +8,9 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops, pointcloud
+from . import _lib, ops
 from ._lib import PmnError
+from .ply import read_ply_model  # noqa: F401  (the models that are drawn)
 from .tsdf import camera21
 
 
@@ -120,101 +121,6 @@ def orbit_cameras(bounds: Sequence[float], n: int, h: int, w: int, fov: float = 
 
 
 # ---- models -------------------------------------------------------------------------------------------------------------------------
-
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
-              "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8",
-              "float64": "<f8"}
-
-
-def read_ply_model(path: str):
-    """A mesh or a cloud from a PLY file -> dict(vertices [n,3] float32, faces [m,3] int32 | None, colors [n,3] uint8 | None, normals
-    [n,3] float32 | None).  binary_little_endian files are read in full: a ``vertex`` element (first) with x y z and any other scalar
-    properties in any order (red green blue / diffuse_red ... as uchar give the colours, nx ny nz the normals), scalar-only elements in
-    between, and an optional ``face`` element with one list property (count uchar, indices int or uint; all faces triangles) next to
-    any scalar properties.  That covers both kinds of fused.ply, mesh.ply and ground-truth meshes with more or fewer vertex properties
-    than ours.  An ascii or big-endian file is read as a cloud of positions (pointcloud.read_ply_vertices).  PmnError naming the file
-    for anything else."""
-    try:
-        with open(path, "rb") as f:
-            lines = []
-            while True:
-                line = f.readline()
-                if not line or len(lines) > 4096:
-                    raise PmnError(f"{path}: not a PLY file (no end_header)")
-                lines.append(line.decode("ascii", "replace").strip())
-                if lines[-1] == "end_header":
-                    break
-            if lines[0] != "ply":
-                raise PmnError(f"{path}: not a PLY file")
-            fmt = next((ln.split()[1] for ln in lines if ln.startswith("format ")), "")
-            if fmt != "binary_little_endian":
-                nf = [int(ln.split()[2]) for ln in lines if ln.startswith("element face ") and len(ln.split()) == 3]
-                if any(nf):
-                    raise PmnError(f"{path}: a {fmt or 'PLY'} file with {nf[0]} faces: only binary_little_endian meshes can be read "
-                                   f"(its vertices alone would be drawn as a see-through cloud)")
-                try:
-                    return {"vertices": pointcloud.read_ply_vertices(path), "faces": None, "colors": None, "normals": None}
-                except ValueError as e:
-                    raise PmnError(f"{path}: neither a mesh nor a cloud this tool can read ({e})") from e
-            elements = []  # (name, count, [(kind, name, type...)])
-            for ln in lines:
-                tok = ln.split()
-                if tok[:1] == ["element"] and len(tok) == 3:
-                    elements.append((tok[1], int(tok[2]), []))
-                elif tok[:1] == ["property"] and elements:
-                    if tok[1] == "list" and len(tok) == 5:
-                        elements[-1][2].append(("list", tok[4], tok[2], tok[3]))
-                    elif len(tok) == 3:
-                        elements[-1][2].append(("scalar", tok[2], tok[1]))
-                    else:
-                        raise PmnError(f"{path}: malformed PLY property line '{ln}'")
-            if not elements or elements[0][0] != "vertex":
-                raise PmnError(f"{path}: the first PLY element is not 'vertex'")
-            out = {"faces": None}
-            for name, count, props in elements:
-                unknown = [p[2] for p in props if p[0] == "scalar" and p[2] not in _PLY_TYPES] + \
-                          [t for p in props if p[0] == "list" for t in p[2:] if t not in _PLY_TYPES]
-                if unknown:
-                    raise PmnError(f"{path}: unknown PLY property type {unknown[0]}")
-                lists = [p for p in props if p[0] == "list"]
-                if name == "vertex":
-                    if lists:
-                        raise PmnError(f"{path}: a list property inside the vertex element")
-                    rec = np.fromfile(f, np.dtype([(p[1], _PLY_TYPES[p[2]]) for p in props]), count)
-                    if len(rec) != count or any(c not in rec.dtype.names for c in "xyz"):
-                        raise PmnError(f"{path}: the vertex element is truncated or has no x y z")
-                    names = rec.dtype.names
-                    out["vertices"] = np.stack([rec[c].astype(np.float32) for c in "xyz"], 1) if count else np.zeros((0, 3), np.float32)
-                    out["normals"] = np.stack([rec[c].astype(np.float32) for c in ("nx", "ny", "nz")], 1) \
-                        if all(c in names for c in ("nx", "ny", "nz")) else None
-                    out["colors"] = None
-                    for trio in (("red", "green", "blue"), ("diffuse_red", "diffuse_green", "diffuse_blue")):
-                        if all(c in names and rec.dtype[c] == np.uint8 for c in trio):
-                            out["colors"] = np.stack([rec[c] for c in trio], 1)
-                            break
-                elif not lists:
-                    f.seek(count * np.dtype([(p[1], _PLY_TYPES[p[2]]) for p in props]).itemsize, 1)
-                elif name == "face" and len(lists) == 1 and _PLY_TYPES[lists[0][2]] == "u1" and _PLY_TYPES[lists[0][3]] in ("<i4", "<u4"):
-                    fields = []
-                    for p in props:
-                        fields += [("_n", "u1"), ("_v", "<i4", (3,))] if p[0] == "list" else [(p[1], _PLY_TYPES[p[2]])]
-                    rec = np.fromfile(f, np.dtype(fields), count)
-                    if len(rec) != count or (count and (rec["_n"] != 3).any()):
-                        raise PmnError(f"{path}: the face element is truncated or has a face that is not a triangle")
-                    faces = np.ascontiguousarray(rec["_v"], np.int32)
-                    if count and (faces.min() < 0 or faces.max() >= len(out["vertices"])):
-                        raise PmnError(f"{path}: a face refers to a vertex that does not exist")
-                    out["faces"] = faces if count else None
-                    break  # nothing after the faces is needed
-                elif name == "face" and count:
-                    raise PmnError(f"{path}: the face element's properties ({' / '.join(' '.join(p[1:]) for p in props)}) are not one "
-                                   f"'list uchar int|uint' of triangle indices next to scalars: the mesh cannot be read")
-                else:
-                    break  # a list element that is not the faces: what came before it is the model
-            return out
-    except OSError as e:
-        raise PmnError(f"{path}: cannot read the model ({e})") from e
-
 
 def upload_model(model: dict, device) -> dict:
     """The arrays of read_ply_model as contiguous device tensors (None stays None)."""

@@ -1,17 +1,17 @@
 """A surface mesh from a scan's depth maps: a dense truncated-signed-distance volume integrated on the device
-(pmn_tsdf_integrate), its iso-surface by marching tetrahedra (pmn_mt_count / pmn_mt_emit), the grid heuristics of mesh.py and the PLY
-mesh files; and the same volume stored in 8 x 8 x 8 blocks near the surface only (section 18: SparseTsdfVolume), for scenes whose
+(pmn_tsdf_integrate), its iso-surface by marching tetrahedra (pmn_mt_count / pmn_mt_emit), the grid heuristics of mesh.py (the PLY
+mesh files are ply.write_ply_mesh / ply.read_ply_mesh); and the same volume stored in 8 x 8 x 8 blocks near the surface only (section 18: SparseTsdfVolume), for scenes whose
 dense lattice would not fit.  There is no CPU path: the volumes refuse a host device."""
 from __future__ import annotations
 
-import os
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, fusion, ops
+from . import _lib, ops
 from ._lib import PmnError
+from .ply import PLY_FACE, mesh_header, read_ply_mesh, write_ply_mesh  # noqa: F401  (mesh.ply)
 
 MAX_VOXELS = 2 ** 29  # mesh.py --max_voxels: 24 B per sample with colour = 12.9 GB
 MAX_BLOCKS = 2 ** 20  # mesh.py --max_blocks: as many pooled samples
@@ -241,84 +241,3 @@ def choose_grid(points: torch.Tensor, footprint: Optional[torch.Tensor] = None, 
     g = trunc if grow else 0.0
     origin = np.asarray([lo[c] - g for c in range(3)], np.float32)
     return origin, voxel, trunc, dims, note
-
-
-# ---- files ---------------------------------------------------------------------------------------------------------------------
-
-PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])  # property list uchar int vertex_indices: 13 bytes
-
-
-def mesh_header(nv: int, nf: int, colors: bool, normals: bool) -> bytes:
-    h = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % nv
-    if normals:
-        h += "property float nx\nproperty float ny\nproperty float nz\n"
-    if colors:
-        h += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-    return (h + "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % nf).encode("ascii")
-
-
-def _vertex_dtype(colors: bool, normals: bool) -> np.dtype:
-    if colors:
-        return fusion.PLY_VERTEX_NORMALS if normals else fusion.PLY_VERTEX
-    names = ("x", "y", "z", "nx", "ny", "nz") if normals else ("x", "y", "z")
-    return np.dtype([(n, "<f4") for n in names])
-
-
-def write_ply_mesh(path: str, vertices, faces, colors=None, normals=None) -> None:
-    """Binary little-endian PLY: the vertex element of fusion.write_ply (x y z [nx ny nz] [red green blue]) followed by
-    ``element face`` with ``property list uchar int vertex_indices`` (13 bytes per triangle).  Arrays or tensors."""
-    host = lambda a: None if a is None else (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
-    vertices, faces, colors, normals = host(vertices), host(faces), host(colors), host(normals)
-    n = len(vertices)
-    if faces.ndim != 2 or faces.shape[1] != 3 or (len(faces) and (faces.min() < 0 or faces.max() >= n)):
-        raise ValueError("write_ply_mesh: faces must be [m,3] indices into the vertices")
-    if colors is not None:
-        rec = fusion.ply_records(vertices, colors, normals)
-    else:
-        rec = np.empty(n, _vertex_dtype(False, normals is not None))
-        raw = rec.view(np.uint8).reshape(n, rec.dtype.itemsize)
-        raw[:, :12] = np.ascontiguousarray(vertices, "<f4").view(np.uint8).reshape(n, 12)
-        if normals is not None:
-            raw[:, 12:24] = np.ascontiguousarray(normals, "<f4").view(np.uint8).reshape(n, 12)
-    frec = np.empty(len(faces), PLY_FACE)
-    frec["n"] = 3
-    frec["v"] = faces
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "wb") as f:
-        f.write(mesh_header(n, len(faces), colors is not None, normals is not None))
-        rec.tofile(f)
-        frec.tofile(f)
-
-
-def read_ply_mesh(path: str):
-    """(vertices [n,3] float32, faces [m,3] int32, colors [n,3] uint8 | None, normals [n,3] float32 | None) of a file
-    write_ply_mesh wrote; ValueError (naming the file) for anything else."""
-    with open(path, "rb") as f:
-        lines = []
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError(f"{path}: PLY header has no end_header")
-            lines.append(line.decode("ascii", "replace").strip())
-            if lines[-1] == "end_header":
-                break
-        if lines[:2] != ["ply", "format binary_little_endian 1.0"] or not lines[2].startswith("element vertex "):
-            raise ValueError(f"{path}: not a binary little-endian PLY mesh")
-        nv = int(lines[2].split()[2])
-        at = [n for n, ln in enumerate(lines) if ln.startswith("element face ")]
-        if len(at) != 1 or lines[at[0] + 1:] != ["property list uchar int vertex_indices", "end_header"]:
-            raise ValueError(f"{path}: expected one face element with 'property list uchar int vertex_indices'")
-        nf = int(lines[at[0]].split()[2])
-        props = [ln.split()[1:] for ln in lines[3:at[0]]]
-        names = tuple(p[1] for p in props)
-        colors, normals = names[-3:] == ("red", "green", "blue"), names[3:6] == ("nx", "ny", "nz")
-        dt = _vertex_dtype(colors, normals)
-        if names != dt.names:
-            raise ValueError(f"{path}: vertex properties {names} are not a mesh this library writes")
-        rec = np.fromfile(f, dt, nv)
-        frec = np.fromfile(f, PLY_FACE, nf)
-        if len(rec) != nv or len(frec) != nf or (nf and (frec["n"] != 3).any()):
-            raise ValueError(f"{path}: truncated, or a face that is not a triangle")
-    col = lambda *k: np.stack([rec[n] for n in k], 1) if nv else np.zeros((0, 3), rec.dtype[k[0]])
-    return (col("x", "y", "z"), np.ascontiguousarray(frec["v"]), col("red", "green", "blue") if colors else None,
-            col("nx", "ny", "nz") if normals else None)
