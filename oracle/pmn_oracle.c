@@ -5,6 +5,10 @@
  * patchmatchnet_amd/csrc.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
  * load it.  Nothing in the product path links, imports or calls anything in oracle/.
  *
+ * Deliberate departures from the reference (everything else restates it):
+ *   - warp_position: a point on or behind the source camera is replaced by (2w, 2h, 1), not (w, h, 1), so that it samples nothing
+ *     also on a source map smaller than the reference's (where the reference's value lands on the last texel).
+ *
  * Each function cites the reference lines it follows (paths relative to the PatchmatchNet reference
  * checkout) and, where the arithmetic lives in PyTorch itself, the ATen semantics it restates
  * (ATen/native/GridSampler.h: grid_sampler_unnormalize / clip_coordinates / bilinear corner weights).
@@ -90,7 +94,10 @@ static inline float bil_fetch_zeros(const float *plane, int h, int w, const bil_
 
 /* Un-normalised source-image sample position of reference pixel (x,y) at depth d.
  * module.py:161-164  p = (rot @ [x,y,1]) * d + trans
- * module.py:166-169  p.z <= 1e-3  ->  p = (w, h, 1)     (w,h = REFERENCE map size)
+ * module.py:166-169  p.z <= 1e-3  ->  p = (w, h, 1)     (w,h = REFERENCE map size): a point that samples nothing.  The chain
+ *                    carries it to (w (ws-1)/(w-1), h (hs-1)/(h-1)), outside every tap only of a source map as large as the
+ *                    reference's (on a smaller one: the last texel); the replacement here is (2w, 2h, 1), which the
+ *                    same chain carries outside any map, as pmn_pose_position (csrc/pmn_common.hpp) has it
  * module.py:170-173  g = p.xy / p.z ; normalise with (w-1)/2, (h-1)/2
  * module.py:175-181  grid_sample(align_corners=True) un-normalises with the SOURCE map size */
 static inline void warp_position(const float *rot, const float *trans, float x, float y, float d,
@@ -101,9 +108,9 @@ static inline void warp_position(const float *rot, const float *trans, float x, 
     float px = rx * d + trans[0];
     float py = ry * d + trans[1];
     float pz = rz * d + trans[2];
-    if (pz <= 1e-3f) {
-        px = (float)w;
-        py = (float)h;
+    if (!(pz > 1e-3f)) {
+        px = (float)(2 * w);
+        py = (float)(2 * h);
         pz = 1.0f;
     }
     float gx = px / pz, gy = py / pz;

@@ -175,7 +175,12 @@ __device__ __forceinline__ PmnPose pmn_make_pose(const float* __restrict__ P, fl
     return q;
 }
 
-// returns false for a hypothesis behind / on the source camera: (w, h, 1) then lands outside every tap (the reference's sentinel)
+// returns false for a hypothesis behind / on the source camera, which samples nothing.  The reference replaces such a point by
+// (w, h, 1); its chain carries that to (w (ws-1)/(w-1), h (hs-1)/(h-1)), outside every tap only while the source map is as large as
+// the reference's (and fp32 rounding leaves it an ulp BELOW w at w = 30, 53, 98, 100, 192, 200 ...: a weight of ~1e-13 for the last
+// texel).  On a smaller source map it is the last texel itself with a weight of up to 1 (tests/test_camera_space_gpu.py, rig
+// `mixed`).  The replacement here is (2w, 2h, 1): the same chain, no instruction more, carries it to 2 (ws-1) w/(w-1) >= ws and
+// 2 (hs-1) h/(h-1) >= hs for every map of two texels and more (by 2/(w-1): far above rounding), where pmn_axis gives weights of zero.
 __device__ __forceinline__ bool pmn_pose_position(const PmnPose& q, float d, int h, int w, int hs, int ws, float& ix, float& iy) {
 #pragma clang fp contract(off)
     float px = q.rx * d + q.tx;
@@ -183,8 +188,8 @@ __device__ __forceinline__ bool pmn_pose_position(const PmnPose& q, float d, int
     float pz = q.rz * d + q.tz;
     const bool front = pz > 1e-3f;
     if (!front) {
-        px = (float)w;
-        py = (float)h;
+        px = (float)(2 * w);
+        py = (float)(2 * h);
         pz = 1.0f;
     }
     const float rz = pmn_rcp_refined(pz);

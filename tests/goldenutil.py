@@ -75,3 +75,19 @@ def rel_err(a, b, floor=1e-12):
 
 def abs_err(a, b):
     return float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
+
+
+def warp_sides(src_proj, ref_proj, depth, margin: float = 1e-4):
+    """(front, behind) [B,D,h,w] of a differentiable_warping call, decided in float64 and only where it is clear: pz beyond
+    1e-3 by ``margin`` x max(1, |t_z|) on either side.  A hypothesis on or behind the source camera samples nothing (exact zeros);
+    the reference's recorded outputs have, on a source map smaller than the reference's, its last texel there instead."""
+    P = np.matmul(np.asarray(src_proj, np.float64), np.linalg.inv(np.asarray(ref_proj, np.float64)))
+    d = np.asarray(depth, np.float64)
+    B, D, h, w = d.shape
+    y, x = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    front, behind = np.zeros(d.shape, bool), np.zeros(d.shape, bool)
+    for b in range(B):
+        pz = (P[b, 2, 0] * x + P[b, 2, 1] * y + P[b, 2, 2]) * d[b] + P[b, 2, 3]
+        m = margin * max(1.0, abs(P[b, 2, 3]))
+        front[b], behind[b] = pz > 1e-3 + m, pz < 1e-3 - m
+    return front, behind

@@ -47,12 +47,13 @@ class Row:
     H: int = 0               # confidence output size
     W: int = 0
     seed: int = 0
+    rig: str = ""            # warp: projections and depth samples of this rig of tests/camera_space.py at the row's map size
     device_only: bool = False  # needs > 48 KB of dynamic LDS: recording calls hipFuncSetAttribute, which needs a device
 
     @property
     def id(self) -> str:
         k = self.kernel.replace(" ", "").replace("true", "T").replace("false", "F")
-        return f"{self.op}-{k}-s{self.seed}"
+        return f"{self.op}-{k}-s{self.seed}" + (f"-{self.rig}" if self.rig else "")
 
 
 def _g(C: int, G: int, mode: int, DT: int, exact: bool) -> str:
@@ -180,6 +181,32 @@ def _rows() -> List[Row]:
         Row("normalize", "normalize_depth_kernel", B=2, h=17, w=19),
         Row("normalize", "normalize_depth_kernel", B=2, h=40, w=33),
     ]
+    # -- the production warp on rigs that are not DTU (tests/camera_space.py): projections and depth samples of the rig at the row's
+    #    map size.  `far`: their hypotheses leave the source image and fall behind it.  ring rows are 8 x 8 (see _rig_geometry);
+    #    mixed rows have a source map smaller than the reference's, with source 0 in front of the reference looking back at it.
+    #    (Appended after every other row: a row's seed is its place in the table, and the rows above keep theirs.)
+    G = dict(far=True)
+    R += [
+        Row("warp", _g(64, 8, 0, 16, True), C=64, G=8, D=16, B=2, h=9, w=12, N=2, rig="unit", **G),
+        Row("warp", _g(64, 8, 0, 16, False), C=64, G=8, D=12, h=7, w=10, N=2, rig="far_origin", **G),
+        Row("warp", _g(64, 8, 0, 16, True), C=64, G=8, D=16, h=8, w=8, N=3, rig="ring", **G),
+        Row("warp", _g(64, 8, 0, 16, False), C=64, G=8, D=9, B=2, h=9, w=12, N=1, rig="turned", **G),
+        Row("warp", _g(64, 8, 0, 16, True), C=64, G=8, D=16, h=12, w=16, hs=6, ws=8, N=3, rig="mixed", **G),
+        Row("warp", _g(64, 8, 0, 16, False), C=64, G=8, D=15, B=2, h=9, w=12, N=4, rig="wide", **G),
+        Row("warp", f"{P}<2, true>", pixelwise=True, C=64, G=8, D=64, B=2, h=9, w=12, N=2, rig="unit", **G),
+        Row("warp", f"{P}<2, false>", pixelwise=True, C=64, G=8, D=48, h=7, w=10, N=2, rig="far_origin", **G),
+        Row("warp", f"{P}<2, true>", pixelwise=True, C=64, G=8, D=64, h=8, w=8, N=3, rig="ring", **G),
+        Row("warp", f"{P}<2, false>", pixelwise=True, C=64, G=8, D=20, B=2, h=9, w=12, N=1, rig="turned", **G),
+        Row("warp", f"{P}<2, false>", pixelwise=True, C=64, G=8, D=56, h=12, w=16, hs=6, ws=8, N=3, rig="mixed", **G),
+        Row("warp", f"{P}<2, true>", pixelwise=True, C=64, G=8, D=64, B=2, h=9, w=12, N=4, rig="wide", **G),
+    ]
+    for rig, size in (("ring", dict(h=8, w=8)), ("mixed", dict(h=12, w=16, hs=6, ws=8))):
+        R += [
+            Row("warp", _g(32, 8, 0, 16, True), C=32, G=8, D=16, N=3, rig=rig, **size, **G),
+            Row("warp", _g(16, 4, 0, 16, True), C=16, G=4, D=16, N=3, rig=rig, **size, **G),
+            Row("warp", _g(32, 8, 1, 64, False), pixelwise=True, C=32, G=8, D=24, N=3, rig=rig, **size, **G),
+            Row("warp", _g(16, 4, 1, 64, False), pixelwise=True, C=16, G=4, D=8, N=3, rig=rig, **size, **G),
+        ]
     # distinct seeds so that no two rows share inputs
     return [replace(r, seed=100 * i + r.seed) for i, r in enumerate(R)]
 
@@ -374,6 +401,40 @@ def _projection(rng, row: Row, v: int) -> np.ndarray:
     return P.astype(np.float32)
 
 
+RING_T = 4.5                    # depth of the ring rows' camera opposite the reference
+RING_PZ = (1, 2, 3)             # planted hypotheses on the axis pixel: pz = k * 2**-12 (2.4e-4 .. 7.3e-4), between 0 and the front test
+
+
+def _rig_geometry(row: Row):
+    """rel_proj [B,N,4,4] and depth samples [B,D,h,w] of the row's rig (tests/camera_space.py): sample b % rig.B, its first N source
+    views, intrinsics scaled to the row's h x w the way a stage scale would (rows 0 and 1 by w / W0 and h / H0), the reference's
+    float32 sequence for the projections.
+
+    ring rows: source 0 is the camera opposite the reference in its exact form -- on the axis at depth RING_T looking straight
+    back, p = (-x d + cx T, (y - 2 cy) d + cy T, T - d) -- and the pixel on the axis (cx, cy) = (w / 2, h / 2) gets hypotheses at
+    d = T - k 2**-12 in its first levels.  With cx, cy powers of two every operation of that chain is exact in float32, so these
+    hypotheses sit at pz = k 2**-12 for the kernel and for float64 alike: behind the front test, and at the source's principal point
+    for a front test at 0."""
+    import camera_space as CS
+    rig = CS.rigs()[row.rig]
+    B, N, D, h, w = row.B, row.N, row.D, row.h, row.w
+    assert N <= rig.V - 1
+    intr = rig.intrinsics.copy()
+    intr[:, :, 0] *= np.float32(w * rig.scale0 / CS.W_MAP)
+    intr[:, :, 1] *= np.float32(h * rig.scale0 / CS.H_MAP)
+    rel = CS.projections(rig, 1.0, np.float32, intr)
+    rel_proj = np.stack([rel[b % rig.B, :N] for b in range(B)]).astype(np.float32)
+    depth = np.stack([CS.hypotheses(rig, b % rig.B, D, h, w, seed=row.seed + b) for b in range(B)])
+    if row.rig == "ring":
+        cx, cy = w // 2, h // 2
+        assert cx & (cx - 1) == 0 and cy & (cy - 1) == 0 and D > len(RING_PZ)
+        T = RING_T
+        rel_proj[:, 0] = np.float32([[-1, 0, 0, cx * T], [0, 1, -2 * cy, cy * T], [0, 0, -1, T], [0, 0, 0, 1]])
+        for i, k in enumerate(RING_PZ):
+            depth[:, i, cy, cx] = np.float32(T - k * 2.0 ** -12)
+    return rel_proj, depth
+
+
 def inputs(row: Row) -> Dict[str, np.ndarray]:
     """Seeded fp32 inputs of the row's call, in the layouts patchmatchnet_amd.ops takes."""
     rng = np.random.default_rng(row.seed)
@@ -401,6 +462,8 @@ def inputs(row: Row) -> Dict[str, np.ndarray]:
         out["src_nhwc"] = _smooth(rng, (row.N, B, hs, ws, row.C))
         out["rel_proj"] = np.stack([np.stack([_projection(rng, row, v) for v in range(row.N)]) for _ in range(B)])
         out["depth_sample"] = rng.uniform(2.0, 8.0, (B, row.D, h, w)).astype(np.float32)
+        if row.rig:
+            out["rel_proj"], out["depth_sample"] = _rig_geometry(row)
         if not row.pixelwise:
             s = row.vw_shift
             out["view_weights"] = rng.uniform(0.05, 1.0, (B, row.N, h >> s, w >> s)).astype(np.float32)
@@ -585,6 +648,15 @@ def mistakes(row: Row, x: Dict[str, np.ndarray], ref: Dict[str, np.ndarray], mlp
                                                                                   (0, row.w - s.shape[3]))) for s in _planar_src(x)],
                                  x["rel_proj"], x["depth_sample"], x.get("view_weights"), row.vw_shift, mlps[0], mlps[1], row.G)
             out["reference size used for the source map"] = ("similarity", r["similarity"])
+        if row.rig and (row.hs or row.h) < row.h:
+            kw = {"sentinel": (min(row.w, row.ws or row.w) - 1, min(row.h, row.hs or row.h) - 1)}
+            r = R.warp_correlate(x["ref_nhwc"].transpose(0, 3, 1, 2), _planar_src(x), x["rel_proj"], x["depth_sample"],
+                                 x.get("view_weights"), row.vw_shift, mlps[0], mlps[1], row.G, warp_kw=kw)
+            out["sentinel of a behind-camera hypothesis lands inside a smaller source map"] = ("similarity", r["similarity"])
+        if row.rig == "ring":
+            r = R.warp_correlate(x["ref_nhwc"].transpose(0, 3, 1, 2), _planar_src(x), x["rel_proj"], x["depth_sample"],
+                                 x.get("view_weights"), row.vw_shift, mlps[0], mlps[1], row.G, warp_kw={"front_eps": 0.0})
+            out["front test at 0 instead of 1e-3"] = ("similarity", r["similarity"])
         if row.pixelwise and row.D > 1:
             out["view weight of the first hypothesis, not the max"] = ("view_weights", ref["responses"][:, :, 0])
     elif row.op == "aggregate":

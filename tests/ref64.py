@@ -22,23 +22,25 @@ def f64(a) -> np.ndarray:
 
 # ---- bilinear sampling (ATen grid_sampler_2d: corners nw, ne, sw, se; an out-of-range corner contributes nothing) ------------------
 
-def bilinear(src: np.ndarray, ix: np.ndarray, iy: np.ndarray) -> np.ndarray:
-    """src [C,H,W]; ix, iy un-normalised positions of any shape S -> [C, *S] (zero padding outside the map)."""
+def bilinear(src: np.ndarray, ix: np.ndarray, iy: np.ndarray, dtype=np.float64) -> np.ndarray:
+    """src [C,H,W]; ix, iy un-normalised positions of any shape S -> [C, *S] (zero padding outside the map).  ``dtype``: the type
+    every operation runs in (float64: the yardstick; float32: ATen's own arithmetic, tests/camera_space.py)."""
     C, H, W = src.shape
-    ix, iy = f64(ix), f64(iy)
-    # positions far outside cannot reach a texel: clamp them before the integer conversion
-    ix = np.clip(ix, -4.0, W + 4.0)
-    iy = np.clip(iy, -4.0, H + 4.0)
+    T = np.dtype(dtype).type
+    ix, iy = np.asarray(ix, dtype), np.asarray(iy, dtype)
+    # positions far outside (or not a number) cannot reach a texel: clamp them before the integer conversion
+    ix = np.where(np.isnan(ix), T(-4.0), np.clip(ix, T(-4.0), T(W + 4.0)))
+    iy = np.where(np.isnan(iy), T(-4.0), np.clip(iy, T(-4.0), T(H + 4.0)))
     x0, y0 = np.floor(ix), np.floor(iy)
-    out = np.zeros((C,) + ix.shape, np.float64)
-    flat = src.reshape(C, H * W)
+    out = np.zeros((C,) + ix.shape, dtype)
+    flat = np.asarray(src, dtype).reshape(C, H * W)
     for dy in (0, 1):
         for dx in (0, 1):
-            xx, yy = x0 + dx, y0 + dy
-            wgt = (1.0 - np.abs(ix - xx)) * (1.0 - np.abs(iy - yy))
+            xx, yy = x0 + T(dx), y0 + T(dy)
+            wgt = (T(1.0) - np.abs(ix - xx)) * (T(1.0) - np.abs(iy - yy))
             ok = (xx >= 0) & (xx <= W - 1) & (yy >= 0) & (yy <= H - 1)
             idx = (np.clip(yy, 0, H - 1) * W + np.clip(xx, 0, W - 1)).astype(np.int64)
-            out += flat[:, idx] * np.where(ok, wgt, 0.0)
+            out += flat[:, idx] * np.where(ok, wgt, T(0.0))
     return out
 
 
@@ -134,29 +136,46 @@ def mlp(x: np.ndarray, net, sigmoid: bool) -> np.ndarray:
 
 # ---- warping (module.py:130-181) + group-wise correlation (patchmatch.py:193-203) ----------------------------------------------------
 
-def warp_positions(P: np.ndarray, depth: np.ndarray, h: int, w: int, hs: int, ws: int):
+def warp_positions(P: np.ndarray, depth: np.ndarray, h: int, w: int, hs: int, ws: int, dtype=np.float64, front_eps: float = 1e-3,
+                   sentinel=None, details: bool = False, xy=None):
     """P = relative projection src_proj @ inv(ref_proj) [4,4]; depth [D,h,w] -> (ix, iy) [D,h,w] in the source map.  A point on or
-    behind the source camera (z <= 1e-3) is replaced by (w, h, 1), as the reference does."""
-    P = f64(P)
-    y, x = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
-    d = f64(depth)
-    r = [P[i, 0] * x + P[i, 1] * y + P[i, 2] for i in range(3)]
-    px, py, pz = (r[i] * d + P[i, 3] for i in range(3))
-    behind = pz <= 1e-3
-    px, py, pz = np.where(behind, float(w), px), np.where(behind, float(h), py), np.where(behind, 1.0, pz)
-    xn = (px / pz) / ((w - 1) / 2.0) - 1.0
-    yn = (py / pz) / ((h - 1) / 2.0) - 1.0
-    return (xn + 1.0) / 2.0 * (ws - 1), (yn + 1.0) / 2.0 * (hs - 1)
+    behind the source camera (z <= 1e-3) samples NOTHING: the reference replaces it by (w, h, 1), which its chain carries to
+    (w (ws-1)/(w-1), h (hs-1)/(h-1)) -- outside every tap of a source map as large as the reference's, but on the last texel of a
+    smaller one (its recorded output has that: tests/golden ops_small.npz, case B); here its position is (ws, hs), outside every
+    tap of any map (pmn_pose_position replaces the point by (2w, 2h, 1), which lands outside any map as well).
+
+    ``dtype``: the type every operation runs in, in the reference's order (module.py:161-173 and grid_sample's un-normalisation):
+    float64 is the yardstick, float32 the reference's own arithmetic.  ``front_eps`` / ``sentinel`` (the position (ix, iy) given to
+    a point behind the camera) restate mistakes (tests/kernel_space.py).  ``details``: also returns {"front", "pz"}, pz before the
+    sentinel replaces it.  ``xy``: reference pixels (x, y) of depth's shape instead of the h x w grid."""
+    T = np.dtype(dtype).type
+    P = np.asarray(P, dtype)
+    if xy is None:
+        y, x = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing="ij")
+    else:
+        x, y = np.asarray(xy[0], dtype), np.asarray(xy[1], dtype)
+    d = np.asarray(depth, dtype)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        r = [(P[i, 0] * x + P[i, 1] * y) + P[i, 2] for i in range(3)]
+        px, py, pz0 = (r[i] * d + P[i, 3] for i in range(3))
+        front = pz0 > T(front_eps)  # (a NaN depth is not in front: `pz <= 1e-3` is false for it, but so is every later comparison)
+        px, py, pz = np.where(front, px, T(w)), np.where(front, py, T(h)), np.where(front, pz0, T(1.0))
+        xn = (px / pz) / (T(w - 1) / T(2.0)) - T(1.0)
+        yn = (py / pz) / (T(h - 1) / T(2.0)) - T(1.0)
+        ix, iy = (xn + T(1.0)) / T(2.0) * T(ws - 1), (yn + T(1.0)) / T(2.0) * T(hs - 1)
+    sx, sy = (ws, hs) if sentinel is None else sentinel
+    ix, iy = np.where(front, ix, T(sx)), np.where(front, iy, T(sy))
+    return (ix, iy, {"front": front, "pz": pz0}) if details else (ix, iy)
 
 
-def view_similarity(ref: np.ndarray, src: np.ndarray, rel_proj: np.ndarray, depth: np.ndarray, G: int) -> np.ndarray:
+def view_similarity(ref: np.ndarray, src: np.ndarray, rel_proj: np.ndarray, depth: np.ndarray, G: int, warp_kw=None) -> np.ndarray:
     """ref [B,C,h,w], src [B,C,hs,ws] (one source view), rel_proj [B,4,4], depth [B,D,h,w] -> [B,G,D,h,w]:
-    mean over the C/G channels of a group of warped source * reference."""
+    mean over the C/G channels of a group of warped source * reference.  ``warp_kw``: keyword arguments of warp_positions."""
     B, C, h, w = ref.shape
     hs, ws = src.shape[2:]
     out = []
     for b in range(B):
-        ix, iy = warp_positions(rel_proj[b], depth[b], h, w, hs, ws)
+        ix, iy = warp_positions(rel_proj[b], depth[b], h, w, hs, ws, **(warp_kw or {}))
         warped = bilinear(f64(src[b]), ix, iy)  # [C,D,h,w]
         prod = warped * f64(ref[b])[:, None]
         out.append(prod.reshape(G, C // G, *prod.shape[1:]).mean(axis=1))
@@ -164,7 +183,8 @@ def view_similarity(ref: np.ndarray, src: np.ndarray, rel_proj: np.ndarray, dept
 
 
 def warp_correlate(ref: np.ndarray, srcs: Sequence[np.ndarray], rel_proj: np.ndarray, depth: np.ndarray,
-                   view_weights: Optional[np.ndarray], vw_shift: int, similarity_net, pixelwise_net, G: int) -> Dict[str, np.ndarray]:
+                   view_weights: Optional[np.ndarray], vw_shift: int, similarity_net, pixelwise_net, G: int,
+                   warp_kw=None) -> Dict[str, np.ndarray]:
     """Evaluation up to the SimilarityNet MLP (patchmatch.py:179-224, 565-566).  srcs: N maps [B,C,hs,ws]; view_weights [B,N,h>>s,
     w>>s] (read at (y>>s, x>>s)) or None: then PixelwiseNet computes them (max over D of its sigmoid response, patchmatch.py:695-702).
     -> similarity [B,G,D,h,w], cost [B,D,h,w], view_weights [B,N,h,w], responses [B,N,D,h,w] (None when weights were given)."""
@@ -173,7 +193,7 @@ def warp_correlate(ref: np.ndarray, srcs: Sequence[np.ndarray], rel_proj: np.nda
     wsum = 1e-5
     vws, resps = [], []
     for v, src in enumerate(srcs):
-        sim = view_similarity(ref, src, rel_proj[:, v], depth, G)
+        sim = view_similarity(ref, src, rel_proj[:, v], depth, G, warp_kw)
         if view_weights is None:
             resp = mlp(sim, pixelwise_net, sigmoid=True)  # [B,D,h,w]
             resps.append(resp)

@@ -65,7 +65,16 @@ def test_differentiable_warping_op(name):
     out = P.differentiable_warping(t(g[f"{name}_src"]), t(g[f"{name}_src_proj"]), t(g[f"{name}_ref_proj"]),
                                    t(g[f"{name}_depth"]))
     ref = g[f"{name}_warped"]
-    assert GU.abs_err(n(out), ref) < 5e-5
+    # in front of the source camera: the reference's recorded values; on or behind it: nothing is sampled.  (Case B, a 7 x 9 source
+    # under a 10 x 12 reference: there the reference's sentinel (w, h, 1) lands on the last texel of the smaller map; case A, equal
+    # sizes: the reference has zeros too, and the whole output is compared as before.)
+    front, behind = GU.warp_sides(g[f"{name}_src_proj"], g[f"{name}_ref_proj"], g[f"{name}_depth"])
+    assert front.mean() > 0.4 and behind.mean() > 0.2 and (front | behind).mean() > 0.99
+    f, bh = np.broadcast_to(front[:, None], ref.shape), np.broadcast_to(behind[:, None], ref.shape)
+    assert GU.abs_err(n(out)[f], ref[f]) < 5e-5
+    assert (n(out)[bh] == 0).all()
+    if name == "A":
+        assert GU.abs_err(n(out), ref) < 5e-5
     oracle = O.differentiable_warping(g[f"{name}_src"], g[f"{name}_src_proj"], g[f"{name}_ref_proj"], g[f"{name}_depth"])
     frac_zero_mismatch = float(((n(out) == 0) != (oracle == 0)).mean())
     assert frac_zero_mismatch < 1e-3  # the inverse may differ in the last bit between LAPACK and the GPU solver

@@ -18,11 +18,19 @@ def test_differentiable_warping_known_answers(name):
     out = O.differentiable_warping(g[f"{name}_src"], g[f"{name}_src_proj"], g[f"{name}_ref_proj"], g[f"{name}_depth"])
     ref = g[f"{name}_warped"]
     assert out.shape == ref.shape
-    assert GU.abs_err(out, ref) < 2e-5
-    # the negative-depth sentinel must produce exact zeros in the same places (case A has them)
+    # A hypothesis on or behind the source camera samples nothing.  Case A (equal sizes): the reference's sentinel gives exact zeros
+    # in the same places.  Case B (a 7 x 9 source under a 10 x 12 reference): the reference's sentinel (w, h, 1) lands on the last
+    # texel of the smaller map there; the oracle, like the kernels, has exact zeros.  In front of the camera: the reference's values.
+    front, behind = GU.warp_sides(g[f"{name}_src_proj"], g[f"{name}_ref_proj"], g[f"{name}_depth"])
+    assert front.mean() > 0.4 and behind.mean() > 0.2 and (front | behind).mean() > 0.99
+    f, bh = np.broadcast_to(front[:, None], ref.shape), np.broadcast_to(behind[:, None], ref.shape)
+    assert GU.abs_err(out[f], ref[f]) < 2e-5
+    assert (out[bh] == 0).all()
+    np.testing.assert_array_equal(out[f] == 0, ref[f] == 0)
     if name == "A":
         assert (ref == 0).any()
-    np.testing.assert_array_equal(out == 0, ref == 0)
+        assert GU.abs_err(out, ref) < 2e-5
+        np.testing.assert_array_equal(out == 0, ref == 0)
 
 
 @pytest.mark.parametrize("case", ["default", "variant", "counts", "dilations", "rig"])
