@@ -811,6 +811,48 @@ int pmn_mesh_distance(const float *ref_xyz, const long long *ref_keys, long long
                       const int *faces, int n_faces, const float *query, const int *order, long long n_query, double max_dist,
                       double *dist, int *face, double *closest, int *invalid, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  Mesh simplification by vertex clustering
+ * (patchmatchnet_amd/meshops.py simplify_clustering; tests/simplify_ref.py is the numpy form; the reference has
+ * no counterpart).  The caller sorts the vertices into cubic cells of side `cell` whose lattice has its corner at origin_host (HOST
+ * double[3]) and dims_host (HOST int[3], each 1 .. 2^30) cells; a CLUSTER is an occupied cell, clusters are numbered 0 .. n_clusters - 1
+ * in ascending order of the key (z * dims[1] + y) * dims[0] + x, cluster [n_vertices] int32 names every vertex's, and every cluster's
+ * mean position comes from pmn_voxel_mean.  vertices, faces, n_vertices and invalid as in the mesh entry points above; n_faces is
+ * 1 .. PMN_MESH_SIMPLIFY_MAX_FACES (3 * n_faces fits an int32), else PMN_ERR_SHAPE.  No floating-point atomics, no LDS, no lane waits
+ * for another lane: every output is a function of the mesh and the parameters alone, whatever the launch shape or the run.
+ *
+ * pmn_mesh_remap_faces, a thread per face (a, b, c): corner_cluster [n_faces][3] int32 = (cluster[a], cluster[b], cluster[c]) in the
+ * face's own order; flag [n_faces] uint8 = 1 if two of the three agree (out_faces [n_faces][3] int32 is then that triple), else 0 and
+ * out_faces = the triple ROTATED so that its smallest entry comes first, which keeps the orientation.  A face with an index outside
+ * [0, n_vertices) adds 1 to *invalid and gets flag 2, out_faces (-1, -1, -1) and corner_cluster (n_clusters, n_clusters, n_clusters);
+ * nothing is read through it.  One launch; the int32 counter is the feature's only atomic.
+ *
+ * pmn_mesh_cluster_place, a lane per cluster r: out [n_clusters][3] float32, the cluster's representative.  corners [3 * n_faces] int32
+ * holds the entries 3 * f + c of all face corners, STABLY sorted by corner_cluster (entries of invalid faces last), and corner_starts
+ * [n_clusters + 1] int64 the first position of every cluster's run, so a run is in ascending (face, corner) order; cluster_keys
+ * [n_clusters] int64 the clusters' keys; mean [n_clusters][3] float32.  Float64, products and sums in the written order, no
+ * contraction, IEEE division and sqrt, everything RELATIVE TO THE CELL'S CENTRE ctr_k = origin_k + ((double)cell_k + 0.5) * cell:
+ *   per run entry, f = entry / 3 with vertices A, B, C in the face's order:  a = (double)A - ctr (b, c likewise);  e1 = b - a, e2 = c - a;
+ *   n = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x);  w = sqrt((n.x n.x + n.y n.y) + n.z n.z); nothing if w is
+ *   zero or not finite;  h = n / w;  q = (h.x a.x + h.y a.y) + h.z a.z;  g = w * h;
+ *   Sxx += g.x h.x, Sxy += g.x h.y, Sxz += g.x h.z, Syy += g.y h.y, Syz += g.y h.z, Szz += g.z h.z;  t += q * g;  W += w.
+ * A face with two or three corners in the cluster is in the run once per corner and contributes that often.  A run of at most
+ * PMN_MESH_PLACE_LONG_RUN entries is summed by one lane in run order from 0.0; a longer run by a wave: lane l adds the entries l,
+ * l + 64, ... in run order to 0.0 and the 64 values meet in pmn_voxel_mean's butterfly (x_l += x_(l ^ 32), then 16, 8, 4, 2, 1).
+ *   lambda = stiffness * W (stiffness finite, > 0), mt = (double)mean - ctr;  (S + lambda I) x = t + lambda mt  by LDL^T:
+ *   d0 = Sxx + lambda;  l10 = Sxy / d0;  l20 = Sxz / d0;  d1 = (Syy + lambda) - l10 * Sxy;  u = Syz - l10 * Sxz;  l21 = u / d1;
+ *   d2 = ((Szz + lambda) - l20 * Sxz) - l21 * u;  y0 = t.x + lambda * mt.x;  y1 = (t.y + lambda * mt.y) - l10 * y0;
+ *   y2 = ((t.z + lambda * mt.z) - l20 * y0) - l21 * y1;  x.z = y2 / d2;  x.y = y1 / d1 - l21 * x.z;  x.x = (y0 / d0 - l10 * x.y) - l20 * x.z.
+ * S is positive semi-definite with trace W, so the condition number of S + lambda I is at most (1 + stiffness) / stiffness.  W zero
+ * or not finite gives x = mt.  x is clamped per component to [-cell / 2, cell / 2] and out = (float)(ctr + x), one rounding.  Every
+ * vertex of the cluster lies in the same cell, hence within sqrt(3) * cell of out.  One launch, no scratch memory. */
+#define PMN_MESH_PLACE_LONG_RUN 256
+#define PMN_MESH_SIMPLIFY_MAX_FACES 715827882
+int pmn_mesh_remap_faces(const int *faces, int n_faces, int n_vertices, const int *cluster, int n_clusters, int *corner_cluster,
+                         int *out_faces, unsigned char *flag, int *invalid, void *stream);
+int pmn_mesh_cluster_place(const float *vertices, int n_vertices, const int *faces, int n_faces, const int *corners,
+                           const long long *corner_starts, const long long *cluster_keys, int n_clusters, const float *mean,
+                           const double *origin_host, double cell, const int *dims_host, double stiffness, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,8 +10,9 @@ truncated-signed-distance volume on the device (pmn_tsdf_integrate) and the iso-
 observed.  --volume sparse keeps only the 8 x 8 x 8-sample blocks near the surface: a scene whose dense lattice
 would exceed --max_voxels keeps its natural voxel, and where both fit the mesh is the dense one.  --min_component_faces N and
 --keep_components K drop the floaters before the file is written: connected components with fewer than N faces, or outside the K
-largest.  One process on one ROCm GPU; torchrun
-is not supported."""
+largest.  --simplify K then clusters the vertices into cells of K voxels and
+writes one vertex per cluster, placed by the clusters' plane quadrics; simplify_mesh.py does the same to a file.
+One process on one ROCm GPU; torchrun is not supported."""
 import argparse
 import os
 import sys
@@ -45,6 +46,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="drop connected components with fewer faces than this (0 = off)")
     p.add_argument("--keep_components", type=int, default=0,
                    help="keep only this many connected components, the largest by face count (0 = off)")
+    p.add_argument("--simplify", type=float, default=0.0,
+                   help="cluster the vertices into cells of this many voxels, one vertex per cluster (> 1; 0 = off)")
     p.add_argument("--views_per_launch", type=int, default=8, help="views integrated per kernel launch (1..16)")
     return p
 
@@ -151,6 +154,14 @@ def mesh_scan(args, scan, device):
             vertices, faces, colors, normals, min_faces=args.min_component_faces, keep_largest=args.keep_components, return_counts=True)
         cleaned = "{}: {} components, {} kept; {} vertices and {} faces dropped".format(
             name, found, kept, nv0 - vertices.shape[0], nf0 - faces.shape[0])
+    simplified = None
+    if args.simplify > 0:
+        nv0, nf0 = vertices.shape[0], faces.shape[0]
+        if nv0:
+            vertices, faces, colors, normals = meshops.simplify_clustering(vertices, faces, args.simplify * voxel, colors=colors,
+                                                                           normals=normals)
+        simplified = "{}: simplified at cell {:.6g} ({:g} voxels): {} vertices, {} faces -> {} vertices, {} faces".format(
+            name, args.simplify * voxel, args.simplify, nv0, nf0, vertices.shape[0], faces.shape[0])
     torch.cuda.synchronize(device)
     t4 = time.perf_counter()
     out = os.path.join(args.output_folder, scan, "mesh.ply")
@@ -166,6 +177,8 @@ def mesh_scan(args, scan, device):
               faces.shape[0], t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, out))
     if cleaned:
         print(cleaned)
+    if simplified:
+        print(simplified)
 
 
 def main(argv=None) -> int:
@@ -185,6 +198,8 @@ def main(argv=None) -> int:
         raise PmnError("--max_blocks must be at least 1")
     if args.min_component_faces < 0 or args.keep_components < 0:
         raise PmnError("--min_component_faces and --keep_components must be >= 0")
+    if args.simplify != 0 and not (args.simplify > 1 and args.simplify < float("inf")):
+        raise PmnError("--simplify must be 0 (off) or a finite number of voxels greater than 1, got {}".format(args.simplify))
     device = torch.device(args.device)
     if device.type != "cuda":
         raise PmnError("--device {}: mesh.py runs on a ROCm GPU (no CPU fallback)".format(args.device))

@@ -454,3 +454,235 @@ extern "C" int pmn_mesh_distance(const float* ref_xyz, const long long* ref_keys
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
+
+// ---- simplification by vertex clustering --------------------------------------------------------------------
+// meshops.simplify_clustering sorts the vertices into cubic cells (a cluster per occupied cell, numbered in ascending key order), takes
+// every cluster's mean from pmn_voxel_mean, and calls the two kernels below.  tests/simplify_ref.py restates both in numpy.
+//
+// pmn_mesh_remap_faces, a thread per face (a, b, c): corner_cluster = (cluster[a], cluster[b], cluster[c]) in the face's own order;
+// flag 1 and that triple if two of the three agree; else flag 0 and the triple rotated so that its smallest entry comes first -- a
+// rotation, so the orientation stays.  A face with an index outside [0, nv) is counted into *invalid, gets flag 2, the triple
+// (-1, -1, -1) and corner_cluster (m, m, m), and nothing is read through it.
+//
+// pmn_mesh_cluster_place, a lane per cluster r.  corners holds 3 f + c for every face corner, stably sorted by corner_cluster, so the run
+// [corner_starts[r], corner_starts[r + 1]) of cluster r is in ascending (face, corner) order.  Everything is float64, nothing contracted,
+// IEEE division and sqrt, and RELATIVE TO THE CELL'S CENTRE ctr_k = origin_k + ((double)cell_k + 0.5) * cell (cell_k decoded from the
+// cluster's key), so that a scene at coordinates of 10^4 keeps the plane offsets.  Per corner of face (A, B, C), f = entry / 3:
+//   a = (double)A - ctr (likewise b, c);  e1 = b - a, e2 = c - a;
+//   n = (e1.y e2.z - e1.z e2.y,  e1.z e2.x - e1.x e2.z,  e1.x e2.y - e1.y e2.x);  w = sqrt((n.x n.x + n.y n.y) + n.z n.z);
+//   nothing if w is zero or not finite;  h = n / w;  q = (h.x a.x + h.y a.y) + h.z a.z  (the plane is h.p = q);  g = w * h;
+//   Sxx += g.x h.x, Sxy += g.x h.y, Sxz += g.x h.z, Syy += g.y h.y, Syz += g.y h.z, Szz += g.z h.z;  t += q * g;  W += w
+// in this order of accumulators, each starting from 0.0.  A face with two or three corners in the cluster is in its run once per
+// corner and so contributes twice or three times: the weight of a face is its area times the number of its corners in the cluster.
+// A run of at most PMN_MESH_PLACE_LONG_RUN corners is summed by its lane in run order; a longer one by the wave, lane l taking the
+// entries l, l + 64, ... in run order and the 64 partial sums meeting in pmn_voxel_mean's butterfly (x_l += x_(l ^ 32), 16, 8, 4, 2, 1;
+// every lane then holds the same bits).  No atomics, no LDS, no lane waits for another: the result is a function of the mesh alone.
+// Then with lambda = stiffness * W and mt = (double)mean - ctr:  (S + lambda I) x = t + lambda mt  by LDL^T in the order
+//   d0 = Sxx + lambda;  l10 = Sxy / d0;  l20 = Sxz / d0;  d1 = (Syy + lambda) - l10 * Sxy;  u = Syz - l10 * Sxz;  l21 = u / d1;
+//   d2 = ((Szz + lambda) - l20 * Sxz) - l21 * u;  b = t + lambda * mt;  y0 = b.x;  y1 = b.y - l10 * y0;  y2 = (b.z - l20 * y0) - l21 * y1;
+//   x.z = y2 / d2;  x.y = y1 / d1 - l21 * x.z;  x.x = (y0 / d0 - l10 * x.y) - l20 * x.z
+// S is positive semi-definite with trace W (up to rounding), so the matrix has eigenvalues in [lambda, W + lambda]: its condition number
+// is at most (1 + stiffness) / stiffness whatever the faces.  W zero or not finite gives x = mt.  x is clamped per component to
+// [-cell / 2, cell / 2] (a projection onto the cell: continuous, no fallback branch) and out = (float)(ctr + x).
+
+#define MESH_Q 10  // Sxx Sxy Sxz Syy Syz Szz tx ty tz W
+
+struct MeshPlaceArgs {
+    const float* vertices;       // [nv][3]
+    const int* faces;            // [nt][3]
+    const int* corners;          // [3 nt]
+    const long long* starts;     // [m + 1]
+    const long long* keys;       // [m]
+    const float* mean;           // [m][3]
+    float* out;                  // [m][3]
+    int nv, nt, m;
+    long long dx, dy;            // the lattice's first two dimensions
+    double origin[3], cell, stiffness;
+};
+
+// adds the quadric of corner entry e, seen from (cx, cy, cz), to q[]
+__device__ __forceinline__ void mesh_place_corner(const MeshPlaceArgs& a, int e, double cx, double cy, double cz, double* q) {
+#pragma clang fp contract(off)
+    if ((unsigned)e >= 3u * (unsigned)a.nt) return;
+    const int f = e / 3;
+    const int ia = a.faces[3 * (size_t)f], ib = a.faces[3 * (size_t)f + 1], ic = a.faces[3 * (size_t)f + 2];
+    if (!(mesh_index_ok(ia, a.nv) && mesh_index_ok(ib, a.nv) && mesh_index_ok(ic, a.nv))) return;
+    const float* A = a.vertices + 3 * (size_t)ia;
+    const float* B = a.vertices + 3 * (size_t)ib;
+    const float* C = a.vertices + 3 * (size_t)ic;
+    const double ax = (double)A[0] - cx, ay = (double)A[1] - cy, az = (double)A[2] - cz;
+    const double bx = (double)B[0] - cx, by = (double)B[1] - cy, bz = (double)B[2] - cz;
+    const double gx = (double)C[0] - cx, gy = (double)C[1] - cy, gz = (double)C[2] - cz;
+    const double e1x = bx - ax, e1y = by - ay, e1z = bz - az;
+    const double e2x = gx - ax, e2y = gy - ay, e2z = gz - az;
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const double w = sqrt((nx * nx + ny * ny) + nz * nz);
+    if (!(w > 0.0) || !(w < __builtin_inf())) return;
+    const double hx = nx / w, hy = ny / w, hz = nz / w;
+    const double p = (hx * ax + hy * ay) + hz * az;
+    const double wx = w * hx, wy = w * hy, wz = w * hz;
+    q[0] += wx * hx;
+    q[1] += wx * hy;
+    q[2] += wx * hz;
+    q[3] += wy * hy;
+    q[4] += wy * hz;
+    q[5] += wz * hz;
+    q[6] += p * wx;
+    q[7] += p * wy;
+    q[8] += p * wz;
+    q[9] += w;
+}
+
+__global__ __launch_bounds__(256) void mesh_cluster_place_kernel(const MeshPlaceArgs a) {
+#pragma clang fp contract(off)
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool live = r < a.m;
+    const long long n_corners = 3LL * a.nt;
+    long long s = 0, len = 0;
+    double cx = 0.0, cy = 0.0, cz = 0.0;
+    if (live) {
+        s = a.starts[r];
+        long long e = a.starts[r + 1];
+        s = s < 0 ? 0 : s;
+        e = e > n_corners ? n_corners : e;
+        len = e > s ? e - s : 0;
+        const long long key = a.keys[r];
+        const long long kx = key % a.dx, ky = (key / a.dx) % a.dy, kz = key / (a.dx * a.dy);
+        cx = a.origin[0] + ((double)kx + 0.5) * a.cell;
+        cy = a.origin[1] + ((double)ky + 0.5) * a.cell;
+        cz = a.origin[2] + ((double)kz + 0.5) * a.cell;
+    }
+    double q[MESH_Q];
+#pragma unroll
+    for (int i = 0; i < MESH_Q; ++i) q[i] = 0.0;
+    const bool is_long = len > PMN_MESH_PLACE_LONG_RUN;
+    if (live && !is_long)
+        for (long long i = s; i < s + len; ++i) mesh_place_corner(a, a.corners[i], cx, cy, cz, q);
+    // the wave's long runs, one after the other (as voxel_mean_kernel walks them)
+    unsigned long long todo = __ballot(is_long);
+    while (todo) {
+        const int owner = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const long long rs = __shfl(s, owner, 64), rl = __shfl(len, owner, 64);
+        const double ox = __shfl(cx, owner, 64), oy = __shfl(cy, owner, 64), oz = __shfl(cz, owner, 64);
+        double part[MESH_Q];
+#pragma unroll
+        for (int i = 0; i < MESH_Q; ++i) part[i] = 0.0;
+        for (long long i = rs + lane; i < rs + rl; i += 64) mesh_place_corner(a, a.corners[i], ox, oy, oz, part);
+#pragma unroll
+        for (int i = 0; i < MESH_Q; ++i) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) part[i] += __shfl_xor(part[i], o, 64);
+            if (lane == owner) q[i] = part[i];
+        }
+    }
+    if (!live) return;
+    const double mx = (double)a.mean[3 * (size_t)r] - cx, my = (double)a.mean[3 * (size_t)r + 1] - cy,
+                 mz = (double)a.mean[3 * (size_t)r + 2] - cz;
+    double x = mx, y = my, z = mz;
+    const double W = q[9];
+    if (W > 0.0 && W < __builtin_inf()) {
+        const double lam = a.stiffness * W;
+        const double d0 = q[0] + lam;
+        const double l10 = q[1] / d0, l20 = q[2] / d0;
+        const double d1 = (q[3] + lam) - l10 * q[1];
+        const double u = q[4] - l10 * q[2];
+        const double l21 = u / d1;
+        const double d2 = ((q[5] + lam) - l20 * q[2]) - l21 * u;
+        const double y0 = q[6] + lam * mx;
+        const double y1 = (q[7] + lam * my) - l10 * y0;
+        const double y2 = ((q[8] + lam * mz) - l20 * y0) - l21 * y1;
+        z = y2 / d2;
+        y = y1 / d1 - l21 * z;
+        x = (y0 / d0 - l10 * y) - l20 * z;
+    }
+    const double half = a.cell * 0.5;
+    x = x > half ? half : x;
+    x = x < -half ? -half : x;
+    y = y > half ? half : y;
+    y = y < -half ? -half : y;
+    z = z > half ? half : z;
+    z = z < -half ? -half : z;
+    a.out[3 * (size_t)r] = (float)(cx + x);
+    a.out[3 * (size_t)r + 1] = (float)(cy + y);
+    a.out[3 * (size_t)r + 2] = (float)(cz + z);
+}
+
+__global__ __launch_bounds__(256) void mesh_remap_faces_kernel(const int* __restrict__ faces, int nt, int nv,
+                                                               const int* __restrict__ cluster, int m, int* corner_cluster,
+                                                               int* out_faces, unsigned char* flag, int* invalid) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= nt) return;
+    const size_t o = 3 * (size_t)f;
+    const int a = faces[o], b = faces[o + 1], c = faces[o + 2];
+    if (!(mesh_index_ok(a, nv) && mesh_index_ok(b, nv) && mesh_index_ok(c, nv))) {
+        atomicAdd(invalid, 1);
+        corner_cluster[o] = corner_cluster[o + 1] = corner_cluster[o + 2] = m;
+        out_faces[o] = out_faces[o + 1] = out_faces[o + 2] = -1;
+        flag[f] = 2;
+        return;
+    }
+    const int ca = cluster[a], cb = cluster[b], cc = cluster[c];
+    corner_cluster[o] = ca;
+    corner_cluster[o + 1] = cb;
+    corner_cluster[o + 2] = cc;
+    int r0 = ca, r1 = cb, r2 = cc;
+    if (cb < ca && cb < cc) {
+        r0 = cb;
+        r1 = cc;
+        r2 = ca;
+    } else if (cc < ca && cc < cb) {
+        r0 = cc;
+        r1 = ca;
+        r2 = cb;
+    }
+    out_faces[o] = r0;
+    out_faces[o + 1] = r1;
+    out_faces[o + 2] = r2;
+    flag[f] = (ca == cb || cb == cc || ca == cc) ? 1 : 0;
+}
+
+extern "C" int pmn_mesh_remap_faces(const int* faces, int n_faces, int n_vertices, const int* cluster, int n_clusters,
+                                    int* corner_cluster, int* out_faces, unsigned char* flag, int* invalid, void* stream) {
+    if (!cluster || !corner_cluster || !out_faces || !flag || !invalid) return PMN_ERR_ARG;
+    if (!faces) return PMN_ERR_ARG;
+    if (n_vertices < 1 || n_faces < 1 || n_vertices > 2147483647 - 255 || n_faces > PMN_MESH_SIMPLIFY_MAX_FACES) return PMN_ERR_SHAPE;
+    if (n_clusters < 1 || n_clusters > n_vertices) return PMN_ERR_ARG;
+    PMN_LAUNCH(mesh_remap_faces_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces, n_faces,
+               n_vertices, cluster, n_clusters, corner_cluster, out_faces, flag, invalid);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}
+
+extern "C" int pmn_mesh_cluster_place(const float* vertices, int n_vertices, const int* faces, int n_faces, const int* corners,
+                                      const long long* corner_starts, const long long* cluster_keys, int n_clusters, const float* mean,
+                                      const double* origin_host, double cell, const int* dims_host, double stiffness, float* out,
+                                      void* stream) {
+    if (!vertices || !faces || !corners || !corner_starts || !cluster_keys || !mean || !origin_host || !dims_host || !out)
+        return PMN_ERR_ARG;
+    if (n_vertices < 1 || n_faces < 1 || n_vertices > 2147483647 - 255 || n_faces > PMN_MESH_SIMPLIFY_MAX_FACES) return PMN_ERR_SHAPE;
+    if (n_clusters < 1 || n_clusters > n_vertices) return PMN_ERR_ARG;
+    if (!(cell > 0.0) || !std::isfinite(cell) || !(stiffness > 0.0) || !std::isfinite(stiffness)) return PMN_ERR_ARG;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(origin_host[i]) || dims_host[i] < 1 || dims_host[i] > (1 << 30)) return PMN_ERR_ARG;
+    MeshPlaceArgs a;
+    a.vertices = vertices;
+    a.faces = faces;
+    a.corners = corners;
+    a.starts = corner_starts;
+    a.keys = cluster_keys;
+    a.mean = mean;
+    a.out = out;
+    a.nv = n_vertices;
+    a.nt = n_faces;
+    a.m = n_clusters;
+    a.dx = dims_host[0];
+    a.dy = dims_host[1];
+    for (int i = 0; i < 3; ++i) a.origin[i] = origin_host[i];
+    a.cell = cell;
+    a.stiffness = stiffness;
+    PMN_LAUNCH(mesh_cluster_place_kernel, dim3((unsigned)((n_clusters + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}

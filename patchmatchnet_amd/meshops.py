@@ -3,19 +3,24 @@ removal of small components -- the floaters of a TSDF mesh -- and points drawn o
 (pmn_mesh_face_samples / pmn_mesh_sample), which is what a surface is scored by.  A mesh is ``vertices`` [Nv,3] float32 and ``faces``
 [Nt,3] int32 on a ROCm GPU, as ops.mt_extract returns them.  There is no CPU path: everything that launches refuses a host tensor.
 tests/meshops_ref.py restates all of it in numpy.  build_face_grid / point_mesh_distance (pmn_mesh_distance) are
-the exact distance from points to the surface itself; tests/mesh_distance_ref.py is their numpy form."""
+the exact distance from points to the surface itself; tests/mesh_distance_ref.py is their numpy form.  simplify_clustering (DESIGN.md
+section 28, pmn_mesh_remap_faces / pmn_mesh_cluster_place) shrinks a mesh to one vertex per occupied cell; tests/simplify_ref.py is its
+numpy form."""
 from __future__ import annotations
 
 import ctypes
 import math
+import time
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import PmnError, check
 from .ops import _dev_as, _ptr, _stream
-from .pointcloud import Grid, _cell_order, _points, _sort_into_grid
+from .pointcloud import Grid, _cell_order, _cells, _points, _sort_into_grid
+from .registration import voxel_mean
 
 INT32_MAX = 2 ** 31 - 1
 # settings of build_face_grid, chosen from the sweep recorded in DESIGN.md 25 (profiles/mesh_distance_bench.log); they change the time
@@ -322,3 +327,184 @@ def point_mesh_distance(query: torch.Tensor, face_grid: FaceGrid, max_dist: floa
         _raise_invalid(what, bad, int(face_grid.vertices.shape[0]))
     out = (dist,) + ((face.long(),) if return_face else ()) + ((closest,) if return_closest else ())
     return out[0] if len(out) == 1 else out
+
+
+# ---- simplification by vertex clustering -------------------------------------------------------------------------
+
+def _lexsort_rows(tri: torch.Tensor) -> torch.Tensor:
+    """int64 [n]: the rows of an int [n,3] tensor in ascending (column 0, 1, 2) order, equal rows in input order (three stable sorts)."""
+    order = torch.sort(tri[:, 2], stable=True).indices
+    for col in (1, 0):
+        order = order[torch.sort(tri[order, col], stable=True).indices]
+    return order
+
+
+def _canonical_face_order(faces: torch.Tensor) -> torch.Tensor:
+    """int64 [Nt]: the faces ordered by their vertex triple rotated so that the smallest index comes first, then by the rotation that
+    took them there: an order that does not know where a face stood in the array.  Faces that tie are the same triple in the same
+    rotation, i.e. the same numbers to every kernel.  Nothing is read through an index."""
+    a, b, c = faces.unbind(1)
+    shift = torch.where((b < a) & (b < c), 1, torch.where((c < a) & (c < b), 2, 0))
+    rot = torch.gather(faces, 1, (shift[:, None] + torch.arange(3, device=faces.device)) % 3)
+    order = torch.sort(shift, stable=True).indices
+    for col in (2, 1, 0):
+        order = order[torch.sort(rot[order, col], stable=True).indices]
+    return order
+
+
+def simplify_clustering(vertices: torch.Tensor, faces: torch.Tensor, cell: float, colors: Optional[torch.Tensor] = None,
+                        normals: Optional[torch.Tensor] = None, origin=None, placement: str = "quadric", stiffness: float = 1e-3,
+                        return_map: bool = False, timings: Optional[dict] = None):
+    """Quadric vertex clustering: (vertices, faces, colors, normals[, vertex_map]) of the mesh with one vertex per occupied cubic cell
+    of side ``cell``.  The lattice's corner is min(vertices) - cell / 2 unless ``origin`` (three finite numbers, none above the
+    minimum) is given; the cells, their key and the stable sort are voxel_downsample's, and clusters are numbered in ascending key
+    order.  pmn_voxel_mean gives every cluster's mean position, colour (bytes as floats, back to bytes by floorf(c + 0.5f) clamped) and
+    normal (renormalised in float64; a mean of zero or non-finite length gives a zero normal).  ``placement="quadric"``: the
+    representative is the point of pmn_mesh_cluster_place -- the minimiser of the area-weighted squared distances to the planes of the
+    faces at the cluster's corners plus ``stiffness`` * (their total weight) * the squared distance to the mean, clamped to the cell
+    (the kernel is handed the faces sorted by their rotated vertex triple, so the order of the input faces changes no bit of it);
+    the system's condition number is at most (1 + stiffness) / stiffness.  ``placement="mean"``: the mean itself.  Either way every
+    input vertex lies in its representative's cell, hence within sqrt(3) * cell of it.
+    Faces are mapped through the clusters (pmn_mesh_remap_faces); a face with two corners in one cluster is dropped, among faces with
+    the same rotated triple the one with the lowest input index stays (opposite orientations are different faces), kept faces keep
+    their input order and start with their smallest index, clusters that no kept face names are dropped.  ``vertex_map`` [Nv] int32 is
+    the output index of every input vertex, or -1.  A mesh that collapses to nothing returns empty tensors.  Everything is a function
+    of the mesh and the parameters alone, bit for bit.  PmnError for a host tensor, non-finite vertices, a cell or stiffness that is
+    not positive and finite, a lattice beyond a 63-bit key, and faces that name a vertex outside the array (counted, never
+    dereferenced).  ``timings``, if a dict, receives the seconds of each stage (it adds synchronisations)."""
+    what = "simplify_clustering"
+    cell, stiffness = float(cell), float(stiffness)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise PmnError(f"{what}: cell must be positive and finite, got {cell}")
+    if not (stiffness > 0.0 and math.isfinite(stiffness)):
+        raise PmnError(f"{what}: stiffness must be positive and finite, got {stiffness}")
+    if placement not in ("quadric", "mean"):
+        raise PmnError(f"{what}: placement must be 'quadric' or 'mean', got {placement!r}")
+    faces = _faces(faces, what)
+    vertices = _dev_as(vertices, f"{what}: vertices", torch.float32)
+    dev, nv, nt = faces.device, vertices.shape[0], faces.shape[0]
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.device != dev:
+        raise PmnError(f"{what}: vertices must be [Nv,3] on {dev}")
+    if nv > INT32_MAX - 255 or nt > _lib.MESH_SIMPLIFY_MAX_FACES:
+        raise PmnError(f"{what}: at most 2^31 - 256 vertices and {_lib.MESH_SIMPLIFY_MAX_FACES} faces, got {nv} and {nt}")
+    colors = _per_vertex(colors, "colors", torch.uint8, nv, dev, what)
+    normals = _per_vertex(normals, "normals", torch.float32, nv, dev, what)
+    if nt and not nv:
+        _raise_invalid(what, nt, 0)
+
+    def result(v, f, c, n, vmap):
+        return (v, f, c, n) + ((vmap,) if return_map else ())
+
+    def empty():
+        return result(vertices.new_zeros((0, 3)), faces.new_zeros((0, 3)), None if colors is None else colors.new_zeros((0, 3)),
+                      None if normals is None else normals.new_zeros((0, 3)), torch.full((nv,), -1, dtype=torch.int32, device=dev))
+
+    if nv == 0:
+        return empty()
+    bad = int((~torch.isfinite(vertices)).any(1).sum())
+    if bad:
+        raise PmnError(f"{what}: {bad} vertices have non-finite coordinates")
+
+    clock = [time.perf_counter()]
+
+    def lap(stage):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            timings[stage] = timings.get(stage, 0.0) + now - clock[0]
+            clock[0] = now
+
+    # clusters: the cells, the key and the stable sort of registration.voxel_downsample
+    lo = vertices.min(0).values.double().cpu().numpy()
+    if origin is None:
+        org = lo - cell / 2
+    else:
+        org = np.asarray(origin, np.float64).reshape(-1)
+        if org.shape != (3,) or not np.isfinite(org).all() or (org > lo).any():
+            raise PmnError(f"{what}: origin must be three finite numbers, none above the vertices' minimum {lo.tolist()}")
+    c = _cells(vertices, org.tolist(), cell)
+    dims = (c.max(0).values + 1).cpu().tolist()
+    if max(dims) > 2 ** 30 or dims[0] * dims[1] * dims[2] >= 2 ** 62:
+        raise PmnError(f"{what}: a lattice of {dims} cells does not fit a 63-bit key; use a larger cell")
+    keys = (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
+    keys, perm = torch.sort(keys, stable=True)
+    head = torch.ones(nv, dtype=torch.bool, device=dev)
+    head[1:] = keys[1:] != keys[:-1]
+    run = torch.cumsum(head, 0) - 1                        # the cluster of every sorted vertex
+    m = int(run[-1]) + 1
+    starts = torch.cat([torch.nonzero(head).reshape(-1), head.new_full((1,), nv, dtype=torch.int64)]).contiguous()
+    cluster = torch.empty(nv, dtype=torch.int32, device=dev)
+    cluster[perm] = run.to(torch.int32)
+    lap("sort")
+
+    # means: pmn_voxel_mean over the sorted vertices, colours and normals as further columns
+    cols = [t.float() for t in (colors, normals) if t is not None]
+    attr = torch.cat(cols, 1)[perm].contiguous() if cols else None
+    mean = voxel_mean(vertices[perm].contiguous(), starts, attr)
+    mean, mean_attr = mean if attr is not None else (mean, None)
+    out_colors = out_normals = None
+    if colors is not None:
+        out_colors = torch.floor(mean_attr[:, :3] + 0.5).clamp_(0.0, 255.0).to(torch.uint8)
+    if normals is not None:
+        n64 = mean_attr[:, -3:].double()
+        length = torch.sqrt((n64[:, 0] * n64[:, 0] + n64[:, 1] * n64[:, 1]) + n64[:, 2] * n64[:, 2])
+        ok = (length > 0) & torch.isfinite(length)
+        out_normals = torch.where(ok[:, None], n64 / torch.where(ok, length, torch.ones_like(length))[:, None],
+                                  torch.zeros_like(n64)).float()
+    lap("means")
+    if nt == 0:
+        return empty()
+
+    # faces through the clusters, and the corner list of every cluster
+    L = _lib.lib()
+    corner_cluster = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    tri = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    flag = torch.empty(nt, dtype=torch.uint8, device=dev)
+    invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(L.pmn_mesh_remap_faces(faces.data_ptr(), nt, nv, cluster.data_ptr(), m, corner_cluster.data_ptr(), tri.data_ptr(),
+                                     flag.data_ptr(), invalid.data_ptr(), _stream(faces)), "pmn_mesh_remap_faces")
+    lap("remap")
+    if placement == "quadric":
+        # the kernel sums a run in (face, corner) order: it gets the faces in an order of their own, not the array's, so that
+        # permuting the input faces changes no bit of a representative
+        canon = _canonical_face_order(faces)
+        faces_canon = faces[canon].contiguous()
+        by_cluster = torch.sort(corner_cluster[canon].reshape(-1), stable=True)
+        corners = by_cluster.indices.to(torch.int32)
+        corner_starts = torch.searchsorted(by_cluster.values, torch.arange(m + 1, dtype=torch.int32, device=dev)).contiguous()
+        cluster_keys = keys[starts[:-1]].contiguous()
+        rep = torch.empty((m, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(L.pmn_mesh_cluster_place(vertices.data_ptr(), nv, faces_canon.data_ptr(), nt, corners.data_ptr(), corner_starts.data_ptr(),
+                                           cluster_keys.data_ptr(), m, mean.data_ptr(), (ctypes.c_double * 3)(*org.tolist()), cell,
+                                           (ctypes.c_int * 3)(*dims), stiffness, rep.data_ptr(), _stream(faces)),
+                  "pmn_mesh_cluster_place")
+    else:
+        rep = mean
+    lap("placement")
+
+    # compaction (integer torch, as remove_components): one face per rotated triple, the clusters the kept faces name
+    order = _lexsort_rows(tri)
+    st = tri[order]
+    first = torch.ones(nt, dtype=torch.bool, device=dev)
+    first[1:] = (st[1:] != st[:-1]).any(1)
+    fkeep = torch.zeros(nt, dtype=torch.bool, device=dev)
+    fkeep[order] = first & (flag[order] == 0)
+    named = torch.zeros(m + 1, dtype=torch.bool, device=dev)
+    named[torch.where(fkeep[:, None], tri, torch.full_like(tri, m)).reshape(-1).long()] = True  # slot m takes the dropped faces
+    named = named[:m]
+    vscan = torch.cumsum(named, 0, dtype=torch.int64)
+    fscan = torch.cumsum(fkeep, 0, dtype=torch.int64)
+    nkv, nkf, bad = torch.stack((vscan[-1], fscan[-1], invalid[0].long())).tolist()  # the host read that sizes the outputs
+    if bad:
+        _raise_invalid(what, bad, nv)
+    vidx = torch.searchsorted(vscan, torch.arange(1, nkv + 1, dtype=torch.int64, device=dev))
+    fidx = torch.searchsorted(fscan, torch.arange(1, nkf + 1, dtype=torch.int64, device=dev))
+    new_faces = (vscan[tri[fidx].long()] - 1).to(torch.int32)
+    cl = cluster.long()
+    vmap = torch.where(named[cl], vscan[cl] - 1, torch.full_like(cl, -1)).to(torch.int32)
+    out = result(rep[vidx], new_faces, None if out_colors is None else out_colors[vidx],
+                 None if out_normals is None else out_normals[vidx], vmap)
+    lap("compaction")
+    return out
