@@ -147,18 +147,29 @@ def _field(dims, kind):
     return np.clip(d / 3.0, -1, 1).astype(np.float32)
 
 
-def _compare_extraction(name, tsdf_np, weight_np, origin, voxel, min_weight, rgb=None, cweight=None):
+def _compare_extraction(name, tsdf_np, weight_np, origin, voxel, min_weight, rgb=None, cweight=None, oracles=None, empty=False):
+    """ops.mt_extract against the oracle under this file's gates -> (vertices, faces) of the kernels.  ``oracles`` = the (float32,
+    float64) results of R.extract on these inputs where the caller has them already; ``empty``: the case has no surface, and the
+    kernels must return empty outputs of the right shape, type and device (tests/test_mesher_space_gpu.py)."""
     from patchmatchnet_amd import ops
     dev = torch.device("cuda")
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    up = lambda a: None if a is None else torch.from_numpy(np.array(a)).to(dev)  # a contiguous copy: the rows' arrays are read-only
     v, f, c, n = ops.mt_extract(up(tsdf_np), up(weight_np), origin, voxel, min_weight, up(rgb), up(cweight), normals=True)
     torch.cuda.synchronize()
+    o32, o64 = oracles or (R.extract(tsdf_np, weight_np, origin, voxel, min_weight, rgb, cweight, True, np.float32),
+                           R.extract(tsdf_np, weight_np, origin, voxel, min_weight, rgb, cweight, True, np.float64))
+    if empty:
+        assert len(o32["faces"]) == 0 and len(o32["vertices"]) == 0, name
+        for t, dtype in ((v, torch.float32), (f, torch.int32), (n, torch.float32)) + (((c, torch.uint8),) if rgb is not None else ()):
+            assert tuple(t.shape) == (0, 3) and t.dtype == dtype and t.device.type == "cuda", (name, t.shape, t.dtype, t.device)
+        assert (c is None) == (rgb is None), name
+        print(f"{name}: no vertex, no face")
+        return v.cpu().numpy(), f.cpu().numpy()
     v, f, n = v.cpu().numpy(), f.cpu().numpy(), n.cpu().numpy()
-    o32 = R.extract(tsdf_np, weight_np, origin, voxel, min_weight, rgb, cweight, True, np.float32)
-    o64 = R.extract(tsdf_np, weight_np, origin, voxel, min_weight, rgb, cweight, True, np.float64)
     assert len(o32["faces"]) > 0, name
     assert v.shape == o32["vertices"].shape and f.shape == o32["faces"].shape, (name, v.shape, f.shape, o32["vertices"].shape)
     assert np.array_equal(f, o32["faces"]), name
+    assert np.array_equal(np.isfinite(v), np.isfinite(o32["vertices"])), name
     ulp = np.spacing(np.maximum(np.abs(o32["vertices"]), np.float32(1e-30)))
     dpos = float((np.abs(v.astype(np.float64) - o32["vertices"]) / ulp).max())
     own = float(np.abs(o32["normals"].astype(np.float64) - o64["normals"]).max())

@@ -51,7 +51,7 @@ def soup(vertices, faces, colors=None, normals=None):
             first = np.where(less, c, first)
         order = (first[:, None] + np.arange(3)[None]) % 3
         tri = tri[np.arange(len(tri))[:, None], order]
-    return _sorted_rows(tri.reshape(len(tri), -1)), _sorted_rows(rec)
+    return _sorted_rows(tri.reshape(len(tri), 3 * rec.shape[1])), _sorted_rows(rec)  # (not -1: a mesh may have no triangle)
 
 
 def assert_same_mesh(a, b, what=""):
@@ -179,6 +179,31 @@ def restrict(vol, samples):
     if vol["rgb"] is not None:
         out["rgb"] = np.where(samples[None], vol["rgb"], np.float32(0))
         out["cweight"] = np.where(samples, vol["cweight"], np.float32(0))
+    return out
+
+
+def pool_of(vol, keep):
+    """Dense planes (tsdf_ref.new_volume's dict, any sides >= 2) as the pool of the blocks ``keep`` ([nbz,nby,nbx] bool) -> dict: blocks
+    int32 [B] ascending, table int32 [nbz,nby,nbx], tsdf / weight / cweight [B,8,8,8], rgb [3,B,8,8,8].  The samples of a border block
+    beyond the lattice hold what a fresh pool holds (tsdf 1, the rest 0)."""
+    nz, ny, nx = vol["tsdf"].shape
+    nbz, nby, nbx = keep.shape
+    assert (nbx, nby, nbz) == n_blocks((nx, ny, nz))
+    blocks = np.nonzero(keep.reshape(-1))[0].astype(np.int32)
+    table = np.full(keep.size, -1, np.int32)
+    table[blocks] = np.arange(len(blocks), dtype=np.int32)
+
+    def blocked(plane, fill):
+        full = np.full((nbz * BLOCK, nby * BLOCK, nbx * BLOCK), fill, np.float32)
+        full[:nz, :ny, :nx] = plane
+        p = full.reshape(nbz, BLOCK, nby, BLOCK, nbx, BLOCK).transpose(0, 2, 4, 1, 3, 5).reshape(-1, BLOCK, BLOCK, BLOCK)
+        return np.ascontiguousarray(p[blocks])
+
+    out = {"blocks": blocks, "table": table.reshape(keep.shape), "tsdf": blocked(vol["tsdf"], 1), "weight": blocked(vol["weight"], 0),
+           "rgb": None, "cweight": None}
+    if vol["rgb"] is not None:
+        out["rgb"] = np.stack([blocked(vol["rgb"][c], 0) for c in range(3)])
+        out["cweight"] = blocked(vol["cweight"], 0)
     return out
 
 
