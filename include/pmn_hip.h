@@ -853,6 +853,51 @@ int pmn_mesh_cluster_place(const float *vertices, int n_vertices, const int *fac
                            const long long *corner_starts, const long long *cluster_keys, int n_clusters, const float *mean,
                            const double *origin_host, double cell, const int *dims_host, double stiffness, float *out, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  Mesh smoothing by umbrella steps and vertex normals from the
+ * faces (patchmatchnet_amd/meshops.py smooth_taubin / smooth_laplacian / vertex_normals; tests/smooth_ref.py is
+ * the numpy form; the reference has no counterpart).  No floating-point atomics, no LDS, no lane waits for another lane: every output
+ * is a function of the mesh and the parameters alone, whatever the launch shape or the run.  Float64 from the float32 coordinates,
+ * products and sums in the written order, no contraction, IEEE division and sqrt.
+ *
+ * THE ROW RULE of both entry points.  A row (a run of a CSR structure) of at most PMN_MESH_SMOOTH_LONG_ROW entries is summed by one
+ * lane in row order from 0.0; a longer row by a wave: lane l adds the entries l, l + 64, ... in row order to 0.0 and the 64 values
+ * meet in pmn_voxel_mean's butterfly (x_l += x_(l ^ 32), then 16, 8, 4, 2, 1) -- the rule of pmn_mesh_cluster_place.
+ *
+ * pmn_mesh_smooth: n_steps umbrella steps over xyz [n_vertices][3] float32 (1 <= n_vertices <= 2^31 - 256, else PMN_ERR_SHAPE).
+ * starts [n_vertices + 1] int64 and neighbours [n_entries] int32 are the vertex adjacency in CSR form (row i = the neighbours of
+ * vertex i; n_entries >= 0, neighbours may be NULL only then); pinned [n_vertices] uint8 or NULL; factors_host: HOST double
+ * [n_steps], each finite (else PMN_ERR_ARG), 0 <= n_steps <= PMN_MESH_SMOOTH_MAX_STEPS.  Taubin's filter is lambda, mu, lambda, mu,
+ * ...; the plain Laplacian lambda, lambda, ....  One step, for vertex i with row r of d entries (starts clamped to [0, n_entries], a
+ * start beyond its end is an empty row), reading p and writing p':
+ *   d == 0 or pinned[i] != 0:  p'_i = p_i, bit for bit;
+ *   otherwise per component:   s = the row rule's sum over j in r of ((double)p_j - (double)p_i);  p'_i = (float)((double)p_i +
+ *   factor * (s / (double)d)):  the division, the product and the sum are rounded once each in float64, then one rounding to float32.
+ * The differences are taken relative to the vertex itself, so a scene at coordinates of 10^4 keeps them.  The CSR is not trusted: an
+ * entry outside [0, n_vertices) adds nothing to s (d stays the row's length) and, in the FIRST step only, 1 to *invalid (int32, zeroed
+ * by the caller), so *invalid is the number of such entries when n_steps >= 1.
+ * Steps ping-pong between out and scratch (each [n_vertices][3] float32) so that the last step writes out: step k (from 0) writes out
+ * when n_steps - 1 - k is even, step 0 reads xyz, xyz is never written.  n_steps = 0 copies xyz to out.  scratch may be NULL when
+ * n_steps <= 1.  out or scratch overlapping xyz or each other: PMN_ERR_ARG.  Every argument check returns before any launch.
+ * max(n_steps, 1) launches of ceil(n_vertices / 256) workgroups, a lane per vertex, no scratch memory.
+ *
+ * pmn_mesh_vertex_normals: out [n_vertices][3] float32, the area-weighted normal of every vertex.  faces [n_faces][3] int32 (1 ..
+ * PMN_MESH_SIMPLIFY_MAX_FACES, else PMN_ERR_SHAPE); corners [3 * n_faces] int32 holds the entries 3 * f + c of the face corners STABLY
+ * sorted by the vertex they name, and corner_starts [n_vertices + 1] int64 the first position of every vertex's run, so a run is in
+ * ascending (face, corner) order of the faces AS HANDED IN (meshops.vertex_normals hands them in _canonical_face_order, so that the
+ * order of the caller's faces changes no bit).  For vertex i, with A, B, C the vertices of face f = entry / 3 in the face's stored
+ * order:  e1 = (double)B - (double)A, e2 = (double)C - (double)A;  n += (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y -
+ * e1.y e2.x) by the row rule (the cross product carries the area weight);  length = sqrt((n.x n.x + n.y n.y) + n.z n.z);
+ * out_i = (float)(n / length), or zero when length is zero or not finite; flip != 0 negates the result (exactly).  The normal
+ * follows the right-hand rule of the stored winding.  An entry outside [0, 3 * n_faces) or a face with an index outside [0,
+ * n_vertices) adds nothing; such faces are counted into *invalid by a launch of their own.  Two launches, no scratch memory. */
+#define PMN_MESH_SMOOTH_LONG_ROW 256
+#define PMN_MESH_SMOOTH_MAX_STEPS 65536
+int pmn_mesh_smooth(const float *xyz, int n_vertices, const long long *starts, const int *neighbours, long long n_entries,
+                    const unsigned char *pinned, const double *factors_host, int n_steps, float *out, float *scratch, int *invalid,
+                    void *stream);
+int pmn_mesh_vertex_normals(const float *vertices, int n_vertices, const int *faces, int n_faces, const int *corners,
+                            const long long *corner_starts, int flip, float *out, int *invalid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,13 +10,20 @@ truncated-signed-distance volume on the device (pmn_tsdf_integrate) and the iso-
 observed.  --volume sparse keeps only the 8 x 8 x 8-sample blocks near the surface: a scene whose dense lattice
 would exceed --max_voxels keeps its natural voxel, and where both fit the mesh is the dense one.  --min_component_faces N and
 --keep_components K drop the floaters before the file is written: connected components with fewer than N faces, or outside the K
-largest.  --simplify K then clusters the vertices into cells of K voxels and
+largest (DESIGN.md section 19).  --smooth N then runs N iterations of Taubin's filter over the vertices (DESIGN.md section 30;
+--smooth_lambda, --smooth_mu, --smooth_boundary) and, unless --no_normals, replaces the normals by those of the smoothed faces;
+smooth_mesh.py does the same to a file.  --simplify K then clusters the vertices into cells of K voxels and
 writes one vertex per cluster, placed by the clusters' plane quadrics; simplify_mesh.py does the same to a file.
 One process on one ROCm GPU; torchrun is not supported."""
 import argparse
 import os
 import sys
 import time
+
+
+# pmn_mt_emit winds its triangles so that (B - A) x (C - A) points WITH the TSDF gradient it writes as the normal, from inside to outside
+# (measured on a meshed sphere: DESIGN.md section 30, tests/test_smooth_gpu.py), so normals recomputed from the faces are not flipped.
+MESHER_WINDING_FLIP = False
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -46,6 +53,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="drop connected components with fewer faces than this (0 = off)")
     p.add_argument("--keep_components", type=int, default=0,
                    help="keep only this many connected components, the largest by face count (0 = off)")
+    p.add_argument("--smooth", type=int, default=0,
+                   help="iterations of Taubin's filter over the mesh, before --simplify (0 = off)")
+    p.add_argument("--smooth_lambda", type=float, default=0.5, help="--smooth: the shrinking step's factor, in (0, 1]")
+    p.add_argument("--smooth_mu", type=float, default=-0.53, help="--smooth: the inflating step's factor, < -smooth_lambda")
+    p.add_argument("--smooth_boundary", type=str, default="fixed", choices=("fixed", "free"),
+                   help="--smooth: fixed leaves the vertices on an open edge where they are")
     p.add_argument("--simplify", type=float, default=0.0,
                    help="cluster the vertices into cells of this many voxels, one vertex per cluster (> 1; 0 = off)")
     p.add_argument("--views_per_launch", type=int, default=8, help="views integrated per kernel launch (1..16)")
@@ -154,6 +167,21 @@ def mesh_scan(args, scan, device):
             vertices, faces, colors, normals, min_faces=args.min_component_faces, keep_largest=args.keep_components, return_counts=True)
         cleaned = "{}: {} components, {} kept; {} vertices and {} faces dropped".format(
             name, found, kept, nv0 - vertices.shape[0], nf0 - faces.shape[0])
+    smoothed = None
+    if args.smooth > 0:
+        nb, mean_d, max_d = 0, 0.0, 0.0
+        if vertices.shape[0]:
+            adjacency = meshops.vertex_adjacency(faces, vertices.shape[0])
+            before = vertices
+            vertices = meshops.smooth_taubin(before, faces, args.smooth, args.smooth_lambda, args.smooth_mu,
+                                             boundary=args.smooth_boundary, adjacency=adjacency)
+            if normals is not None:  # of the geometry that is written, on the side the mesher's own normals point to
+                normals = meshops.vertex_normals(vertices, faces, flip=MESHER_WINDING_FLIP)
+            moved = (vertices.double() - before.double()).norm(dim=1) / voxel
+            nb, mean_d, max_d = int(adjacency.boundary.sum()), float(moved.mean()), float(moved.max())
+        smoothed = "{}: smoothed by {} Taubin iterations (lambda {:g}, mu {:g}, boundary {}): {} vertices, {} on the boundary; " \
+                   "displacement mean {:.4f}, max {:.4f} voxels".format(name, args.smooth, args.smooth_lambda, args.smooth_mu,
+                                                                         args.smooth_boundary, vertices.shape[0], nb, mean_d, max_d)
     simplified = None
     if args.simplify > 0:
         nv0, nf0 = vertices.shape[0], faces.shape[0]
@@ -177,6 +205,8 @@ def mesh_scan(args, scan, device):
               faces.shape[0], t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, out))
     if cleaned:
         print(cleaned)
+    if smoothed:
+        print(smoothed)
     if simplified:
         print(simplified)
 
@@ -200,6 +230,12 @@ def main(argv=None) -> int:
         raise PmnError("--min_component_faces and --keep_components must be >= 0")
     if args.simplify != 0 and not (args.simplify > 1 and args.simplify < float("inf")):
         raise PmnError("--simplify must be 0 (off) or a finite number of voxels greater than 1, got {}".format(args.simplify))
+    if args.smooth < 0:
+        raise PmnError("--smooth must be >= 0 iterations, got {}".format(args.smooth))
+    if not (args.smooth_lambda > 0 and args.smooth_lambda <= 1):
+        raise PmnError("--smooth_lambda must be in (0, 1], got {}".format(args.smooth_lambda))
+    if not (args.smooth_mu < -args.smooth_lambda and args.smooth_mu > float("-inf")):
+        raise PmnError("--smooth_mu must be finite and < -smooth_lambda = {}, got {}".format(-args.smooth_lambda, args.smooth_mu))
     device = torch.device(args.device)
     if device.type != "cuda":
         raise PmnError("--device {}: mesh.py runs on a ROCm GPU (no CPU fallback)".format(args.device))

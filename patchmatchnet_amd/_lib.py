@@ -31,6 +31,8 @@ VOXEL_MAX_CHANNELS = 8
 CROP_MAX_VERTICES = 4096
 MESH_PLACE_LONG_RUN = 256
 MESH_SIMPLIFY_MAX_FACES = 715827882
+MESH_SMOOTH_LONG_ROW = 256
+MESH_SMOOTH_MAX_STEPS = 65536
 
 _fp = ctypes.c_void_p  # device float* (passed as integer address)
 _ip = ctypes.c_void_p
@@ -119,6 +121,8 @@ SIGNATURES = {
                           ctypes.c_longlong, ctypes.c_double, _fp, _ip, _fp, _ip, _s],
     "pmn_mesh_remap_faces": [_ip, _i, _i, _ip, _i, _ip, _ip, _ip, _ip, _s],
     "pmn_mesh_cluster_place": [_fp, _i, _ip, _i, _ip, _ip, _ip, _i, _fp, _hp, ctypes.c_double, _hp, ctypes.c_double, _fp, _s],
+    "pmn_mesh_smooth": [_fp, _i, _ip, _ip, ctypes.c_longlong, _ip, _hp, _i, _fp, _fp, _ip, _s],
+    "pmn_mesh_vertex_normals": [_fp, _i, _ip, _i, _ip, _ip, _i, _fp, _ip, _s],
 }
 
 # pmn_depth_metrics' row layout and scratch size (the PMN_METRICS_* macros of include/pmn_hip.h; tests/test_validate_io.py checks them)

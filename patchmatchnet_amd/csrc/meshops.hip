@@ -686,3 +686,245 @@ extern "C" int pmn_mesh_cluster_place(const float* vertices, int n_vertices, con
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
+
+// ---- smoothing and vertex normals ---------------------------------------------------------------------------
+// meshops.vertex_adjacency builds the CSR of the vertices' neighbours (integer torch); pmn_mesh_smooth applies umbrella steps over it and
+// pmn_mesh_vertex_normals sums the faces' cross products per vertex.  tests/smooth_ref.py restates both in numpy; the arithmetic is
+// spelled out in include/pmn_hip.h.  Both kernels are a lane per vertex and follow ONE rule for a row: at most PMN_MESH_SMOOTH_LONG_ROW
+// entries are summed by the row's lane in row order; a longer row by the wave, lane l taking the entries l, l + 64, ... in row order and
+// the 64 partial sums meeting in pmn_voxel_mean's butterfly, exactly as mesh_cluster_place_kernel does.  No atomics on floats, no LDS.
+
+struct MeshRowSum {
+    double x, y, z;
+};
+
+// the wave's long rows, one after the other (as voxel_mean_kernel walks them): `add(entry index, the owner's own value, sums)` adds one
+// entry; the owner's lane ends with the butterfly's result.  Every shuffle stands where the whole wave is active.
+template <typename Add>
+__device__ __forceinline__ void mesh_long_rows(bool is_long, long long s, long long len, const MeshRowSum& own, int lane, MeshRowSum& q,
+                                               Add add) {
+#pragma clang fp contract(off)
+    unsigned long long todo = __ballot(is_long);
+    while (todo) {
+        const int owner = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const long long rs = __shfl(s, owner, 64), rl = __shfl(len, owner, 64);
+        const MeshRowSum o = {__shfl(own.x, owner, 64), __shfl(own.y, owner, 64), __shfl(own.z, owner, 64)};
+        MeshRowSum part = {0.0, 0.0, 0.0};
+        for (long long i = rs + lane; i < rs + rl; i += 64) add(i, o, part);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            part.x += __shfl_xor(part.x, o, 64);
+            part.y += __shfl_xor(part.y, o, 64);
+            part.z += __shfl_xor(part.z, o, 64);
+        }
+        if (lane == owner) q = part;
+    }
+}
+
+struct MeshSmoothArgs {
+    const float* src;            // [nv][3]
+    float* dst;                  // [nv][3]
+    const long long* starts;     // [nv + 1]
+    const int* neighbours;       // [n_entries]
+    const unsigned char* pinned; // [nv] or null
+    int* invalid;                // counted in the first step only, else null
+    long long n_entries;
+    int nv;
+    double factor;
+};
+
+__global__ __launch_bounds__(256) void mesh_smooth_kernel(const MeshSmoothArgs a) {
+#pragma clang fp contract(off)
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool live = v < a.nv;
+    long long s = 0, len = 0;
+    float fx = 0.0f, fy = 0.0f, fz = 0.0f;
+    bool moves = false;
+    if (live) {
+        s = a.starts[v];
+        long long e = a.starts[v + 1];
+        s = s < 0 ? 0 : s;
+        e = e > a.n_entries ? a.n_entries : e;
+        len = e > s ? e - s : 0;
+        fx = a.src[3 * (size_t)v];
+        fy = a.src[3 * (size_t)v + 1];
+        fz = a.src[3 * (size_t)v + 2];
+        moves = len > 0 && !(a.pinned && a.pinned[v]);
+    }
+    // (a pinned or empty row still counts its bad entries: *invalid is a property of the CSR, not of the mask)
+    const double px = (double)fx, py = (double)fy, pz = (double)fz;
+    MeshRowSum q = {0.0, 0.0, 0.0};
+    int bad = 0;
+    const bool is_long = len > PMN_MESH_SMOOTH_LONG_ROW;
+    if (live && !is_long)
+        for (long long i = s; i < s + len; ++i) {
+            const int j = a.neighbours[i];
+            if (!mesh_index_ok(j, a.nv)) {
+                ++bad;
+                continue;
+            }
+            const float* P = a.src + 3 * (size_t)j;
+            q.x += (double)P[0] - px;
+            q.y += (double)P[1] - py;
+            q.z += (double)P[2] - pz;
+        }
+    const MeshRowSum own = {px, py, pz};
+    mesh_long_rows(is_long, s, len, own, lane, q, [&](long long i, const MeshRowSum& o, MeshRowSum& part) {
+        const int j = a.neighbours[i];
+        if (!mesh_index_ok(j, a.nv)) {
+            ++bad;
+            return;
+        }
+        const float* P = a.src + 3 * (size_t)j;
+        part.x += (double)P[0] - o.x;
+        part.y += (double)P[1] - o.y;
+        part.z += (double)P[2] - o.z;
+    });
+    if (bad && a.invalid) atomicAdd(a.invalid, bad);
+    if (!live) return;
+    if (moves) {
+        const double d = (double)len;
+        fx = (float)(px + a.factor * (q.x / d));
+        fy = (float)(py + a.factor * (q.y / d));
+        fz = (float)(pz + a.factor * (q.z / d));
+    }
+    a.dst[3 * (size_t)v] = fx;
+    a.dst[3 * (size_t)v + 1] = fy;
+    a.dst[3 * (size_t)v + 2] = fz;
+}
+
+__global__ __launch_bounds__(256) void mesh_copy_xyz_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+
+static bool mesh_overlap(const void* p, const void* q, size_t bytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + bytes && b < a + bytes;
+}
+
+extern "C" int pmn_mesh_smooth(const float* xyz, int n_vertices, const long long* starts, const int* neighbours, long long n_entries,
+                               const unsigned char* pinned, const double* factors_host, int n_steps, float* out, float* scratch,
+                               int* invalid, void* stream) {
+    if (!xyz || !starts || !out || !invalid || n_entries < 0 || (n_entries > 0 && !neighbours)) return PMN_ERR_ARG;
+    if (n_steps < 0 || n_steps > PMN_MESH_SMOOTH_MAX_STEPS || (n_steps > 0 && !factors_host) || (n_steps > 1 && !scratch))
+        return PMN_ERR_ARG;
+    if (n_vertices < 1 || n_vertices > 2147483647 - 255) return PMN_ERR_SHAPE;
+    for (int k = 0; k < n_steps; ++k)
+        if (!std::isfinite(factors_host[k])) return PMN_ERR_ARG;
+    const size_t bytes = 3 * sizeof(float) * (size_t)n_vertices;
+    if (mesh_overlap(out, xyz, bytes)) return PMN_ERR_ARG;
+    if (scratch && (mesh_overlap(scratch, xyz, bytes) || mesh_overlap(scratch, out, bytes))) return PMN_ERR_ARG;
+    const dim3 grid((unsigned)((n_vertices + 255) / 256));
+    if (n_steps == 0) {
+        const long long n = 3LL * n_vertices;
+        PMN_LAUNCH(mesh_copy_xyz_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, xyz, out, n);
+        PMN_CHECK_LAUNCH();
+        return PMN_OK;
+    }
+    MeshSmoothArgs a;
+    a.starts = starts;
+    a.neighbours = neighbours;
+    a.pinned = pinned;
+    a.n_entries = n_entries;
+    a.nv = n_vertices;
+    const float* src = xyz;
+    for (int k = 0; k < n_steps; ++k) {
+        a.src = src;
+        a.dst = ((n_steps - 1 - k) & 1) ? scratch : out;
+        a.invalid = k == 0 ? invalid : nullptr;
+        a.factor = factors_host[k];
+        PMN_LAUNCH(mesh_smooth_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+        src = a.dst;
+    }
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}
+
+struct MeshNormalArgs {
+    const float* vertices;       // [nv][3]
+    const int* faces;            // [nt][3]
+    const int* corners;          // [3 nt]
+    const long long* starts;     // [nv + 1]
+    float* out;                  // [nv][3]
+    int nv, nt, flip;
+};
+
+// adds (B - A) x (C - A) of corner entry e's face to q
+__device__ __forceinline__ void mesh_normal_corner(const MeshNormalArgs& a, int e, MeshRowSum& q) {
+#pragma clang fp contract(off)
+    if ((unsigned)e >= 3u * (unsigned)a.nt) return;
+    const int f = e / 3;
+    const int ia = a.faces[3 * (size_t)f], ib = a.faces[3 * (size_t)f + 1], ic = a.faces[3 * (size_t)f + 2];
+    if (!(mesh_index_ok(ia, a.nv) && mesh_index_ok(ib, a.nv) && mesh_index_ok(ic, a.nv))) return;
+    const float* A = a.vertices + 3 * (size_t)ia;
+    const float* B = a.vertices + 3 * (size_t)ib;
+    const float* C = a.vertices + 3 * (size_t)ic;
+    const double ax = (double)A[0], ay = (double)A[1], az = (double)A[2];
+    const double e1x = (double)B[0] - ax, e1y = (double)B[1] - ay, e1z = (double)B[2] - az;
+    const double e2x = (double)C[0] - ax, e2y = (double)C[1] - ay, e2z = (double)C[2] - az;
+    q.x += e1y * e2z - e1z * e2y;
+    q.y += e1z * e2x - e1x * e2z;
+    q.z += e1x * e2y - e1y * e2x;
+}
+
+__global__ __launch_bounds__(256) void mesh_vertex_normals_kernel(const MeshNormalArgs a) {
+#pragma clang fp contract(off)
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool live = v < a.nv;
+    const long long n_corners = 3LL * a.nt;
+    long long s = 0, len = 0;
+    if (live) {
+        s = a.starts[v];
+        long long e = a.starts[v + 1];
+        s = s < 0 ? 0 : s;
+        e = e > n_corners ? n_corners : e;
+        len = e > s ? e - s : 0;
+    }
+    MeshRowSum q = {0.0, 0.0, 0.0};
+    const bool is_long = len > PMN_MESH_SMOOTH_LONG_ROW;
+    if (live && !is_long)
+        for (long long i = s; i < s + len; ++i) mesh_normal_corner(a, a.corners[i], q);
+    const MeshRowSum none = {0.0, 0.0, 0.0};
+    mesh_long_rows(is_long, s, len, none, lane, q,
+                   [&](long long i, const MeshRowSum&, MeshRowSum& part) { mesh_normal_corner(a, a.corners[i], part); });
+    if (!live) return;
+    const double length = sqrt((q.x * q.x + q.y * q.y) + q.z * q.z);
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    if (length > 0.0 && length < __builtin_inf()) {
+        nx = (float)(q.x / length);
+        ny = (float)(q.y / length);
+        nz = (float)(q.z / length);
+        if (a.flip) {
+            nx = -nx;
+            ny = -ny;
+            nz = -nz;
+        }
+    }
+    a.out[3 * (size_t)v] = nx;
+    a.out[3 * (size_t)v + 1] = ny;
+    a.out[3 * (size_t)v + 2] = nz;
+}
+
+extern "C" int pmn_mesh_vertex_normals(const float* vertices, int n_vertices, const int* faces, int n_faces, const int* corners,
+                                       const long long* corner_starts, int flip, float* out, int* invalid, void* stream) {
+    if (!vertices || !faces || !corners || !corner_starts || !out || !invalid) return PMN_ERR_ARG;
+    if (n_vertices < 1 || n_faces < 1 || n_vertices > 2147483647 - 255 || n_faces > PMN_MESH_SIMPLIFY_MAX_FACES) return PMN_ERR_SHAPE;
+    MeshNormalArgs a;
+    a.vertices = vertices;
+    a.faces = faces;
+    a.corners = corners;
+    a.starts = corner_starts;
+    a.out = out;
+    a.nv = n_vertices;
+    a.nt = n_faces;
+    a.flip = flip;
+    PMN_LAUNCH(mesh_dist_check_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces, n_faces,
+               n_vertices, invalid);
+    PMN_LAUNCH(mesh_vertex_normals_kernel, dim3((unsigned)((n_vertices + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}

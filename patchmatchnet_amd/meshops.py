@@ -5,7 +5,8 @@ removal of small components -- the floaters of a TSDF mesh -- and points drawn o
 tests/meshops_ref.py restates all of it in numpy.  build_face_grid / point_mesh_distance (pmn_mesh_distance) are
 the exact distance from points to the surface itself; tests/mesh_distance_ref.py is their numpy form.  simplify_clustering (DESIGN.md
 section 28, pmn_mesh_remap_faces / pmn_mesh_cluster_place) shrinks a mesh to one vertex per occupied cell; tests/simplify_ref.py is its
-numpy form."""
+numpy form.  vertex_adjacency, smooth_taubin / smooth_laplacian (pmn_mesh_smooth) and vertex_normals (pmn_mesh_vertex_normals) are
+DESIGN.md section 30: noise removal and the normals of the geometry itself; tests/smooth_ref.py is their numpy form."""
 from __future__ import annotations
 
 import ctypes
@@ -507,4 +508,191 @@ def simplify_clustering(vertices: torch.Tensor, faces: torch.Tensor, cell: float
     out = result(rep[vidx], new_faces, None if out_colors is None else out_colors[vidx],
                  None if out_normals is None else out_normals[vidx], vmap)
     lap("compaction")
+    return out
+
+
+# ---- smoothing and vertex normals from the faces --------------------------------------------------------------
+
+class VertexAdjacency(NamedTuple):
+    """The neighbours of every vertex in CSR form (vertex_adjacency)."""
+    starts: torch.Tensor      # [Nv + 1] int64: row i is neighbours[starts[i]:starts[i + 1]]
+    neighbours: torch.Tensor  # [E] int32: the distinct neighbours of every vertex, ascending within a row
+    boundary: torch.Tensor    # [Nv] bool: the vertex lies on an edge that exactly one face corner-pair names
+
+
+def _mesh_on_device(vertices: torch.Tensor, faces: torch.Tensor, what: str):
+    faces = _faces(faces, what)
+    vertices = _dev_as(vertices, f"{what}: vertices", torch.float32)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.device != faces.device:
+        raise PmnError(f"{what}: vertices must be [Nv,3] on {faces.device}")
+    if vertices.shape[0] > INT32_MAX - 255 or faces.shape[0] > _lib.MESH_SIMPLIFY_MAX_FACES:
+        raise PmnError(f"{what}: at most 2^31 - 256 vertices and {_lib.MESH_SIMPLIFY_MAX_FACES} faces, got {vertices.shape[0]} and "
+                       f"{faces.shape[0]}")
+    return vertices, faces
+
+
+def vertex_adjacency(faces: torch.Tensor, n_vertices: int) -> VertexAdjacency:
+    """The vertex-to-vertex incidence of a mesh.  Every face (a, b, c) contributes its six directed pairs; a pair with equal ends is
+    dropped; duplicates are merged (the 63-bit key a * Nv + b, a stable sort, the first of every run), so row i holds the distinct
+    neighbours of i in ascending order.  An undirected edge is a boundary edge when exactly one face corner-pair names it, where faces
+    that repeat a vertex name none; a vertex is a boundary vertex when it lies on one.  A function of the SET of faces, not of their
+    order.  Integer torch, nothing is read through a face index; one host read.  PmnError, with their number, for faces that name a
+    vertex outside 0..Nv-1."""
+    what = "vertex_adjacency"
+    faces = _faces(faces, what)
+    nv, nt, dev = int(n_vertices), int(faces.shape[0]), faces.device
+    if not 0 <= nv <= INT32_MAX - 255 or nt > _lib.MESH_SIMPLIFY_MAX_FACES:
+        raise PmnError(f"{what}: n_vertices must be 0 .. 2^31 - 256 and at most {_lib.MESH_SIMPLIFY_MAX_FACES} faces, got {nv} / {nt}")
+    f = faces.long()
+    bad = int(((f < 0) | (f >= nv)).any(1).sum()) if nt else 0  # the host read
+    if bad:
+        _raise_invalid(what, bad, nv)
+    a, b, c = f.unbind(1)
+    src, dst = torch.cat((a, b, b, c, c, a)), torch.cat((b, a, c, b, a, c))
+    keys = torch.sort((src * nv + dst)[src != dst], stable=True).values
+    head = torch.ones(keys.shape[0], dtype=torch.bool, device=dev)
+    head[1:] = keys[1:] != keys[:-1]
+    keys = keys[head]
+    rows = torch.div(keys, max(nv, 1), rounding_mode="floor")
+    starts = torch.searchsorted(rows, torch.arange(nv + 1, dtype=torch.int64, device=dev)).contiguous()
+    neighbours = (keys - rows * nv).to(torch.int32).contiguous()
+    # the corner-pairs (a, b), (b, c), (c, a) of the faces with three different vertices, as undirected edges, counted
+    proper = (a != b) & (b != c) & (a != c)
+    p, q = torch.cat((a, b, c))[proper.repeat(3)], torch.cat((b, c, a))[proper.repeat(3)]
+    edge, count = torch.unique(torch.minimum(p, q) * nv + torch.maximum(p, q), return_counts=True)
+    edge = edge[count == 1]
+    boundary = torch.zeros(nv, dtype=torch.bool, device=dev)
+    boundary[torch.div(edge, max(nv, 1), rounding_mode="floor")] = True
+    boundary[edge % max(nv, 1)] = True
+    return VertexAdjacency(starts, neighbours, boundary)
+
+
+def _check_adjacency(adjacency, nv: int, dev, what: str) -> VertexAdjacency:
+    if not isinstance(adjacency, VertexAdjacency):
+        raise PmnError(f"{what}: adjacency must come from vertex_adjacency")
+    for t, name, dtype, shape in ((adjacency.starts, "starts", torch.int64, (nv + 1,)),
+                                  (adjacency.neighbours, "neighbours", torch.int32, None),
+                                  (adjacency.boundary, "boundary", torch.bool, (nv,))):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev or \
+                (shape is not None and tuple(t.shape) != shape):
+            raise PmnError(f"{what}: the adjacency's {name} must be a contiguous {dtype} tensor{'' if shape is None else ' ' + str(list(shape))} "
+                           f"on {dev}")
+    return adjacency
+
+
+def smooth_steps(vertices: torch.Tensor, faces: torch.Tensor, factors, boundary: str = "fixed", pinned: Optional[torch.Tensor] = None,
+                 adjacency: Optional[VertexAdjacency] = None) -> torch.Tensor:
+    """pmn_mesh_smooth: new float32 [Nv,3] vertices after one umbrella step per entry of ``factors`` (finite numbers): a vertex with
+    neighbours moves by factor * (the mean over its neighbours j of p_j - p_i), in float64 with one rounding to float32 per step
+    (include/pmn_hip.h); a vertex without neighbours, or a pinned one, keeps its bits.  ``boundary="fixed"`` pins the boundary vertices
+    of vertex_adjacency (they still feed their neighbours), ``"free"`` treats them like any other; ``pinned`` (bool [Nv]) is or-ed in.
+    No factors: a bit-equal copy.  ``adjacency``: what vertex_adjacency(faces, Nv) returned, to spare building it again.  The caller's
+    tensors are not written.  A function of the mesh and the factors alone, bit for bit, whatever the order of the faces.  An empty
+    mesh returns without a launch.  PmnError for a host tensor, non-finite vertices or factors, an unknown boundary mode and faces that
+    name a vertex outside the array (counted, never dereferenced)."""
+    what = "smooth_steps"
+    factors = [float(x) for x in factors]
+    if not all(math.isfinite(x) for x in factors):
+        raise PmnError(f"{what}: every factor must be finite")
+    if len(factors) > _lib.MESH_SMOOTH_MAX_STEPS:
+        raise PmnError(f"{what}: at most {_lib.MESH_SMOOTH_MAX_STEPS} steps, got {len(factors)}")
+    if boundary not in ("fixed", "free"):
+        raise PmnError(f"{what}: boundary must be 'fixed' or 'free', got {boundary!r}")
+    vertices, faces = _mesh_on_device(vertices, faces, what)
+    dev, nv, nt = faces.device, int(vertices.shape[0]), int(faces.shape[0])
+    if pinned is not None:
+        pinned = _dev_as(pinned, f"{what}: pinned", torch.bool)
+        if tuple(pinned.shape) != (nv,) or pinned.device != dev:
+            raise PmnError(f"{what}: pinned must be [{nv}] on {dev}, got {tuple(pinned.shape)} on {pinned.device}")
+    if nt and not nv:
+        _raise_invalid(what, nt, 0)
+    if nv == 0:
+        return vertices.clone()
+    bad = int((~torch.isfinite(vertices)).any(1).sum())
+    if bad:
+        raise PmnError(f"{what}: {bad} vertices have non-finite coordinates")
+    adj = vertex_adjacency(faces, nv) if adjacency is None else _check_adjacency(adjacency, nv, dev, what)
+    if nt == 0:
+        return vertices.clone()
+    pin = adj.boundary if boundary == "fixed" else None
+    if pinned is not None:
+        pin = pinned if pin is None else pin | pinned
+    out = torch.empty_like(vertices)
+    scratch = torch.empty_like(vertices) if len(factors) > 1 else None
+    invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_entries = int(adj.neighbours.shape[0])
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_mesh_smooth(vertices.data_ptr(), nv, adj.starts.data_ptr(), adj.neighbours.data_ptr() if n_entries else None,
+                                         n_entries, _ptr(pin), (ctypes.c_double * max(len(factors), 1))(*factors), len(factors),
+                                         out.data_ptr(), _ptr(scratch), invalid.data_ptr(), _stream(vertices)), "pmn_mesh_smooth")
+    if adjacency is not None and factors:  # a CSR someone handed in is not trusted: the kernel skipped and counted what it could not use
+        bad = int(invalid.item())
+        if bad:
+            raise PmnError(f"{what}: {bad} entries of the adjacency name a vertex outside 0..{nv - 1}")
+    return out
+
+
+def _check_lam(what: str, lam: float, iterations: int):
+    lam, iterations = float(lam), int(iterations)
+    if not (lam > 0.0 and lam <= 1.0):
+        raise PmnError(f"{what}: lam must be in (0, 1], got {lam}")
+    if iterations < 0:
+        raise PmnError(f"{what}: iterations must be >= 0, got {iterations}")
+    return lam, iterations
+
+
+def smooth_taubin(vertices: torch.Tensor, faces: torch.Tensor, iterations: int = 10, lam: float = 0.5, mu: float = -0.53,
+                  boundary: str = "fixed", pinned: Optional[torch.Tensor] = None,
+                  adjacency: Optional[VertexAdjacency] = None) -> torch.Tensor:
+    """Taubin's low-pass filter: ``iterations`` times a shrinking umbrella step with ``lam`` and an inflating one with ``mu``, i.e.
+    smooth_steps with the factors lam, mu, lam, mu, ...; the pair removes ripple without the shrinkage of smooth_laplacian.  New float32
+    [Nv,3] vertices; faces, colours and the number of vertices are the caller's and unchanged; ``iterations=0`` is a bit-equal copy.
+    PmnError, beyond smooth_steps's, for ``lam`` outside (0, 1], ``mu`` not finite or not < -lam (Taubin's condition for a low-pass
+    filter) and negative iterations."""
+    what = "smooth_taubin"
+    lam, iterations = _check_lam(what, lam, iterations)
+    mu = float(mu)
+    if not (math.isfinite(mu) and mu < -lam):
+        raise PmnError(f"{what}: mu must be finite and < -lam = {-lam}, got {mu}")
+    if 2 * iterations > _lib.MESH_SMOOTH_MAX_STEPS:
+        raise PmnError(f"{what}: at most {_lib.MESH_SMOOTH_MAX_STEPS // 2} iterations, got {iterations}")
+    return smooth_steps(vertices, faces, [lam, mu] * iterations, boundary=boundary, pinned=pinned, adjacency=adjacency)
+
+
+def smooth_laplacian(vertices: torch.Tensor, faces: torch.Tensor, iterations: int = 1, lam: float = 0.5, boundary: str = "fixed",
+                     pinned: Optional[torch.Tensor] = None, adjacency: Optional[VertexAdjacency] = None) -> torch.Tensor:
+    """``iterations`` umbrella steps with ``lam`` in (0, 1] (smooth_steps with the factors lam, lam, ...): smooths and shrinks."""
+    what = "smooth_laplacian"
+    lam, iterations = _check_lam(what, lam, iterations)
+    if iterations > _lib.MESH_SMOOTH_MAX_STEPS:
+        raise PmnError(f"{what}: at most {_lib.MESH_SMOOTH_MAX_STEPS} iterations, got {iterations}")
+    return smooth_steps(vertices, faces, [lam] * iterations, boundary=boundary, pinned=pinned, adjacency=adjacency)
+
+
+def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, flip: bool = False) -> torch.Tensor:
+    """pmn_mesh_vertex_normals: float32 [Nv,3], for every vertex the normalised sum of (B - A) x (C - A) over the faces (A, B, C) at
+    its corners -- area-weighted, float64, one rounding -- by the right-hand rule of the faces' stored winding; ``flip`` negates it
+    exactly.  A vertex with no face, or only faces without area, gets zero.  The kernel is handed the faces in _canonical_face_order,
+    so the order of the caller's faces changes no bit.  An empty mesh returns without a launch.  PmnError for a host tensor and for
+    faces that name a vertex outside the array (counted, never dereferenced); one host read."""
+    what = "vertex_normals"
+    vertices, faces = _mesh_on_device(vertices, faces, what)
+    dev, nv, nt = faces.device, int(vertices.shape[0]), int(faces.shape[0])
+    if nt and not nv:
+        _raise_invalid(what, nt, 0)
+    out = torch.zeros_like(vertices)
+    if nv == 0 or nt == 0:
+        return out
+    faces_canon = faces[_canonical_face_order(faces)].contiguous()
+    by_vertex = torch.sort(faces_canon.reshape(-1), stable=True)
+    corners = by_vertex.indices.to(torch.int32)
+    corner_starts = torch.searchsorted(by_vertex.values, torch.arange(nv + 1, dtype=torch.int32, device=dev)).contiguous()
+    invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_mesh_vertex_normals(vertices.data_ptr(), nv, faces_canon.data_ptr(), nt, corners.data_ptr(),
+                                                 corner_starts.data_ptr(), 1 if flip else 0, out.data_ptr(), invalid.data_ptr(),
+                                                 _stream(vertices)), "pmn_mesh_vertex_normals")
+    bad = int(invalid.item())
+    if bad:
+        _raise_invalid(what, bad, nv)
     return out
