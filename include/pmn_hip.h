@@ -781,6 +781,44 @@ int pmn_radius_count(const float *to_xyz, const long long *to_keys, long long n_
                      const int *dims_host, const float *query, const int *order, long long n_from, double radius, int same_cloud,
                      int *count, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  Normals of a point cloud from its neighbourhoods
+ * (pointcloud.knn_normals / estimate_normals, cloud_normals.py; tests/cloud_normals_ref.py is the numpy form; the
+ * reference has no counterpart).  The grid, query, order, n_from, k, max_dist and same_cloud are pmn_knn_distance's, and so is the
+ * search: the same walk, the same comparisons, the same cap, the same exclusion of the query by index.  What differs is what the lane
+ * does with its list.  Everything below is float64, IEEE, without contraction, from the float32 coordinates widened to float64.
+ *
+ * Neighbourhood: the slots of pmn_knn_distance's list that hold a point (index >= 0), in rank order j = 0 .. c - 1; a capped slot is
+ * no neighbour, the point uses what it has.  The point set is the query q itself plus those c neighbours, m = 1 + c (on a cloud's own
+ * points that is Open3D's knn = k + 1).
+ * Moments: d_j = p_j - q per axis; s_a = sum_j d_ja (3 sums), M_ab = sum_j d_ja * d_jb (6 sums: xx xy xz yy yz zz), each started at 0
+ * and added in rank order.  q is the zero delta and enters through m alone.  C_ab = M_ab - (s_a * s_b) / m.
+ * Eigenvectors: A = C, V = I, then PMN_NORMAL_SWEEPS = 6 sweeps over the pairs (p, q) = (0, 1), (0, 2), (1, 2), r the third index.
+ * A pair whose A_pq is exactly 0 is skipped; otherwise
+ *   theta = (A_qq - A_pp) / (2 * A_pq);  root = |theta| + sqrt(theta * theta + 1);  t = theta < 0 ? -1 / root : 1 / root;
+ *   c = 1 / sqrt(t * t + 1);  s = t * c;  h = t * A_pq;  A_pp -= h;  A_qq += h;  A_pq = 0;
+ *   (A_rp, A_rq) = (c * A_rp - s * A_rq, s * A_rp + c * A_rq);  (V_ip, V_iq) = (c * V_ip - s * V_iq, s * V_ip + c * V_iq), i = 0, 1, 2.
+ * The eigenvalues are the diagonal of A, sorted ascending l0 <= l1 <= l2 with equal values in column order; the normal is the column
+ * of V that belongs to l0, as it stands (a product of rotations: a unit vector to a few ulp of float64; it is not renormalised).
+ * Degenerate: the normal is (0, 0, 0) and the variation 0 when m < 3, when l2 == 0, or when l1 <= line_ratio * l2 (points on a line
+ * define no plane; line_ratio finite and >= 0).  No other tolerance decides which points have a normal.
+ * Sign: canonical = the component of largest magnitude is positive, the lowest axis among equal magnitudes.  With n_viewpoints > 0
+ * (viewpoints: DEVICE float64 [n_viewpoints][3], at most 4096) the viewpoint c nearest to q is found by e = c - q per axis,
+ * e.x * e.x + e.y * e.y + e.z * e.z, a later viewpoint winning only with a strictly smaller value; the canonical normal is negated
+ * when n.x * e.x + n.y * e.y + n.z * e.z < 0, evaluated on the unrounded vector, and kept when that is exactly 0.  This is a
+ * HEURISTIC: a fused cloud does not record which view wrote a point, so "the nearest camera saw it" is an assumption, wrong for
+ * surfaces that face away from the camera that happens to be nearest.
+ * Outputs, indexed as query: normal [n_from][3] float32 (not NULL), the float64 vector rounded once per component; variation [n_from]
+ * float64 or NULL = l0 / (l0 + l1 + l2), the surface variation (rounding may leave it a few ulp below 0 on an exact plane); count
+ * [n_from] int32 or NULL = m - 1, the neighbours used.  PMN_ERR_ARG for pmn_knn_distance's reasons, for n_viewpoints outside 0 ..
+ * 4096 or non-zero with viewpoints NULL, and for a line_ratio that is negative or not finite.  One launch of ceil(n_from / 64) one-wave
+ * workgroups, one lane per query, kernels specialised on the list's capacity (8, 16, 32); the lists are never written. */
+#define PMN_NORMAL_SWEEPS 6
+#define PMN_NORMAL_MAX_VIEWPOINTS 4096
+int pmn_knn_normals(const float *to_xyz, const long long *to_keys, long long n_to, const double *origin_host, double cell,
+                    const int *dims_host, const float *query, const int *order, long long n_from, int k, double max_dist,
+                    int same_cloud, const double *viewpoints, int n_viewpoints, double line_ratio, float *normal, double *variation,
+                    int *count, void *stream);
+
 /* Added under ABI 25 (purely additive: the version number did not move).  The exact distance from points to a triangle mesh
  * (patchmatchnet_amd/meshops.py build_face_grid / point_mesh_distance; tests/mesh_distance_ref.py is the numpy
  * form; the reference has no counterpart).  vertices, faces, n_vertices, n_faces and invalid as in the mesh entry points above: a face

@@ -33,6 +33,8 @@ MESH_PLACE_LONG_RUN = 256
 MESH_SIMPLIFY_MAX_FACES = 715827882
 MESH_SMOOTH_LONG_ROW = 256
 MESH_SMOOTH_MAX_STEPS = 65536
+NORMAL_SWEEPS = 6
+NORMAL_MAX_VIEWPOINTS = 4096
 
 _fp = ctypes.c_void_p  # device float* (passed as integer address)
 _ip = ctypes.c_void_p
@@ -117,6 +119,8 @@ SIGNATURES = {
                          _fp, _ip, _fp, _s],
     "pmn_radius_count": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, ctypes.c_double, _i, _ip,
                          _s],
+    "pmn_knn_normals": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, _i, ctypes.c_double, _i,
+                        _fp, _i, ctypes.c_double, _fp, _fp, _ip, _s],
     "pmn_mesh_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _ip, ctypes.c_double, _fp, _i, _ip, _i, _fp, _ip,
                           ctypes.c_longlong, ctypes.c_double, _fp, _ip, _fp, _ip, _s],
     "pmn_mesh_remap_faces": [_ip, _i, _i, _ip, _i, _ip, _ip, _ip, _ip, _s],

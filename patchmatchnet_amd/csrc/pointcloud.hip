@@ -168,6 +168,186 @@ __global__ __launch_bounds__(64) void radius_count_kernel(RadiusArgs a) {
     a.count[q] = b.count;
 }
 
+// ---- pmn_knn_normals ----------------------------------------------------------------------------------------------------------------
+// knn_distance_kernel's walk with another epilogue: instead of writing the lists out (12 k n bytes) the lane that found them turns
+// them into the covariance of the neighbourhood and that into its eigenvector of least variance (include/pmn_hip.h states every
+// operation; tests/cloud_normals_ref.py repeats them in numpy).  The list is read through static slot indices only, as everywhere
+// else, and every entry of the 3 x 3 matrix and of the rotation is a named scalar: nothing here may become a per-lane array.
+
+struct NormalArgs {
+    GridArgs g;
+    const float* query;  // [n_from][3]
+    const int* order;    // [n_from] or null (identity)
+    int n_from;
+    int k;
+    int same_cloud;
+    double max_dist;
+    const double* viewpoints;  // [n_viewpoints][3] or null
+    int n_viewpoints;
+    double line_ratio;
+    float* normal;       // [n_from][3]
+    double* variation;   // [n_from] or null
+    int* count;          // [n_from] or null
+};
+
+// One Jacobi rotation in the (p, q) plane; r is the third index.  Skipped when the off-diagonal entry is exactly 0.
+__device__ __forceinline__ void pc_jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
+                                                 double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
+#pragma clang fp contract(off)
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double root = fabs(theta) + sqrt(theta * theta + 1.0);
+    const double t = theta < 0.0 ? -1.0 / root : 1.0 / root;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    const double h = t * apq;
+    app = app - h;
+    aqq = aqq + h;
+    apq = 0.0;
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp;
+    arq = rq;
+    const double x0 = c * v0p - s * v0q, y0 = s * v0p + c * v0q;
+    v0p = x0;
+    v0q = y0;
+    const double x1 = c * v1p - s * v1q, y1 = s * v1p + c * v1q;
+    v1p = x1;
+    v1q = y1;
+    const double x2 = c * v2p - s * v2q, y2 = s * v2p + c * v2q;
+    v2p = x2;
+    v2q = y2;
+}
+
+// exchanges eigenpair a and b when b's value is strictly the smaller: three of these sort three pairs, equal values keeping their order
+__device__ __forceinline__ void pc_eigen_order(double& la, double& ax, double& ay, double& az, double& lb, double& bx, double& by,
+                                               double& bz) {
+    const bool swap = lb < la;
+    const double l = la, x = ax, y = ay, z = az;
+    la = swap ? lb : la;
+    ax = swap ? bx : ax;
+    ay = swap ? by : ay;
+    az = swap ? bz : az;
+    lb = swap ? l : lb;
+    bx = swap ? x : bx;
+    by = swap ? y : by;
+    bz = swap ? z : bz;
+}
+
+template <int CAP>
+__global__ __launch_bounds__(64) void knn_normals_kernel(NormalArgs a) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n_from) return;
+    const int q = a.order ? a.order[t] : t;
+    const double qx = (double)a.query[(size_t)q * 3], qy = (double)a.query[(size_t)q * 3 + 1], qz = (double)a.query[(size_t)q * 3 + 2];
+    KBest<CAP> b;
+    b.init(a.k, a.max_dist * a.max_dist, a.same_cloud ? q : -1);
+    pc_walk(a.g, qx, qy, qz, b);
+    // the moments of the deltas, neighbours in rank order (ascending slot); the query is the zero delta and counts in m alone
+    double sx = 0.0, sy = 0.0, sz = 0.0, mxx = 0.0, mxy = 0.0, mxz = 0.0, myy = 0.0, myz = 0.0, mzz = 0.0;
+    int used = 0;
+#pragma unroll
+    for (int s = 0; s < CAP; ++s) {  // static register; a sentinel (-2) or capped (-1) slot is no neighbour
+        const int i = b.idx[s];
+        if (i < 0) continue;
+        const float* p = a.g.xyz + (size_t)i * 3;
+        const double dx = (double)p[0] - qx, dy = (double)p[1] - qy, dz = (double)p[2] - qz;
+        sx += dx;
+        sy += dy;
+        sz += dz;
+        mxx += dx * dx;
+        mxy += dx * dy;
+        mxz += dx * dz;
+        myy += dy * dy;
+        myz += dy * dz;
+        mzz += dz * dz;
+        ++used;
+    }
+    const double m = (double)(used + 1);
+    double a00 = mxx - (sx * sx) / m, a01 = mxy - (sx * sy) / m, a02 = mxz - (sx * sz) / m;
+    double a11 = myy - (sy * sy) / m, a12 = myz - (sy * sz) / m, a22 = mzz - (sz * sz) / m;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;  // v[row][column]
+    for (int sweep = 0; sweep < PMN_NORMAL_SWEEPS; ++sweep) {
+        pc_jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0, 1)
+        pc_jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0, 2)
+        pc_jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1, 2)
+    }
+    // eigenpairs (value, column of v) ascending, equal values by column
+    pc_eigen_order(a00, v00, v10, v20, a11, v01, v11, v21);
+    pc_eigen_order(a11, v01, v11, v21, a22, v02, v12, v22);
+    pc_eigen_order(a00, v00, v10, v20, a11, v01, v11, v21);
+    const double l0 = a00, l1 = a11, l2 = a22;
+    double nx = 0.0, ny = 0.0, nz = 0.0, var = 0.0;
+    if (used >= 2 && l2 != 0.0 && l1 > a.line_ratio * l2) {
+        nx = v00;
+        ny = v10;
+        nz = v20;
+        var = l0 / (l0 + l1 + l2);
+        // canonical sign: the component of largest magnitude positive, the lowest axis among equals
+        const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+        const double lead = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+        bool flip = lead < 0.0;
+        if (a.n_viewpoints > 0) {  // towards the nearest viewpoint, the lowest index among equals
+            double best = 0.0, bx = 0.0, by = 0.0, bz = 0.0;
+            bool have = false;
+            for (int v = 0; v < a.n_viewpoints; ++v) {  // wave-uniform addresses
+                const double dx = a.viewpoints[(size_t)v * 3] - qx, dy = a.viewpoints[(size_t)v * 3 + 1] - qy,
+                             dz = a.viewpoints[(size_t)v * 3 + 2] - qz;
+                const double d = dx * dx + dy * dy + dz * dz;
+                if (!have || d < best) {
+                    have = true;
+                    best = d;
+                    bx = dx;
+                    by = dy;
+                    bz = dz;
+                }
+            }
+            const double cnx = flip ? -nx : nx, cny = flip ? -ny : ny, cnz = flip ? -nz : nz;
+            const double dot = cnx * bx + cny * by + cnz * bz;
+            flip = flip != (dot < 0.0);
+        }
+        nx = flip ? -nx : nx;
+        ny = flip ? -ny : ny;
+        nz = flip ? -nz : nz;
+    }
+    a.normal[(size_t)q * 3] = (float)nx;
+    a.normal[(size_t)q * 3 + 1] = (float)ny;
+    a.normal[(size_t)q * 3 + 2] = (float)nz;
+    if (a.variation) a.variation[q] = var;
+    if (a.count) a.count[q] = used;
+}
+
+extern "C" int pmn_knn_normals(const float* to_xyz, const long long* to_keys, long long n_to, const double* origin_host, double cell,
+                               const int* dims_host, const float* query, const int* order, long long n_from, int k, double max_dist,
+                               int same_cloud, const double* viewpoints, int n_viewpoints, double line_ratio, float* normal,
+                               double* variation, int* count, void* stream) {
+    NormalArgs a;
+    const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
+    if (rc != PMN_OK) return rc;
+    if (!query || !normal || n_from < 1 || n_from >= (1LL << 31) - 64 || k < 1 || k > 32) return PMN_ERR_ARG;
+    if (!(max_dist > 0.0) || !std::isfinite(max_dist) || !std::isfinite(max_dist * max_dist)) return PMN_ERR_ARG;
+    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
+    if (n_viewpoints < 0 || n_viewpoints > PMN_NORMAL_MAX_VIEWPOINTS || (n_viewpoints > 0 && !viewpoints)) return PMN_ERR_ARG;
+    if (!(line_ratio >= 0.0) || !std::isfinite(line_ratio)) return PMN_ERR_ARG;
+    a.query = query;
+    a.order = order;
+    a.n_from = (int)n_from;
+    a.k = k;
+    a.same_cloud = same_cloud ? 1 : 0;
+    a.max_dist = max_dist;
+    a.viewpoints = viewpoints;
+    a.n_viewpoints = n_viewpoints;
+    a.line_ratio = line_ratio;
+    a.normal = normal;
+    a.variation = variation;
+    a.count = count;
+    const dim3 grid((unsigned)((n_from + 63) / 64));
+    if (k <= 8) PMN_LAUNCH(knn_normals_kernel<8>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    else if (k <= 16) PMN_LAUNCH(knn_normals_kernel<16>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    else PMN_LAUNCH(knn_normals_kernel<32>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}
+
 extern "C" int pmn_knn_distance(const float* to_xyz, const long long* to_keys, long long n_to, const double* origin_host, double cell,
                                 const int* dims_host, const float* query, const int* order, long long n_from, int k, double max_dist,
                                 int same_cloud, double* d2, int* index, double* mean, void* stream) {

@@ -309,6 +309,92 @@ def radius_outliers(points: torch.Tensor, radius: float, min_neighbors: int, cel
     return count >= int(min_neighbors), count
 
 
+def _viewpoints(what: str, viewpoints, device) -> Optional[torch.Tensor]:
+    """None, or the viewpoints as a contiguous float64 [V,3] tensor on ``device`` (a tensor there already, or host numbers)."""
+    if viewpoints is None:
+        return None
+    if isinstance(viewpoints, torch.Tensor):
+        if viewpoints.device != device:
+            raise PmnError(f"{what}: viewpoints are on {viewpoints.device}, the grid on {device}")
+        if viewpoints.dtype != torch.float64:
+            raise PmnError(f"{what}: viewpoints: expected float64, got {viewpoints.dtype}")
+        v = viewpoints
+    else:
+        v = torch.as_tensor(np.asarray(viewpoints, np.float64)).to(device)
+    if v.dim() != 2 or v.shape[1] != 3 or not 1 <= v.shape[0] <= _lib.NORMAL_MAX_VIEWPOINTS:
+        raise PmnError(f"{what}: viewpoints: expected [V,3] with 1 <= V <= {_lib.NORMAL_MAX_VIEWPOINTS}, got {tuple(v.shape)}")
+    if not bool(torch.isfinite(v).all()):
+        raise PmnError(f"{what}: viewpoints have non-finite coordinates")
+    return v.contiguous()
+
+
+def knn_normals(query: Optional[torch.Tensor], grid: Grid, k: int, max_dist: float, same_cloud: bool = False, viewpoints=None,
+                line_ratio: float = 1e-6, return_variation: bool = False, return_count: bool = False):
+    """pmn_knn_normals: float32 [n,3], the normal of every query point from the point itself and its ``k`` (1..32) nearest points of
+    ``grid`` nearer than ``max_dist`` (knn_distance's search): the eigenvector of least variance of their covariance, float64 on the
+    device (include/pmn_hip.h states every operation).  (0, 0, 0) where fewer than two neighbours lie in range, where all points
+    coincide, or where they lie on a line (second eigenvalue <= ``line_ratio`` times the largest).
+    Sign: the component of largest magnitude is positive, or with ``viewpoints`` ([V,3], V <= 4096; a float64 tensor on the grid's
+    device or host numbers) the normal faces the viewpoint nearest to the point -- a heuristic, a cloud does not say which camera saw
+    a point.  Unlike the C entry, which only enqueues, this wrapper waits for the device when viewpoints are given: it checks them
+    for non-finite values (one host read) and uploads host numbers first.  ``return_variation``: also float64 [n], the surface variation l0 / (l0 + l1 + l2), 0 where the normal is;
+    ``return_count``: also int32 [n], the neighbours used (less than k where slots were capped).  ``same_cloud``: as knn_distance."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
+        raise PmnError(f"knn_normals: k must be an integer in 1..32, got {k!r}")
+    if not (max_dist > 0.0 and np.isfinite(max_dist) and np.isfinite(float(max_dist) ** 2)):
+        raise PmnError(f"knn_normals: max_dist must be positive and finite, got {max_dist}")
+    if not (line_ratio >= 0.0 and np.isfinite(line_ratio)):
+        raise PmnError(f"knn_normals: line_ratio must be finite and >= 0, got {line_ratio}")
+    query, order = _search_query("knn_normals", query, grid, same_cloud)
+    n, k, dev = int(query.shape[0]), int(k), query.device
+    views = _viewpoints("knn_normals", viewpoints, dev)
+    normal = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    variation = torch.empty(n, dtype=torch.float64, device=dev) if return_variation else None
+    count = torch.empty(n, dtype=torch.int32, device=dev) if return_count else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_knn_normals(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n, k,
+                                         float(max_dist), int(bool(same_cloud)), views.data_ptr() if views is not None else None,
+                                         int(views.shape[0]) if views is not None else 0, float(line_ratio), normal.data_ptr(),
+                                         variation.data_ptr() if return_variation else None,
+                                         count.data_ptr() if return_count else None, _stream(query)), "pmn_knn_normals")
+    out = [_unsort(normal, grid, same_cloud)]
+    if return_variation:
+        out.append(_unsort(variation, grid, same_cloud))
+    if return_count:
+        out.append(_unsort(count, grid, same_cloud))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def estimate_normals(points: torch.Tensor, k: int = 16, max_dist: Optional[float] = None, cell: Optional[float] = None,
+                     viewpoints=None, orient_like: Optional[torch.Tensor] = None, line_ratio: float = 1e-6,
+                     return_variation: bool = False, return_count: bool = False):
+    """Normals of a cloud from its own neighbourhoods (Open3D estimate_normals with knn = k + 1): builds the cleaning grid
+    (default_cell; ``max_dist`` defaults to CLEAN_MAX_DIST_CELLS cells, as in statistical_outliers) and calls knn_normals with
+    same_cloud.  Orientation: ``viewpoints`` as in knn_normals, or ``orient_like``, float32 [n,3] on the device (for example the
+    depth-map normals of an ``eval.py --normals 1`` cloud): a normal n is negated where n . orient_like < 0 (float64 torch on the
+    device, on the rounded normal); giving both is an error.  ``cell`` changes the time only."""
+    points = _points(points, "points")
+    if viewpoints is not None and orient_like is not None:
+        raise PmnError("estimate_normals: give viewpoints or orient_like, not both")
+    if orient_like is not None:
+        if not isinstance(orient_like, torch.Tensor) or orient_like.device != points.device:
+            raise PmnError(f"estimate_normals: orient_like must be a tensor on {points.device} (no CPU fallback)")
+        if orient_like.dtype != torch.float32 or tuple(orient_like.shape) != tuple(points.shape):
+            raise PmnError(f"estimate_normals: orient_like: expected float32 {tuple(points.shape)}, got {orient_like.dtype} "
+                           f"{tuple(orient_like.shape)}")
+    grid = _clean_grid(points, cell)
+    if max_dist is None:
+        max_dist = CLEAN_MAX_DIST_CELLS * grid.cell
+    out = knn_normals(None, grid, k, max_dist, same_cloud=True, viewpoints=viewpoints, line_ratio=line_ratio,
+                      return_variation=return_variation, return_count=return_count)
+    if orient_like is not None:
+        normal = out[0] if isinstance(out, tuple) else out
+        against = (normal.double() * orient_like.double()).sum(1) < 0
+        normal = torch.where(against[:, None], -normal, normal)
+        out = (normal,) + out[1:] if isinstance(out, tuple) else normal
+    return out
+
+
 def reduce_points(points: torch.Tensor, dst: float, order=None, seed: int = 0, cell: Optional[float] = None,
                   return_rounds: bool = False):
     """reducePts_haa.m on the device: bool [n], the greedy maximal set of points no two of which are within ``dst`` (<=) of each
