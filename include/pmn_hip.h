@@ -819,6 +819,38 @@ int pmn_knn_normals(const float *to_xyz, const long long *to_keys, long long n_t
                     int same_cloud, const double *viewpoints, int n_viewpoints, double line_ratio, float *normal, double *variation,
                     int *count, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  A signed distance from an ORIENTED point cloud, written into
+ * the pool planes of the block-sparse volume above, which pmn_mt_count_blocks / pmn_mt_emit_blocks then mesh (pointcloud.cloud_sdf /
+ * mesh_from_cloud, mesh_cloud.py; tests/cloud_sdf_ref.py is the numpy form; the reference has no counterpart).
+ * The first six arguments are pmn_nn_distance's grid over the n_to points; normals (DEVICE float32 [n_to][3]) and colors (DEVICE uint8
+ * [n_to][3], or NULL) are in the grid's SORTED order.  blocks, n_blocks, volume_dims_host, volume_origin_host, voxel, trunc and the
+ * pool planes tsdf, weight, rgb, cweight are pmn_tsdf_integrate_blocks'; rgb and cweight are given exactly when colors is.
+ * 1 <= k <= 32; radius, boundary, radius * radius and boundary * boundary positive and finite, else PMN_ERR_ARG.
+ *
+ * Per sample (i, j, k) of a listed block, everything float64, IEEE, without contraction, from float32 data widened to float64:
+ * Position: x_c = origin_c + (float)index_c * voxel in FLOAT32, as pmn_tsdf_integrate forms it, then widened.  A sample of a border
+ * block with an index >= n on some axis is outside the lattice and is not written.
+ * Neighbourhood: pmn_knn_distance's list for the query x with max_dist = radius: the k nearest points with d2 < R2 = radius * radius
+ * strictly, ascending (d2, sorted index); the sample is a position, never a point, so nothing is excluded.  c = the slots that hold a
+ * point, j = 0 .. c - 1 their rank.
+ * Weights: u = 1 - d2_j / R2, u2 = u * u, w_j = u2 * u2 (no exponential: the host model is exact).
+ * Distance: s_j = (n.x * (x.x - p.x) + n.y * (x.y - p.y)) + n.z * (x.z - p.z);  W = sum_j w_j, S = sum_j w_j * s_j, both started at 0 and
+ * added in rank order;  f = S / W.
+ * Open boundaries (Hoppe's rule): t2 = d2_0 - s_0 * s_0 for the nearest neighbour j = 0, the squared distance along its tangent plane.
+ * The sample is UNOBSERVED when c = 0, when t2 > boundary * boundary, or when W is not above 0 (every neighbour so close to the radius
+ * that its weight rounded to 0: f would be 0 / 0).
+ * Outputs: unobserved: tsdf = 1, weight = 0, rgb = 0, cweight = 0.  Observed: tsdf = (float)fmin(1, fmax(-1, f / (double)trunc)),
+ * weight = (float)c -- pmn_mt_count_blocks' min_weight then reads "at least this many neighbours" -- and with colours
+ * rgb_ch = (float)((sum_j w_j * colour_j,ch) / W), the sum in rank order, cweight = (float)c.
+ * Sign: the volume's own: positive on the side the normals point to, so the extracted normals and winding face that side.
+ * Every sample of every listed block inside the lattice is written, by plain stores.  One launch of 8 * n_blocks one-wave workgroups
+ * (a wave per 8 x 8 layer of a block, a lane per sample), kernels specialised on the list's capacity (8, 16, 32); no atomics, the
+ * lists are never written. */
+int pmn_cloud_sdf_blocks(const float *to_xyz, const long long *to_keys, long long n_to, const double *origin_host, double cell,
+                         const int *dims_host, const float *normals, const unsigned char *colors, const int *blocks, int n_blocks,
+                         const int *volume_dims_host, const float *volume_origin_host, float voxel, float trunc, int k, double radius,
+                         double boundary, float *tsdf, float *weight, float *rgb, float *cweight, void *stream);
+
 /* Added under ABI 25 (purely additive: the version number did not move).  The exact distance from points to a triangle mesh
  * (patchmatchnet_amd/meshops.py build_face_grid / point_mesh_distance; tests/mesh_distance_ref.py is the numpy
  * form; the reference has no counterpart).  vertices, faces, n_vertices, n_faces and invalid as in the mesh entry points above: a face

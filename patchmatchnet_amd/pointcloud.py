@@ -395,6 +395,144 @@ def estimate_normals(points: torch.Tensor, k: int = 16, max_dist: Optional[float
     return out
 
 
+# ---- a surface from an oriented cloud -------------------------------------------------------------------------------
+# SETTINGS, not measurements: the ratios below were chosen by reasoning (a sample should see about a ring of neighbours on either side,
+# the band should hold the marching cells next to the surface, a boundary is cut about half a support away from the last point) and
+# no sweep stands behind them.  Each is an argument of mesh_from_cloud and a flag of mesh_cloud.py.
+SDF_SPACING_K = 8           # s = the median over the cloud of the mean distance to this many nearest other points
+SDF_VOXEL_SPACINGS = 1.0    # voxel = this times s
+SDF_RADIUS_VOXELS = 3.0     # radius = this times voxel; trunc = radius
+SDF_BOUNDARY_RADII = 0.5    # boundary = this times radius
+
+
+def _per_point(t, name: str, what: str, dtype, n: int, device) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise PmnError(f"{what}: {name}: expected a torch.Tensor")
+    if not t.is_cuda or t.device != device:
+        raise PmnError(f"{what}: {name} is on {t.device}, the points on {device} (no CPU fallback)")
+    if t.dtype != dtype:
+        raise PmnError(f"{what}: {name}: expected {dtype}, got {t.dtype}")
+    if tuple(t.shape) != (n, 3):
+        raise PmnError(f"{what}: {name}: expected [{n},3], got {tuple(t.shape)}")
+    return t
+
+
+def cloud_sdf(volume, grid: Grid, normals: torch.Tensor, colors: Optional[torch.Tensor] = None, k: int = 16,
+              radius: Optional[float] = None, boundary: Optional[float] = None) -> None:
+    """pmn_cloud_sdf_blocks: fills the pool planes of ``volume`` (a tsdf.SparseTsdfVolume after allocate_points) with the signed
+    distance to the oriented cloud of ``grid``: per sample the ``k`` (1..32) nearest points within ``radius``, f = sum w n . (x - p) /
+    sum w with w = (1 - d2 / radius^2)^4 in rank order, unobserved (tsdf 1, weight 0) where no point is in range or where the nearest
+    point's tangent plane is met further than ``boundary`` from it; weight = the number of neighbours (include/pmn_hip.h states every
+    operation).  ``normals`` float32 [n,3] and ``colors`` uint8 [n,3] (given exactly when the volume has colour planes) are in the
+    ORIGINAL order of the points the grid was built from; they are gathered through grid.perm here.  ``radius`` defaults to the grid's
+    cell, ``boundary`` to half the radius.  One launch; every argument is checked before it."""
+    from .tsdf import SparseTsdfVolume
+    if not isinstance(volume, SparseTsdfVolume):
+        raise PmnError("cloud_sdf: volume must be a tsdf.SparseTsdfVolume")
+    volume._allocated("cloud_sdf")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
+        raise PmnError(f"cloud_sdf: k must be an integer in 1..32, got {k!r}")
+    radius = float(grid.cell) if radius is None else float(radius)
+    boundary = SDF_BOUNDARY_RADII * radius if boundary is None else float(boundary)
+    for name, v in (("radius", radius), ("boundary", boundary)):
+        if not (v > 0.0 and np.isfinite(v) and np.isfinite(v * v) and v * v > 0.0):
+            raise PmnError(f"cloud_sdf: {name} and its square must be positive and finite, got {v}")
+    if not isinstance(grid.xyz, torch.Tensor) or not grid.xyz.is_cuda or grid.xyz.device != volume.tsdf.device:
+        raise PmnError(f"cloud_sdf: the grid is on {getattr(grid.xyz, 'device', None)}, the volume on {volume.tsdf.device} "
+                       f"(no CPU fallback)")
+    n, dev = int(grid.xyz.shape[0]), grid.xyz.device
+    normals = _per_point(normals, "normals", "cloud_sdf", torch.float32, n, dev)
+    if (colors is not None) != (volume.rgb is not None):
+        raise PmnError("cloud_sdf: colors must be given exactly when the volume has colour planes")
+    if colors is not None:
+        colors = _per_point(colors, "colors", "cloud_sdf", torch.uint8, n, dev)
+    bad = int((~torch.isfinite(normals)).any(1).sum())
+    if bad:
+        raise PmnError(f"cloud_sdf: {bad} normals are not finite")
+    nrm = normals[grid.perm].contiguous()
+    col = colors[grid.perm].contiguous() if colors is not None else None
+    dims = (ctypes.c_int * 3)(*volume.dims)
+    origin = (ctypes.c_float * 3)(*[float(v) for v in volume.origin])
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_cloud_sdf_blocks(*_grid_args(grid), nrm.data_ptr(), col.data_ptr() if col is not None else None,
+                                              volume.blocks.data_ptr(), int(volume.blocks.shape[0]), dims, origin, volume.voxel,
+                                              volume.trunc, int(k), radius, boundary, volume.tsdf.data_ptr(), volume.weight.data_ptr(),
+                                              volume.rgb.data_ptr() if col is not None else None,
+                                              volume.cweight.data_ptr() if col is not None else None, _stream(grid.xyz)),
+              "pmn_cloud_sdf_blocks")
+
+
+def cloud_spacing(points: torch.Tensor, k: int = SDF_SPACING_K) -> float:
+    """s, the spacing mesh_from_cloud sizes its voxel from: the median (the lower of the two middle values) over the cloud of
+    knn_distance's mean distance to the ``k`` nearest other points, on the cleaning grid with its default cap."""
+    points = _points(points, "points")
+    grid = _clean_grid(points, None)
+    return float(knn_distance(None, grid, k, CLEAN_MAX_DIST_CELLS * grid.cell, same_cloud=True).median())
+
+
+def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, colors: Optional[torch.Tensor] = None, voxel: Optional[float] = None,
+                    radius: Optional[float] = None, trunc: Optional[float] = None, k: int = 16, boundary: Optional[float] = None,
+                    min_neighbors: int = 3, max_blocks: Optional[int] = None, normals_out: bool = True):
+    """A surface mesh from an oriented cloud: (vertices [Nv,3] float32, faces [Nt,3] int32, colors [Nv,3] uint8 | None,
+    normals [Nv,3] float32 | None, info dict), on the device.  ``points`` float32 [n,3], ``normals`` float32 [n,3] (for example
+    estimate_normals'), ``colors`` uint8 [n,3] or None.  A point whose normal is zero or not finite -- cloud_normals.py's degenerate
+    points -- is dropped and counted in info.  Defaults (the SDF_* settings above, none of them measured): voxel = s = cloud_spacing,
+    radius = 3 voxels, trunc = radius, boundary = radius / 2.  The lattice is tsdf.choose_grid's for the sparse volume (1st..99th
+    percentile box of the points grown by radius; when it would exceed the virtual lattice the voxel grows, with the defaults that
+    follow it, and info["note"] says so); the search grid's cell is radius.  Then SparseTsdfVolume.allocate_points(points, radius),
+    cloud_sdf and extract(min_weight=min_neighbors): a vertex needs ``min_neighbors`` points within radius of both ends of its edge."""
+    from . import ops, tsdf
+    points = _points(points, "points")
+    n, dev = int(points.shape[0]), points.device
+    normals = _per_point(normals, "normals", "mesh_from_cloud", torch.float32, n, dev)
+    if colors is not None:
+        colors = _per_point(colors, "colors", "mesh_from_cloud", torch.uint8, n, dev)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
+        raise PmnError(f"mesh_from_cloud: k must be an integer in 1..32, got {k!r}")
+    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or not 1 <= int(min_neighbors) <= int(k):
+        raise PmnError(f"mesh_from_cloud: min_neighbors must be an integer in 1..k, got {min_neighbors!r}")
+    for name, v in (("voxel", voxel), ("radius", radius), ("trunc", trunc), ("boundary", boundary)):
+        if v is not None and not (float(v) > 0.0 and np.isfinite(float(v))):
+            raise PmnError(f"mesh_from_cloud: {name} must be positive and finite, got {v}")
+    max_blocks = tsdf.MAX_BLOCKS if max_blocks is None else int(max_blocks)
+    good = torch.isfinite(normals).all(1) & (normals != 0).any(1)
+    dropped = n - int(good.sum())
+    if dropped == n:
+        raise PmnError("mesh_from_cloud: no point has a normal (all are zero or not finite); cloud_normals.py estimates them")
+    if dropped:
+        points, normals = points[good].contiguous(), normals[good].contiguous()
+        colors = colors[good].contiguous() if colors is not None else None
+    s = None
+    if voxel is None:
+        s = cloud_spacing(points)
+        voxel = SDF_VOXEL_SPACINGS * s
+        if not (voxel > 0.0 and np.isfinite(voxel)):
+            raise PmnError(f"mesh_from_cloud: the cloud's spacing is {s}; give voxel")
+    voxel, note = float(voxel), None
+    while True:  # a voxel that has to grow takes the defaults that depend on it along
+        r = SDF_RADIUS_VOXELS * voxel if radius is None else float(radius)
+        origin, grown, _, dims, why = tsdf.choose_grid(points, voxel=voxel, trunc=r, max_voxels=tsdf.MAX_VIRTUAL_VOXELS,
+                                                       limit_name="the virtual lattice's", max_axis=ops.SPARSE_MAX_AXIS - 1)
+        if why is None:
+            break
+        voxel, note = grown, why
+    radius = r
+    trunc = radius if trunc is None else float(trunc)
+    boundary = SDF_BOUNDARY_RADII * radius if boundary is None else float(boundary)
+    volume = tsdf.SparseTsdfVolume(origin, voxel, dims, trunc, dev, color=colors is not None, max_blocks=max_blocks)
+    grid = build_grid(points, radius)
+    blocks = volume.allocate_points(points, radius)
+    cloud_sdf(volume, grid, normals, colors, k=int(k), radius=radius, boundary=boundary)
+    vertices, faces, vcolors, vnormals = volume.extract(min_weight=float(min_neighbors), normals=normals_out)
+    nb = volume.nblocks
+    info = {"points": n, "dropped": dropped, "s": s, "voxel": volume.voxel, "radius": radius, "trunc": volume.trunc,
+            "boundary": boundary, "k": int(k), "min_neighbors": int(min_neighbors), "dims": tuple(volume.dims),
+            "origin": [float(v) for v in volume.origin], "blocks": blocks, "blocks_marked": volume.marked,
+            "block_share": blocks / float(nb[0] * nb[1] * nb[2]), "observed": int((volume.weight > 0).sum()),
+            "vertices": int(vertices.shape[0]), "faces": int(faces.shape[0]), "note": note}
+    return vertices, faces, vcolors, vnormals, info
+
+
 def reduce_points(points: torch.Tensor, dst: float, order=None, seed: int = 0, cell: Optional[float] = None,
                   return_rounds: bool = False):
     """reducePts_haa.m on the device: bool [n], the greedy maximal set of points no two of which are within ``dst`` (<=) of each

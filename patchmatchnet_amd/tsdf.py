@@ -138,6 +138,53 @@ class SparseTsdfVolume(_Volume):
         self.cweight = torch.zeros(shape, dtype=torch.float32, device=self.device) if self.color else None
         return B
 
+    def allocate_points(self, points: torch.Tensor, reach: float) -> int:
+        """``allocate`` for a cloud instead of views (pointcloud.cloud_sdf): marks the blocks that the box
+        p +- ``reach``, grown by one voxel as ops.tsdf_mark_blocks grows its boxes, of any point touches, dilates them by one block
+        and builds list, table and pool.  ``points``: float32 [n,3] on the volume's device.  The marking is torch (plumbing): the
+        blocks of the box's eight corners, which with the dilation cover the whole box because ``reach`` may not exceed 8 voxels (a
+        box then spans at most three blocks per axis, and the middle one lies next to both ends).  A box that misses the virtual
+        lattice marks nothing.  Returns the number of blocks B.  PmnError if nothing was marked or if B > max_blocks."""
+        if not isinstance(points, torch.Tensor) or not points.is_cuda or self.device.index not in (None, points.device.index) or \
+                points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+            raise PmnError(f"SparseTsdfVolume.allocate_points: points must be a float32 [n,3] tensor on {self.device}")
+        reach = float(reach)
+        if not (np.isfinite(reach) and reach > 0 and reach <= ops.SPARSE_BLOCK * self.voxel):
+            raise PmnError(f"SparseTsdfVolume.allocate_points: reach must be positive and at most {ops.SPARSE_BLOCK} voxels "
+                           f"({ops.SPARSE_BLOCK * self.voxel:.6g}), got {reach}")
+        if not bool(torch.isfinite(points).all()):
+            raise PmnError("SparseTsdfVolume.allocate_points: points have non-finite coordinates")
+        nbx, nby, nbz = self.nblocks
+        S = ops.SPARSE_BLOCK
+        top = torch.tensor([d - 1 for d in self.dims], dtype=torch.float64, device=self.device)
+        rel = points.double() - torch.from_numpy(self.origin.astype(np.float64)).to(self.device)
+        lo = torch.ceil((rel - reach) / self.voxel) - 1.0   # sample indices of the box, +- one voxel
+        hi = torch.floor((rel + reach) / self.voxel) + 1.0
+        inside = ((hi >= 0) & (lo <= top)).all(1)
+        ends = (lo[inside].clamp_min(0.0).long() // S, torch.minimum(hi[inside], top).long() // S)  # first and last block per axis
+        flags = torch.zeros(nbz * nby * nbx, dtype=torch.uint8, device=self.device)
+        for corner in range(8):
+            bx, by, bz = (ends[(corner >> c) & 1][:, c] for c in range(3))
+            flags[(bz * nby + by) * nbx + bx] = 1
+        flags = flags.view(nbz, nby, nbx)
+        blocks = torch.nonzero(self._dilate(flags).reshape(-1)).reshape(-1)  # ascending; synchronises
+        self.marked, self.needed = int(flags.sum(dtype=torch.int64).item()), int(blocks.numel())
+        del flags
+        if self.needed == 0:
+            raise PmnError("SparseTsdfVolume.allocate_points: no point lies within reach of the lattice (0 blocks)")
+        if self.needed > self.max_blocks:
+            raise PmnError(f"SparseTsdfVolume.allocate_points: {self.needed} blocks needed, max_blocks is {self.max_blocks}")
+        B = self.needed
+        self.blocks = blocks.to(torch.int32)
+        self.table = torch.full((nbz, nby, nbx), -1, dtype=torch.int32, device=self.device)
+        self.table.view(-1)[blocks] = torch.arange(B, dtype=torch.int32, device=self.device)
+        shape = (B,) + (S,) * 3
+        self.tsdf = torch.ones(shape, dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.rgb = torch.zeros((3,) + shape, dtype=torch.float32, device=self.device) if self.color else None
+        self.cweight = torch.zeros(shape, dtype=torch.float32, device=self.device) if self.color else None
+        return B
+
     def _allocated(self, what):
         if self.blocks is None:
             raise PmnError(f"SparseTsdfVolume.{what}: call allocate() first")
