@@ -819,6 +819,34 @@ int pmn_knn_normals(const float *to_xyz, const long long *to_keys, long long n_t
                     int same_cloud, const double *viewpoints, int n_viewpoints, double line_ratio, float *normal, double *variation,
                     int *count, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  Density clustering of a point cloud: DBSCAN with an
+ * order-free border rule (pointcloud.cluster_dbscan, cluster_cloud.py; tests/dbscan_ref.py is the numpy form;
+ * the reference has no counterpart).  The first six arguments are pmn_nn_distance's grid over the n points (n <= 2^31 - 256); the
+ * cloud is its own query set with pmn_radius_count's same_cloud meaning, and every per-point array below is DEVICE, [n], in the
+ * grid's SORTED order.  eps is finite and >= 0 with eps * eps finite, else PMN_ERR_ARG.  A pair (i, j) is WITHIN EPS when
+ * sqrt(d2) <= eps, d2 = dx*dx + dy*dy + dz*dz of the float32 coordinates widened to float64, x, y, z order, no contraction: exactly
+ * pmn_radius_count's test.
+ *
+ * pmn_cloud_core: core [n] uint8 = 1 where the points within eps of point i, ITSELF INCLUDED, number at least min_points (>= 1, else
+ * PMN_ERR_ARG), that is pmn_radius_count(same_cloud) + 1 >= min_points, else 0.  One launch of ceil(n / 64) one-wave workgroups.
+ *
+ * pmn_cloud_dbscan: from core (as written by pmn_cloud_core with the same grid and eps),
+ *   parent [n] int32: for a core point the smallest sorted index of its CLUSTER, the connected component of the graph on the core
+ *     points whose edges are the core pairs within eps; for any other point its own index.  A lock-free union-find in parent itself
+ *     (relaxed agent-scope integer atomics; no lane waits for another: csrc/union_find.hpp, csrc/cloud_cluster.hip).
+ *   label [n] int32, or NULL (then orig is NULL too and the border launch is left out): a core point's parent; for a point that is not
+ *     core the parent of the core point within eps that is least in (d2, orig) lexicographic order, a BORDER point, or -1 where no
+ *     core point is within eps, NOISE.  orig [n] int32 names every sorted point's index in the caller's own order (the grid's
+ *     permutation): the order of the sorted points inside a cell is the sort's, not the cloud's, so it must not decide a tie.
+ * Core flags, the partition into clusters and the noise set are a function of (points, eps, min_points) alone -- not of the cell, the
+ * order inside a cell, the launch shape or the run; only a cluster's NAME, a sorted index, depends on the grid.  Four launches
+ * (init, link, flatten, border; one lane per point, the walking launches in one-wave workgroups); no floating-point atomics. */
+int pmn_cloud_core(const float *xyz, const long long *keys, long long n, const double *origin_host, double cell, const int *dims_host,
+                   double eps, long long min_points, unsigned char *core, void *stream);
+int pmn_cloud_dbscan(const float *xyz, const long long *keys, long long n, const double *origin_host, double cell,
+                     const int *dims_host, double eps, const unsigned char *core, const int *orig, int *parent, int *label,
+                     void *stream);
+
 /* Added under ABI 25 (purely additive: the version number did not move).  A signed distance from an ORIENTED point cloud, written into
  * the pool planes of the block-sparse volume above, which pmn_mt_count_blocks / pmn_mt_emit_blocks then mesh (pointcloud.cloud_sdf /
  * mesh_from_cloud, mesh_cloud.py; tests/cloud_sdf_ref.py is the numpy form; the reference has no counterpart).

@@ -121,6 +121,8 @@ SIGNATURES = {
                          _s],
     "pmn_knn_normals": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, _i, ctypes.c_double, _i,
                         _fp, _i, ctypes.c_double, _fp, _fp, _ip, _s],
+    "pmn_cloud_core": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, ctypes.c_double, ctypes.c_longlong, _ip, _s],
+    "pmn_cloud_dbscan": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, ctypes.c_double, _ip, _ip, _ip, _ip, _s],
     "pmn_cloud_sdf_blocks": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, _ip, _i, _hp, _hp, _f, _f, _i,
                              ctypes.c_double, ctypes.c_double, _fp, _fp, _fp, _fp, _s],
     "pmn_mesh_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _ip, ctypes.c_double, _fp, _i, _ip, _i, _fp, _ip,

@@ -60,43 +60,13 @@
 #include <cmath>
 
 #include "pc_grid.hpp"
-
-#define MESH_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+#include "union_find.hpp"
 
 __device__ __forceinline__ bool mesh_index_ok(int v, int nv) { return (unsigned)v < (unsigned)nv; }
 
 // ---- components ------------------------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void mesh_cc_init_kernel(int* parent, int nv) {
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v < nv) parent[v] = v;
-}
-
-// the root of v as far as this lane can see; halves the path on the way (a best-effort store of a smaller ancestor)
-__device__ __forceinline__ int mesh_cc_find(int* parent, int v) {
-    int p = __hip_atomic_load(parent + v, MESH_RLX_AGENT);
-    while (p < v) {  // (p > v cannot be stored; read as a root, it would fail the swap below, never loop here)
-        const int g = __hip_atomic_load(parent + p, MESH_RLX_AGENT);
-        if (g < p) __hip_atomic_store(parent + v, g, MESH_RLX_AGENT);
-        v = p;
-        p = g;
-    }
-    return v;
-}
-
-__device__ __forceinline__ void mesh_cc_unite(int* parent, int a, int b) {
-    while (true) {
-        a = mesh_cc_find(parent, a);
-        b = mesh_cc_find(parent, b);
-        if (a == b) return;
-        const int hi = a > b ? a : b, lo = a > b ? b : a;
-        int seen = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, MESH_RLX_AGENT)) return;
-        if (!(seen < hi)) return;  // cannot happen (a slot only ever falls); a lane never retries without having descended
-        a = seen;
-        b = lo;
-    }
-}
+// init, find, unite and flatten: union_find.hpp (shared with cloud_cluster.hip)
 
 __global__ __launch_bounds__(256) void mesh_cc_hook_kernel(const int* __restrict__ faces, int nt, int nv, int* parent, int* invalid) {
     const int f = blockIdx.x * 256 + threadIdx.x;
@@ -108,17 +78,6 @@ __global__ __launch_bounds__(256) void mesh_cc_hook_kernel(const int* __restrict
     }
     if (a != b) mesh_cc_unite(parent, a, b);
     if (b != c) mesh_cc_unite(parent, b, c);
-}
-
-__global__ __launch_bounds__(256) void mesh_cc_flatten_kernel(int* parent, int nv) {
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv) return;
-    int r = v, p = __hip_atomic_load(parent + v, MESH_RLX_AGENT);
-    while (p < r) {  // another lane may already have flattened a slot on the way: its value is the same root
-        r = p;
-        p = __hip_atomic_load(parent + r, MESH_RLX_AGENT);
-    }
-    __hip_atomic_store(parent + v, r, MESH_RLX_AGENT);
 }
 
 extern "C" int pmn_mesh_components(const int* faces, int n_faces, int n_vertices, int* label, int* invalid, void* stream) {

@@ -9,6 +9,8 @@ There is no CPU path: the searches refuse host tensors.  The clouds come from pl
 
 The same grid serves cloud cleaning (clean_cloud.py): pmn_knn_distance and pmn_radius_count are the k nearest
 neighbours and the number of points within a radius, and statistical_outliers / radius_outliers the two filters built on them.
+cluster_dbscan (cluster_cloud.py) takes a cloud apart into its dense pieces over the same grid: pmn_cloud_core and
+pmn_cloud_dbscan (csrc/cloud_cluster.hip).
 
 Semantics: every distance is sqrt(dx*dx + dy*dy + dz*dz) of the float32 PLY coordinates widened to float64; the visiting
 order of the reduction is an explicit, seeded permutation (the MATLAB draws an unseeded randperm), and for a given order the result is
@@ -307,6 +309,72 @@ def radius_outliers(points: torch.Tensor, radius: float, min_neighbors: int, cel
         cell = max(default_cell(points), float(radius) / 8.0)
     count = radius_count(None, build_grid(points, cell), radius, same_cloud=True)
     return count >= int(min_neighbors), count
+
+
+# ---- density clustering ------------------------------------------------------------------------------------------------
+
+def cluster_dbscan(points: torch.Tensor, eps: float, min_points: int, cell: Optional[float] = None):
+    """DBSCAN on the device with an order-free border rule (pmn_cloud_core, pmn_cloud_dbscan): (labels int64 [n] in the
+    order of ``points``, core bool [n], sizes int64 [C]).  Distances are radius_count's: "within eps" is sqrt(d2) <= eps on the float64
+    distance of the float32 coordinates.
+    Core: a point with at least ``min_points`` points within ``eps`` of it, itself included (sklearn's and Open3D's rule).  Cluster: a
+    connected component of the core points under "within eps".  Border: a point that is not core but has a core point within eps; it
+    joins the cluster of the core point least in (d2, index in ``points``) order.  Open3D's cluster_dbscan and sklearn's DBSCAN give a
+    border point to whichever cluster reaches it first, which depends on their visiting order; that rule is REPLACED here, so a border
+    point that two clusters can reach may be labelled differently from theirs (core flags, the core points' partition and the noise set
+    agree).  Noise: every other point, label -1.  Clusters are numbered 0 .. C - 1 by descending size (core and border members),
+    equal sizes by the lowest index in ``points`` of any member; sizes[c] is the size of cluster c.
+    The result is a function of (points, eps, min_points): ``cell`` (default: default_cell, but not below eps / 8 so that the walk stays
+    within a few shells) changes the time only, and so do the sort inside the grid, the launch shape and the run.  The relabelling from
+    the kernels' roots to size ranks is a handful of torch ops on the device."""
+    points = _points(points, "points")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or min_points < 1:
+        raise PmnError(f"cluster_dbscan: min_points must be an integer >= 1, got {min_points!r}")
+    if not (eps >= 0.0 and np.isfinite(eps) and np.isfinite(float(eps) * float(eps))):
+        raise PmnError(f"cluster_dbscan: eps must be finite and >= 0, got {eps}")
+    if cell is None:
+        cell = max(default_cell(points), float(eps) / 8.0)
+    grid = build_grid(points, cell)
+    n, dev = int(points.shape[0]), points.device
+    core = torch.empty(n, dtype=torch.uint8, device=dev)
+    parent = torch.empty(n, dtype=torch.int32, device=dev)
+    label = torch.empty(n, dtype=torch.int32, device=dev)
+    orig = grid.perm.int()
+    L, args = _lib.lib(), _grid_args(grid)
+    with torch.cuda.device(dev):
+        check(L.pmn_cloud_core(*args, float(eps), int(min_points), core.data_ptr(), _stream(points)), "pmn_cloud_core")
+        check(L.pmn_cloud_dbscan(*args, float(eps), core.data_ptr(), orig.data_ptr(), parent.data_ptr(), label.data_ptr(),
+                                 _stream(points)), "pmn_cloud_dbscan")
+    # roots (sorted indices) -> ranks by (size descending, lowest original index ascending); the second key is unique per cluster.
+    # (Integer scatters into tables of n entries instead of unique's sort were measured slower: one large cluster is one address.)
+    member = label >= 0
+    roots, inverse, counts = torch.unique(label[member].long(), return_inverse=True, return_counts=True)
+    first = torch.full((int(roots.numel()),), n, dtype=torch.int64, device=dev).scatter_reduce_(0, inverse, grid.perm[member], "amin")
+    order = torch.argsort((n - counts) * (2 ** 31) + first)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(int(order.numel()), dtype=torch.int64, device=dev)
+    ranked = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    ranked[member] = rank[inverse]
+    return _unsort(ranked, grid, True), _unsort(core.bool(), grid, True), counts[order]
+
+
+def select_clusters(labels: torch.Tensor, sizes: torch.Tensor, min_cluster_points: int = 0, keep_largest: int = 0) -> torch.Tensor:
+    """bool [n]: the points of cluster_dbscan's clusters that hold at least ``min_cluster_points`` points and, with ``keep_largest`` > 0,
+    are among the ``keep_largest`` first (labels are size ranks, so those are the largest, ties as cluster_dbscan breaks them).  Noise
+    (label -1) is never kept."""
+    for name, v in (("min_cluster_points", min_cluster_points), ("keep_largest", keep_largest)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise PmnError(f"select_clusters: {name} must be an integer >= 0, got {v!r}")
+    for name, t in (("labels", labels), ("sizes", sizes)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1:
+            raise PmnError(f"select_clusters: {name}: expected a 1-D int64 tensor on a ROCm GPU (no CPU fallback)")
+    if labels.device != sizes.device:
+        raise PmnError(f"select_clusters: labels are on {labels.device}, sizes on {sizes.device}")
+    good = sizes >= int(min_cluster_points)
+    if keep_largest > 0:
+        good = good & (torch.arange(int(sizes.numel()), device=sizes.device) < int(keep_largest))
+    good = torch.cat([good, good.new_zeros(1)])  # label -1 reads the last entry
+    return good[labels]
 
 
 def _viewpoints(what: str, viewpoints, device) -> Optional[torch.Tensor]:
