@@ -847,6 +847,46 @@ int pmn_cloud_dbscan(const float *xyz, const long long *keys, long long n, const
                      const int *dims_host, double eps, const unsigned char *core, const int *orig, int *parent, int *label,
                      void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  Planes in a point cloud: the two kernels of a seeded RANSAC
+ * with a least-squares refit (pointcloud.segment_plane / segment_planes, segment_cloud.py; tests/plane_ref.py is
+ * the numpy form; the reference has no counterpart).  xyz: DEVICE float32 [n][3], finite, 1 <= n <= 2^31 - 65; normals: DEVICE float32
+ * [n][3] or NULL; active: DEVICE uint8 [n] or NULL (= every point).  Float64 throughout, products and sums in the written order, no fused
+ * multiply-add; x, y, z, nx, ny, nz are the float32 values widened to float64.  For a plane (a, b, c, d) the residual of a point is
+ * r = a * x + b * y + c * z + d, from left to right, and the point is an INLIER when fabs(r) <= threshold and, if min_cos > 0,
+ * fabs(a * nx + b * ny + c * nz) >= min_cos (a normal of 0 0 0 fails).  With min_cos == 0 normals is not read.  A point with
+ * active[i] == 0 is never an inlier.  threshold finite and >= 0, min_cos in [0, 1], min_cos > 0 only with normals, else PMN_ERR_ARG.
+ *
+ * pmn_plane_score: counts [n_planes] int32 (DEVICE; zeroed by the entry point, on the stream) = the number of inliers of every row of
+ * planes, DEVICE float64 [n_planes][4]; a row with a non-finite entry scores 0.  1 <= n_planes <= PMN_PLANE_MAX_HYPOTHESES, else
+ * PMN_ERR_SHAPE.  A lane holds four points in registers and walks 64 hypotheses, whose coefficients are scalar loads; a hypothesis's count
+ * over a wave is the popcount of a ballot per point slot, lane h % 64 keeps the running count of hypothesis h over the tiles its
+ * persistent wave takes and ends with one relaxed agent-scope int32 atomic add.  Integer sums of integers: counts does not depend on the
+ * launch shape, on the waves' order or on the run.  Two launches (zero, score).
+ *
+ * pmn_plane_inliers: for ONE plane (plane_host = HOST double[4], finite) mask [n] uint8 (DEVICE, or NULL) = 1 for its inliers, and
+ * sums [PMN_PLANE_SUMS] float64 (DEVICE) over its inliers with a = (x, y, z) - centre, each difference and each product rounded once
+ * (centre_host = HOST double[3], finite): [0] their number, [1..3] the sum of a, [4..9] of ax * ax, ax * ay, ax * az, ay * ay, ay * az,
+ * az * az.  The sums are EXACT up to one rounding, by pmn_icp_accumulate's digits (csrc/exact_sum.hpp): each term is scaled by a power of
+ * two, cut into PMN_PLANE_LIMBS signed 32-bit digits, added in 64-bit integers (a lane's PMN_PLANE_BLOCK_POINTS / 64 points, the wave by
+ * a butterfly, the workgroups by a second launch) and the total rounded to float64 once (to nearest, ties to even).  The powers of two
+ * come from extent_host (HOST double[3], finite, >= 0) alone: the CALLER's bound of |(double)p_c - centre_c| over the active points, for
+ * instance half the active bounding box around its centre; an inlier beyond it makes the sums meaningless (nothing is written out of
+ * bounds).  So mask and sums are a function of the arguments alone, bit for bit -- not of the launch shape or the run -- and a term
+ * loses only what lies below 2^-157 of its sum's bound.  scratch: DEVICE, PMN_PLANE_SCRATCH(n) 8-byte words (scratch_doubles states its
+ * size, else PMN_ERR_ARG), contents undefined before and after.  PMN_ERR_SHAPE if a bound's exponent leaves +-800.  No atomics.  Two
+ * launches. */
+#define PMN_PLANE_MAX_HYPOTHESES 4096
+#define PMN_PLANE_SUMS 10
+#define PMN_PLANE_LIMBS 5
+#define PMN_PLANE_BLOCK_POINTS 1024
+#define PMN_PLANE_BLOCKS(n) (((long long)(n) + PMN_PLANE_BLOCK_POINTS - 1) / PMN_PLANE_BLOCK_POINTS)
+#define PMN_PLANE_SCRATCH(n) (PMN_PLANE_BLOCKS(n) * PMN_PLANE_SUMS * PMN_PLANE_LIMBS)
+int pmn_plane_score(const float *xyz, const float *normals, const unsigned char *active, long long n, const double *planes, int n_planes,
+                    double threshold, double min_cos, int *counts, void *stream);
+int pmn_plane_inliers(const float *xyz, const float *normals, const unsigned char *active, long long n, const double *plane_host,
+                      double threshold, double min_cos, const double *centre_host, const double *extent_host, double *scratch,
+                      long long scratch_doubles, unsigned char *mask, double *sums, void *stream);
+
 /* Added under ABI 25 (purely additive: the version number did not move).  A signed distance from an ORIENTED point cloud, written into
  * the pool planes of the block-sparse volume above, which pmn_mt_count_blocks / pmn_mt_emit_blocks then mesh (pointcloud.cloud_sdf /
  * mesh_from_cloud, mesh_cloud.py; tests/cloud_sdf_ref.py is the numpy form; the reference has no counterpart).

@@ -35,6 +35,10 @@ MESH_SMOOTH_LONG_ROW = 256
 MESH_SMOOTH_MAX_STEPS = 65536
 NORMAL_SWEEPS = 6
 NORMAL_MAX_VIEWPOINTS = 4096
+PLANE_MAX_HYPOTHESES = 4096
+PLANE_SUMS = 10
+PLANE_LIMBS = 5
+PLANE_BLOCK_POINTS = 1024
 
 _fp = ctypes.c_void_p  # device float* (passed as integer address)
 _ip = ctypes.c_void_p
@@ -123,6 +127,9 @@ SIGNATURES = {
                         _fp, _i, ctypes.c_double, _fp, _fp, _ip, _s],
     "pmn_cloud_core": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, ctypes.c_double, ctypes.c_longlong, _ip, _s],
     "pmn_cloud_dbscan": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, ctypes.c_double, _ip, _ip, _ip, _ip, _s],
+    "pmn_plane_score": [_fp, _fp, _ip, ctypes.c_longlong, _fp, _i, ctypes.c_double, ctypes.c_double, _ip, _s],
+    "pmn_plane_inliers": [_fp, _fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, ctypes.c_double, _hp, _hp, _fp, ctypes.c_longlong, _ip,
+                          _fp, _s],
     "pmn_cloud_sdf_blocks": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, _ip, _i, _hp, _hp, _f, _f, _i,
                              ctypes.c_double, ctypes.c_double, _fp, _fp, _fp, _fp, _s],
     "pmn_mesh_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _ip, ctypes.c_double, _fp, _i, _ip, _i, _fp, _ip,
@@ -152,6 +159,10 @@ def metrics_scratch(B: int, H: int, W: int) -> int:
 def icp_scratch(n: int) -> int:
     """PMN_ICP_SCRATCH(n): 8-byte words of pmn_icp_accumulate's per-workgroup digit sums."""
     return -(-n // ICP_BLOCK_POINTS) * ICP_SUMS * ICP_LIMBS
+
+def plane_scratch(n: int) -> int:
+    """PMN_PLANE_SCRATCH(n): 8-byte words of pmn_plane_inliers' per-workgroup digit sums."""
+    return -(-n // PLANE_BLOCK_POINTS) * PLANE_SUMS * PLANE_LIMBS
 
 
 # libpmn_hip_experimental.so only (include/pmn_hip_experimental.h; `make -C patchmatchnet_amd/csrc EXPERIMENTAL=1`)

@@ -11,18 +11,18 @@
 // into PMN_ICP_LIMBS signed 32-bit digits held in int64 words; digits are added with integer adds (64 lanes by a butterfly, up to 2^31
 // terms without a carry), a workgroup stores its digit sums into the caller's scratch, and a second launch adds the workgroups' digits,
 // propagates the carries once and rounds the 160-bit total to float64, once.  No atomics of any kind.  What is lost: the part of a term
-// below 2^-157 of the bound of its sum (truncated toward zero), and the one rounding of the total.
+// below 2^-157 of the bound of its sum (truncated toward zero), and the one rounding of the total.  The digit split, the butterfly and
+// the finish live in exact_sum.hpp, which pmn_plane_inliers (cloud_plane.hip) shares.
+#include "exact_sum.hpp"
 #include "pc_grid.hpp"
 
 #define ICP_SUMS PMN_ICP_SUMS
 #define ICP_LIMBS PMN_ICP_LIMBS
 #define ICP_WORDS (ICP_SUMS * ICP_LIMBS)                      // 85 digit sums per workgroup
 #define ICP_PASSES (PMN_ICP_BLOCK_POINTS / 64)                // points per lane
-#define ICP_FINISH_THREADS 64
+static_assert(ICP_LIMBS == EXACT_LIMBS, "pmn_icp_accumulate's scratch is laid out in exact_sum.hpp's digits");
 
-struct IcpScale {
-    double to_digits[ICP_SUMS];  // 2^(157 - e_i), |term_i| < 2^e_i: a term times this is an integer below 2^157 in magnitude plus a fraction
-};
+typedef ExactScale<ICP_SUMS> IcpScale;
 
 struct IcpArgs {
     GridArgs g;
@@ -43,6 +43,20 @@ __device__ __forceinline__ void reg_pose(const double* __restrict__ P, double x,
     ox = P[0] * x + P[1] * y + P[2] * z + P[3];
     oy = P[4] * x + P[5] * y + P[6] * z + P[7];
     oz = P[8] * x + P[9] * y + P[10] * z + P[11];
+}
+
+// Digits K .. 0 of y into the wave's running sums: after the butterfly every lane holds the wave's sum of digit w = i * ICP_LIMBS + K;
+// lane w % 64 keeps it.
+template <int K>
+__device__ __forceinline__ void icp_digits(double& y, int i, int lane, long long& keep0, long long& keep1) {
+    const long long v = exact_wave_sum(exact_split<K>(y));
+    const int word = i * ICP_LIMBS + K;
+    if (word < 64) {
+        if (lane == word) keep0 += v;
+    } else {
+        if (lane == word - 64) keep1 += v;
+    }
+    if constexpr (K > 0) icp_digits<K - 1>(y, i, lane, keep0, keep1);
 }
 
 // One wave per workgroup, as nn_distance_kernel (a far query holds up 63 neighbours, not 255); a wave takes ICP_PASSES groups of 64
@@ -79,94 +93,17 @@ __global__ __launch_bounds__(64) void icp_accumulate_kernel(IcpArgs a) {
 #pragma unroll
         for (int i = 0; i < ICP_SUMS; ++i) {
             double y = term[i] * a.scale.to_digits[i];  // exact: a power of two
-#pragma unroll
-            for (int k = ICP_LIMBS - 1; k >= 0; --k) {
-                const double w = __builtin_ldexp(1.0, 32 * k);
-                const double d = trunc(y * __builtin_ldexp(1.0, -32 * k));  // |d| < 2^32 (the top digit: < 2^29)
-                y -= d * w;                                                 // exact: removes the leading bits
-                long long v = (long long)d;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-                const int word = i * ICP_LIMBS + k;
-                if (word < 64) {
-                    if (lane == word) keep0 += v;
-                } else {
-                    if (lane == word - 64) keep1 += v;
-                }
-            }
+            icp_digits<ICP_LIMBS - 1>(y, i, lane, keep0, keep1);
         }
     }
     a.partial[(size_t)lane * a.nb + blockIdx.x] = keep0;
     if (lane + 64 < ICP_WORDS) a.partial[(size_t)(lane + 64) * a.nb + blockIdx.x] = keep1;
 }
 
-// sums[i]: one workgroup (one wave) per sum adds the nb workgroups' digits -- integers, so the order is free; it is fixed anyway -- then
-// lane 0 propagates the carries and rounds.
-__global__ __launch_bounds__(ICP_FINISH_THREADS) void icp_finish_kernel(const long long* __restrict__ partial, int nb, IcpScale scale,
-                                                                        double* __restrict__ sums) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x, lane = threadIdx.x;
-    long long L[ICP_LIMBS];
-#pragma unroll
-    for (int k = 0; k < ICP_LIMBS; ++k) {
-        const long long* __restrict__ p = partial + (size_t)(i * ICP_LIMBS + k) * nb;
-        long long v = 0;
-        for (int j = lane; j < nb; j += ICP_FINISH_THREADS) v += p[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        L[k] = v;
-    }
-    if (lane != 0) return;
-    // digits into [0, 2^32), the top one keeps the sign (|total| < 2^31 * 2^157: the top word stays below 2^60)
-#pragma unroll
-    for (int k = 0; k + 1 < ICP_LIMBS; ++k) {
-        const long long c = L[k] >> 32;  // floor
-        L[k] -= c * 4294967296LL;
-        L[k + 1] += c;
-    }
-    const bool neg = L[ICP_LIMBS - 1] < 0;
-    if (neg) {  // magnitude: complement every digit, add one
-        long long carry = 1;
-#pragma unroll
-        for (int k = 0; k + 1 < ICP_LIMBS; ++k) {
-            const long long d = 4294967295LL - L[k] + carry;
-            carry = d >> 32;
-            L[k] = d & 4294967295LL;
-        }
-        L[ICP_LIMBS - 1] = -1 - L[ICP_LIMBS - 1] + carry;
-    }
-    // The magnitude as six 32-bit digits, rounded to float64 ONCE (to nearest, ties to even): the 64 bits from the leading digit down
-    // plus the digit below them, the rest as a sticky bit.  Adding the digits as doubles would round more than once, and where those
-    // roundings fall depends on the scale, that is on the grid's cell.
-    unsigned long long D[ICP_LIMBS + 1];
-#pragma unroll
-    for (int k = 0; k + 1 < ICP_LIMBS; ++k) D[k] = (unsigned long long)L[k];
-    D[ICP_LIMBS - 1] = (unsigned long long)L[ICP_LIMBS - 1] & 4294967295ULL;
-    D[ICP_LIMBS] = (unsigned long long)L[ICP_LIMBS - 1] >> 32;
-    int h = -1;
-#pragma unroll
-    for (int k = 0; k <= ICP_LIMBS; ++k) h = D[k] ? k : h;
-    double x = 0.0;
-    if (h >= 0) {
-        unsigned long long d0 = 0, d1 = 0, d2 = 0, below = 0;  // digits h, h - 1, h - 2 and the OR of the lower ones
-#pragma unroll
-        for (int k = 0; k <= ICP_LIMBS; ++k) {
-            d0 = k == h ? D[k] : d0;
-            d1 = k == h - 1 ? D[k] : d1;
-            d2 = k == h - 2 ? D[k] : d2;
-            below |= k < h - 2 ? D[k] : 0ULL;
-        }
-        const unsigned long long hi = (d0 << 32) | d1;  // >= 2^32
-        const int lz = __clzll((long long)hi);         // 0 .. 31
-        const unsigned long long m = lz ? (hi << lz) | (d2 >> (32 - lz)) : hi;  // bit 63 set
-        const bool sticky = ((d2 << lz) & 4294967295ULL) != 0 || below != 0;
-        unsigned long long q = m >> 11;
-        const unsigned long long r = m & 2047ULL;
-        if (r > 1024ULL || (r == 1024ULL && (sticky || (q & 1ULL)))) q += 1;
-        x = __builtin_ldexp((double)q, 11 - lz + 32 * (h - 1));  // exact: q <= 2^53
-    }
-    x = x / scale.to_digits[i];  // exact: a power of two
-    sums[i] = neg ? -x : x;
+// sums[i]: one workgroup (one wave) per sum (exact_sum.hpp)
+__global__ __launch_bounds__(EXACT_FINISH_THREADS) void icp_finish_kernel(const long long* __restrict__ partial, int nb, IcpScale scale,
+                                                                          double* __restrict__ sums) {
+    exact_finish<ICP_SUMS>(partial, nb, scale, sums);
 }
 
 // ---- pmn_voxel_mean ---------------------------------------------------------------------------------------------------------------------
@@ -291,11 +228,7 @@ extern "C" int pmn_icp_accumulate(const float* to_xyz, const long long* to_keys,
     }
     bound[16] = max_dist * max_dist;
     for (int i = 0; i < ICP_SUMS; ++i) {
-        int e = 0;
-        (void)std::frexp(bound[i], &e);  // bound < 2^e; one more bit of margin for the roundings above
-        e += 1;
-        if (!std::isfinite(bound[i]) || e > 800 || e < -800) return PMN_ERR_SHAPE;  // the scaling must stay a normal float64
-        a.scale.to_digits[i] = std::ldexp(1.0, 32 * (ICP_LIMBS - 1) + 29 - e);
+        if (!exact_scale(bound[i], a.scale.to_digits[i])) return PMN_ERR_SHAPE;  // the scaling must stay a normal float64
     }
     a.src = src;
     a.order = order;
@@ -307,7 +240,7 @@ extern "C" int pmn_icp_accumulate(const float* to_xyz, const long long* to_keys,
     a.nb = (int)PMN_ICP_BLOCKS(n);
     PMN_LAUNCH(icp_accumulate_kernel, dim3((unsigned)a.nb), dim3(64), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
-    PMN_LAUNCH(icp_finish_kernel, dim3(ICP_SUMS), dim3(ICP_FINISH_THREADS), 0, (hipStream_t)stream, (const long long*)a.partial, a.nb,
+    PMN_LAUNCH(icp_finish_kernel, dim3(ICP_SUMS), dim3(EXACT_FINISH_THREADS), 0, (hipStream_t)stream, (const long long*)a.partial, a.nb,
                a.scale, sums);
     PMN_CHECK_LAUNCH();
     return PMN_OK;

@@ -10,7 +10,8 @@ There is no CPU path: the searches refuse host tensors.  The clouds come from pl
 The same grid serves cloud cleaning (clean_cloud.py): pmn_knn_distance and pmn_radius_count are the k nearest
 neighbours and the number of points within a radius, and statistical_outliers / radius_outliers the two filters built on them.
 cluster_dbscan (cluster_cloud.py) takes a cloud apart into its dense pieces over the same grid: pmn_cloud_core and
-pmn_cloud_dbscan (csrc/cloud_cluster.hip).
+pmn_cloud_dbscan (csrc/cloud_cluster.hip).  segment_plane / segment_planes (segment_cloud.py) find the dominant planes
+by seeded RANSAC: pmn_plane_score and pmn_plane_inliers (csrc/cloud_plane.hip) need no grid.
 
 Semantics: every distance is sqrt(dx*dx + dy*dy + dz*dz) of the float32 PLY coordinates widened to float64; the visiting
 order of the reduction is an explicit, seeded permutation (the MATLAB draws an unseeded randperm), and for a given order the result is
@@ -375,6 +376,285 @@ def select_clusters(labels: torch.Tensor, sizes: torch.Tensor, min_cluster_point
         good = good & (torch.arange(int(sizes.numel()), device=sizes.device) < int(keep_largest))
     good = torch.cat([good, good.new_zeros(1)])  # label -1 reads the last entry
     return good[labels]
+
+
+# ---- planes ------------------------------------------------------------------------------------------------------------
+# Named settings, chosen by reasoning and not measured optima: 1024 hypotheses find a plane that holds a fifth of the cloud with
+# probability 1 - (1 - 0.2^3)^1024 > 0.999; three refits because a least-squares fit of the inliers of a good hypothesis moves little
+# after the first.  A threshold of two spacings is the band a surface sampled at that spacing fills.
+PLANE_HYPOTHESES = 1024
+PLANE_REFITS = 3
+PLANE_THRESHOLD_SPACINGS = 2.0
+
+
+def _plane_inputs(what: str, points, normals, active, threshold, min_cos):
+    """The checked point inputs of plane_score / plane_inliers: (points, normals or None, active uint8 or None)."""
+    points = _points(points, "points")
+    n, dev = int(points.shape[0]), points.device
+    if not (isinstance(threshold, (int, float, np.floating, np.integer)) and threshold >= 0.0 and np.isfinite(threshold)):
+        raise PmnError(f"{what}: threshold must be finite and >= 0, got {threshold!r}")
+    if not (isinstance(min_cos, (int, float, np.floating, np.integer)) and 0.0 <= min_cos <= 1.0):
+        raise PmnError(f"{what}: min_cos must lie in [0, 1], got {min_cos!r}")
+    if min_cos > 0.0 and normals is None:
+        raise PmnError(f"{what}: min_cos > 0 needs normals")
+    if normals is not None:
+        normals = _per_point(normals, "normals", what, torch.float32, n, dev)
+        if not normals.is_contiguous():
+            raise PmnError(f"{what}: normals must be contiguous")
+        bad = int((~torch.isfinite(normals)).any(1).sum())
+        if bad:
+            raise PmnError(f"{what}: {bad} normals are not finite")
+    if active is not None:
+        if not isinstance(active, torch.Tensor) or not active.is_cuda or active.device != dev:
+            raise PmnError(f"{what}: active must be a tensor on {dev} (no CPU fallback)")
+        if active.dtype not in (torch.bool, torch.uint8) or tuple(active.shape) != (n,):
+            raise PmnError(f"{what}: active: expected bool or uint8 [{n}], got {active.dtype} {tuple(active.shape)}")
+        active = (active != 0).to(torch.uint8).contiguous()
+    return points, normals, active
+
+
+def plane_score(points: torch.Tensor, planes: torch.Tensor, threshold: float, normals: Optional[torch.Tensor] = None,
+                active: Optional[torch.Tensor] = None, min_cos: float = 0.0) -> torch.Tensor:
+    """pmn_plane_score: int32 [H], the number of inliers of every row (a, b, c, d) of ``planes`` (float64 [H,4] on the device) among
+    ``points``: fabs(a * x + b * y + c * z + d) <= threshold in float64 and, with ``min_cos`` > 0, fabs(a * nx + b * ny + c * nz) >=
+    min_cos on ``normals``; points with ``active`` (bool or uint8 [n]) == 0 never count; a row with a non-finite entry scores 0.
+    More than 4096 rows are scored in several calls."""
+    points, normals, active = _plane_inputs("plane_score", points, normals, active, threshold, min_cos)
+    dev = points.device
+    if not isinstance(planes, torch.Tensor) or not planes.is_cuda or planes.device != dev:
+        raise PmnError(f"plane_score: planes must be a tensor on {dev} (no CPU fallback)")
+    if planes.dtype != torch.float64 or planes.dim() != 2 or planes.shape[1] != 4 or planes.shape[0] < 1 or not planes.is_contiguous():
+        raise PmnError(f"plane_score: planes: expected a contiguous float64 [H,4] tensor with H >= 1, got {planes.dtype} "
+                       f"{tuple(planes.shape)}")
+    H = int(planes.shape[0])
+    counts = torch.empty(H, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        for h0 in range(0, H, _lib.PLANE_MAX_HYPOTHESES):
+            h1 = min(H, h0 + _lib.PLANE_MAX_HYPOTHESES)
+            check(L.pmn_plane_score(points.data_ptr(), normals.data_ptr() if normals is not None else None,
+                                    active.data_ptr() if active is not None else None, int(points.shape[0]), planes[h0:h1].data_ptr(),
+                                    h1 - h0, float(threshold), float(min_cos), counts[h0:h1].data_ptr(), _stream(points)),
+                  "pmn_plane_score")
+    return counts
+
+
+def plane_frame(points: torch.Tensor, active: Optional[torch.Tensor] = None):
+    """(centre, extent), float64 [3] each on the host: the centre (lo + hi) * 0.5 of the bounding box of the active points, in float64
+    from the float32 coordinates, and the bound max(hi - centre, centre - lo) of |p - centre| that plane_inliers scales its sums by."""
+    p = points if active is None else points[active != 0]
+    if p.shape[0] < 1:
+        raise PmnError("plane_frame: no active point")
+    lo, hi = p.min(0).values.double().cpu().numpy(), p.max(0).values.double().cpu().numpy()
+    centre = (lo + hi) * 0.5
+    return centre, np.maximum(hi - centre, centre - lo)
+
+
+def plane_inliers(points: torch.Tensor, plane, threshold: float, normals: Optional[torch.Tensor] = None,
+                  active: Optional[torch.Tensor] = None, min_cos: float = 0.0, centre=None, extent=None, return_mask: bool = True,
+                  scratch: Optional[torch.Tensor] = None):
+    """pmn_plane_inliers: (mask bool [n] on the device or None, sums float64 [10] on the device) of ONE ``plane`` (4 finite floats on
+    the host), with plane_score's inlier test.  sums over the inliers, with a = p - centre: [0] their number, [1..3] the sum of a,
+    [4..9] of ax ax, ax ay, ax az, ay ay, ay az, az az -- exact up to one rounding each, hence the same bits on every run.  ``centre``
+    and ``extent`` default to plane_frame(points, active); a given extent must bound |p - centre| over the active points."""
+    points, normals, active = _plane_inputs("plane_inliers", points, normals, active, threshold, min_cos)
+    n, dev = int(points.shape[0]), points.device
+    plane = np.asarray(plane, np.float64).reshape(-1)
+    if plane.shape != (4,) or not np.isfinite(plane).all():
+        raise PmnError(f"plane_inliers: plane must be 4 finite numbers, got {plane.tolist()}")
+    if centre is None or extent is None:
+        if centre is not None or extent is not None:
+            raise PmnError("plane_inliers: give centre and extent together, or neither")
+        centre, extent = plane_frame(points, active)
+    centre, extent = np.asarray(centre, np.float64).reshape(-1), np.asarray(extent, np.float64).reshape(-1)
+    if centre.shape != (3,) or extent.shape != (3,) or not np.isfinite(centre).all() or not np.isfinite(extent).all() \
+            or (extent < 0.0).any():
+        raise PmnError(f"plane_inliers: centre must be 3 finite numbers and extent 3 finite numbers >= 0, got {centre.tolist()} and "
+                       f"{extent.tolist()}")
+    words = _lib.plane_scratch(n)
+    if scratch is None:
+        scratch = torch.empty(words, dtype=torch.int64, device=dev)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != dev or scratch.dtype != torch.int64 or scratch.dim() != 1 \
+            or scratch.numel() < words or not scratch.is_contiguous():
+        raise PmnError(f"plane_inliers: scratch must be a contiguous int64 tensor of at least {words} words on {dev}")
+    mask = torch.empty(n, dtype=torch.uint8, device=dev) if return_mask else None
+    sums = torch.empty(_lib.PLANE_SUMS, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_plane_inliers(points.data_ptr(), normals.data_ptr() if normals is not None else None,
+                                           active.data_ptr() if active is not None else None, n, (ctypes.c_double * 4)(*plane.tolist()),
+                                           float(threshold), float(min_cos), (ctypes.c_double * 3)(*centre.tolist()),
+                                           (ctypes.c_double * 3)(*extent.tolist()), scratch.data_ptr(), int(scratch.numel()),
+                                           mask.data_ptr() if return_mask else None, sums.data_ptr(), _stream(points)),
+              "pmn_plane_inliers")
+    return (mask.bool() if return_mask else None), sums
+
+
+def _plane_sign(nrm: np.ndarray) -> np.ndarray:
+    """The sign rule: the component of largest magnitude is positive, ties go to the lowest axis (np.argmax takes the first)."""
+    k = np.argmax(np.abs(nrm), axis=-1)
+    s = np.where(np.take_along_axis(nrm, k[..., None], -1)[..., 0] < 0.0, -1.0, 1.0)
+    return nrm * s[..., None]
+
+
+def plane_hypotheses(triplets, indices=None) -> np.ndarray:
+    """The planes through ``triplets`` ([H,3,3]: H times three points, any float type, taken as float64), float64 [H,4] on the host;
+    DESIGN.md 34 states every expression.  u = p1 - p0, v = p2 - p0, w = u x v, l2 = w . w; a row is NaN when l2 is not > 0 or, with
+    ``indices`` ([H,3] integers), when two of its indices coincide; else nrm = w / sqrt(l2) with the sign rule of _plane_sign and
+    d = -(nrm . p0)."""
+    p = np.asarray(triplets, np.float64)
+    if p.ndim != 3 or p.shape[1:] != (3, 3):
+        raise PmnError(f"plane_hypotheses: expected [H,3,3] points, got {p.shape}")
+    u, v = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    w = np.stack([u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1], u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2], u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]], 1)
+    l2 = w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1] + w[:, 2] * w[:, 2]
+    bad = ~(l2 > 0.0)
+    if indices is not None:
+        t = np.asarray(indices)
+        bad |= (t[:, 0] == t[:, 1]) | (t[:, 0] == t[:, 2]) | (t[:, 1] == t[:, 2])
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        nrm = _plane_sign(w / np.sqrt(l2)[:, None])
+        d = -(nrm[:, 0] * p[:, 0, 0] + nrm[:, 1] * p[:, 0, 1] + nrm[:, 2] * p[:, 0, 2])
+    planes = np.concatenate([nrm, d[:, None]], 1)
+    planes[bad | ~np.isfinite(planes).all(1)] = np.nan
+    return planes
+
+
+def plane_from_sums(sums, centre) -> Optional[np.ndarray]:
+    """The least-squares plane of plane_inliers' ten ``sums`` (host float64): the mean m = sums[1:4] / count, the covariance
+    C_cd = S_cd / count - m_c * m_d, the eigenvector of np.linalg.eigh's smallest eigenvalue under the sign rule, through centre + m.
+    None with fewer than 3 inliers or a result that is not finite."""
+    s, c = np.asarray(sums, np.float64), np.asarray(centre, np.float64)
+    cnt = s[0]
+    if cnt < 3.0:
+        return None
+    m = s[1:4] / cnt
+    C = np.empty((3, 3), np.float64)
+    for k, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        C[i, j] = C[j, i] = s[4 + k] / cnt - m[i] * m[j]
+    if not np.isfinite(C).all():
+        return None
+    nrm = _plane_sign(np.linalg.eigh(C)[1][:, 0])
+    d = -(nrm[0] * (c[0] + m[0]) + nrm[1] * (c[1] + m[1]) + nrm[2] * (c[2] + m[2]))
+    plane = np.array([nrm[0], nrm[1], nrm[2], d], np.float64)
+    return plane if np.isfinite(plane).all() else None
+
+
+def plane_rmse(sums, centre, plane) -> float:
+    """sqrt(mean r * r) over the inliers from the ten sums, on the host: with e = a cx + b cy + c cz + d the residual is
+    r = n . a + e for a = p - centre, so sum r r = n^T S n + 2 e n . s + count e e (clamped at 0 before the root)."""
+    s, c, p = np.asarray(sums, np.float64), np.asarray(centre, np.float64), np.asarray(plane, np.float64)
+    if s[0] < 1.0:
+        return 0.0
+    e = p[0] * c[0] + p[1] * c[1] + p[2] * c[2] + p[3]
+    q = (p[0] * p[0] * s[4] + p[1] * p[1] * s[7] + p[2] * p[2] * s[9]
+         + 2.0 * (p[0] * p[1] * s[5] + p[0] * p[2] * s[6] + p[1] * p[2] * s[8]))
+    total = q + 2.0 * e * (p[0] * s[1] + p[1] * s[2] + p[2] * s[3]) + s[0] * e * e
+    return float(np.sqrt(max(total, 0.0) / s[0]))
+
+
+def _min_cos(what: str, normals, normal_angle) -> float:
+    if normal_angle is None:
+        return 0.0
+    if not (isinstance(normal_angle, (int, float, np.floating, np.integer)) and 0.0 <= normal_angle <= 90.0):
+        raise PmnError(f"{what}: normal_angle must lie in [0, 90] degrees, got {normal_angle!r}")
+    if normals is None:
+        raise PmnError(f"{what}: normal_angle needs normals")
+    return min(1.0, max(0.0, float(np.cos(np.radians(float(normal_angle))))))
+
+
+def _plane_settings(what: str, points, threshold, hypotheses, seed, refine):
+    for name, v, lo in (("hypotheses", hypotheses, 1), ("seed", seed, 0), ("refine", refine, 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise PmnError(f"{what}: {name} must be an integer >= {lo}, got {v!r}")
+    return PLANE_THRESHOLD_SPACINGS * cloud_spacing(points) if threshold is None else threshold
+
+
+def _segment_one(what: str, points, normals, active, threshold: float, min_cos: float, hypotheses: int, refine: int, rng):
+    """One plane of the active points, the generator ``rng`` going on from where it stands."""
+    n, dev = int(points.shape[0]), points.device
+    idx = torch.arange(n, device=dev) if active is None else torch.nonzero(active, as_tuple=False)[:, 0]
+    m = int(idx.numel())
+    if m < 3:
+        raise PmnError(f"{what}: a plane needs 3 active points, got {m}")
+    trip = rng.integers(0, m, size=(hypotheses, 3))
+    drawn = points[idx[torch.from_numpy(trip).to(dev)]].cpu().numpy()  # [H,3,3]: the 3H points, gathered on the device
+    planes = plane_hypotheses(drawn, trip)
+    if np.isnan(planes).any(1).all():
+        raise PmnError(f"{what}: all {hypotheses} hypotheses are invalid (repeated or collinear points)")
+    counts = plane_score(points, torch.from_numpy(planes).to(dev), threshold, normals, active, min_cos).cpu().numpy()
+    best = int(np.argmax(counts))
+    centre, extent = plane_frame(points, active)
+    scratch = torch.empty(_lib.plane_scratch(n), dtype=torch.int64, device=dev)
+    kw = dict(normals=normals, active=active, min_cos=min_cos, centre=centre, extent=extent, scratch=scratch)
+    plane = planes[best]
+    mask, sums = plane_inliers(points, plane, threshold, **kw)
+    sums = sums.cpu().numpy()
+    refits = 0
+    for _ in range(refine):
+        new = plane_from_sums(sums, centre)
+        if new is None:
+            break
+        mask2, sums2 = plane_inliers(points, new, threshold, **kw)
+        sums2 = sums2.cpu().numpy()
+        if sums2[0] < sums[0]:  # a refit that loses inliers is rejected and ends the loop
+            break
+        same = bool(torch.equal(mask2, mask))
+        plane, mask, sums, refits = new, mask2, sums2, refits + 1
+        if same:
+            break
+    return {"plane": plane, "inliers": mask, "count": int(sums[0]), "rmse": plane_rmse(sums, centre, plane), "hypothesis": best,
+            "refits": refits}
+
+
+def segment_plane(points: torch.Tensor, threshold: Optional[float] = None, hypotheses: int = PLANE_HYPOTHESES, seed: int = 0,
+                  refine: int = PLANE_REFITS, normals: Optional[torch.Tensor] = None, normal_angle: Optional[float] = None,
+                  active: Optional[torch.Tensor] = None) -> dict:
+    """The dominant plane of a cloud (Open3D segment_plane, PCL SACSegmentation) on the device: seeded RANSAC scored by pmn_plane_score
+    and refitted by least squares over pmn_plane_inliers' exact sums.  Returns a dict: ``plane`` float64 [4] (a, b, c, d
+    with a unit normal whose largest component is positive), ``inliers`` bool [n] on the device, ``count``, ``rmse`` (of the residuals
+    of the inliers), ``hypothesis`` (the index of the winning draw) and ``refits`` (the refits that were accepted, at most ``refine``).
+    A point is an inlier when fabs(a x + b y + c z + d) <= ``threshold`` (default: PLANE_THRESHOLD_SPACINGS times cloud_spacing) and,
+    with ``normal_angle`` (degrees, needs ``normals``), its normal lies within that angle of the plane's, either way round.
+    ``hypotheses`` triplets of the active points are drawn by np.random.Generator(PCG64(seed)); the highest count wins, ties go to the
+    lowest index.  Every output is a function of (points, normals, active, settings, seed), bit for bit; the ORDER of the points
+    matters, through the draw.  PmnError with fewer than 3 active points or when every hypothesis is invalid."""
+    threshold = _plane_settings("segment_plane", points, threshold, hypotheses, seed, refine)
+    min_cos = _min_cos("segment_plane", normals, normal_angle)
+    points, normals, active = _plane_inputs("segment_plane", points, normals, active, threshold, min_cos)
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    return _segment_one("segment_plane", points, normals, active, float(threshold), min_cos, int(hypotheses), int(refine), rng)
+
+
+def segment_planes(points: torch.Tensor, threshold: Optional[float] = None, max_planes: int = 1, min_inliers: int = 3,
+                   hypotheses: int = PLANE_HYPOTHESES, seed: int = 0, refine: int = PLANE_REFITS,
+                   normals: Optional[torch.Tensor] = None, normal_angle: Optional[float] = None,
+                   active: Optional[torch.Tensor] = None) -> dict:
+    """Up to ``max_planes`` planes, one after the other: after a plane is accepted its inliers leave the active set and the SAME
+    generator goes on drawing.  Extraction stops after ``max_planes``, when the best plane holds fewer than ``min_inliers`` points (it is
+    not accepted), or when fewer than 3 active points are left.  Returns a dict: ``labels`` int64 [n] on the device (-1, or the plane's
+    index in order of extraction), ``planes`` float64 [k,4], ``counts`` (list of k) and ``results`` (segment_plane's dict per plane)."""
+    threshold = _plane_settings("segment_planes", points, threshold, hypotheses, seed, refine)
+    for name, v in (("max_planes", max_planes), ("min_inliers", min_inliers)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise PmnError(f"segment_planes: {name} must be an integer >= 1, got {v!r}")
+    min_cos = _min_cos("segment_planes", normals, normal_angle)
+    points, normals, active = _plane_inputs("segment_planes", points, normals, active, threshold, min_cos)
+    n, dev = int(points.shape[0]), points.device
+    left = torch.ones(n, dtype=torch.uint8, device=dev) if active is None else active.clone()
+    if int(left.sum()) < 3:
+        raise PmnError(f"segment_planes: a plane needs 3 active points, got {int(left.sum())}")
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    labels = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    results = []
+    while len(results) < max_planes and int(left.sum()) >= 3:
+        one = _segment_one("segment_planes", points, normals, left, float(threshold), min_cos, int(hypotheses), int(refine), rng)
+        if one["count"] < min_inliers:
+            break
+        labels[one["inliers"]] = len(results)
+        left[one["inliers"]] = 0
+        results.append(one)
+    return {"labels": labels, "planes": np.array([r["plane"] for r in results], np.float64).reshape(-1, 4),
+            "counts": [r["count"] for r in results], "results": results}
 
 
 def _viewpoints(what: str, viewpoints, device) -> Optional[torch.Tensor]:
