@@ -14,10 +14,12 @@ points are written in their original order with ply.write_ply: x y z [nx ny nz] 
 white where it had no colours; other properties are not carried over.  `eval_dtu.py --ply_name fused_clean.ply` and `eval_tnt.py
 --ply_path .../fused_clean.ply` read the result.  One process on one ROCm GPU; torchrun is not supported."""
 import argparse
-import json
-import os
 import sys
 import time
+
+import cloud_tool
+
+TOOL = "clean_cloud.py"
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -39,29 +41,16 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def _fail(msg: str) -> int:
-    print("clean_cloud.py: " + " ".join(str(msg).split()), file=sys.stderr)
-    return 2
-
-
 def clean_file(src: str, dst: str, args, device):
     """Cleans one file; returns (its report entry, the device in use)."""
     import numpy as np
-    import torch
-    from patchmatchnet_amd import ply, pointcloud as PC
-    from patchmatchnet_amd._lib import PmnError
+    from patchmatchnet_amd import pointcloud as PC
 
-    model = ply.read_ply_model(src)
-    if model["faces"] is not None:
-        raise PmnError(f"{src}: a mesh ({len(model['faces'])} faces), not a cloud; drop a mesh's floaters with mesh.py "
-                       f"--keep_components / --min_component_faces")
+    model = cloud_tool.load_cloud(src, mesh_hint="drop a mesh's floaters with mesh.py --keep_components / --min_component_faces")
     n = len(model["vertices"])
-    if n < 1:
-        raise PmnError(f"{src}: no points")
-    if device is None:  # everything that can be refused without the GPU has been
-        device = torch.device(args.device)
+    device = cloud_tool.device_of(args, device)
     t0 = time.perf_counter()
-    pts = torch.from_numpy(np.ascontiguousarray(model["vertices"], np.float32)).to(device)
+    pts = cloud_tool.upload(model["vertices"], np.float32, device)
     out = {"input": src, "output": dst, "points": n}
     if args.method == "statistical":
         keep, _, threshold = PC.statistical_outliers(pts, k=args.k, std_ratio=args.std_ratio, max_dist=args.max_dist, cell=args.cell)
@@ -72,54 +61,34 @@ def clean_file(src: str, dst: str, args, device):
         what = f">= {args.min_neighbors} neighbours within {args.radius:g}"
     keep = keep.cpu().numpy()
     out["seconds_search"] = time.perf_counter() - t0
-    colors = model["colors"][keep] if model["colors"] is not None else np.full((int(keep.sum()), 3), 255, np.uint8)
-    ply.write_ply(dst, model["vertices"][keep], colors, model["normals"][keep] if model["normals"] is not None else None)
+    cloud_tool.write_kept(dst, model, keep)
     out.update(kept=int(keep.sum()), removed=int(n - keep.sum()))
     print(f"{src}: {n} points read, {out['kept']} kept, {out['removed']} removed ({what}) -> {dst}")
     return out, device
 
 
-def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("clean_cloud.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
-        return 2
+def check_args(args) -> None:
+    """ValueError for what can be refused before any file is read."""
     if args.method == "radius":
         if args.radius is None or args.min_neighbors is None:
-            return _fail("--method radius needs --radius and --min_neighbors")
+            raise ValueError("--method radius needs --radius and --min_neighbors")
         if not (args.radius >= 0.0 and args.radius < float("inf")) or args.min_neighbors < 0:
-            return _fail(f"--radius must be finite and >= 0 and --min_neighbors >= 0, got {args.radius} and {args.min_neighbors}")
+            raise ValueError(f"--radius must be finite and >= 0 and --min_neighbors >= 0, got {args.radius} and {args.min_neighbors}")
     elif not 1 <= args.k <= 32:
-        return _fail(f"--k must be in 1..32, got {args.k}")
-    if args.scan_list:
-        if not os.path.isdir(args.input):
-            return _fail(f"--scan_list needs --input to be a folder, got {args.input}")
-        if not os.path.isfile(args.scan_list):
-            return _fail(f"invalid scan list file: {args.scan_list}")
-        with open(args.scan_list) as f:
-            scans = [ln.strip() for ln in f if ln.strip()]
-        jobs = [(os.path.join(args.input, s, "fused.ply"), os.path.join(args.output or args.input, s, "fused_clean.ply")) for s in scans]
-    else:
-        if not args.output:
-            return _fail("--output is required for a single file")
-        jobs = [(args.input, args.output)]
-    for src, _ in jobs:
-        if not os.path.isfile(src):
-            return _fail(f"no such file: {src}")
-    from patchmatchnet_amd import _lib
-    files, device = [], None
+        raise ValueError(f"--k must be in 1..32, got {args.k}")
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    if cloud_tool.refuse_torchrun(TOOL):
+        return 2
     try:
-        for src, dst in jobs:
-            one, device = clean_file(src, dst, args, device)
-            files.append(one)
-    except _lib.PmnError as e:
-        return _fail(e)
-    if args.report:
-        settings = {k: getattr(args, k) for k in ("method", "k", "std_ratio", "radius", "min_neighbors", "cell", "max_dist")}
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as f:
-            json.dump({"abi": _lib.ABI_VERSION, **settings, "files": files}, f, indent=1)
-    return 0
+        check_args(args)
+        jobs = cloud_tool.jobs(args, "fused.ply", "fused_clean.ply")
+    except ValueError as e:
+        return cloud_tool.fail(TOOL, e)
+    settings = {k: getattr(args, k) for k in ("method", "k", "std_ratio", "radius", "min_neighbors", "cell", "max_dist")}
+    return cloud_tool.run(TOOL, jobs, lambda src, dst, scan, device: clean_file(src, dst, args, device), settings, args.report)
 
 
 if __name__ == "__main__":

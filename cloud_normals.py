@@ -21,11 +21,13 @@ unchanged and in order (white where the input had no colours), normals added or 
 shades the result and Poisson meshers read it.  One process on one ROCm GPU; torchrun is not supported."""
 import argparse
 import glob
-import json
 import os
 import sys
 import time
 
+import cloud_tool
+
+TOOL = "cloud_normals.py"
 ORIENT = ("cameras", "viewpoint", "existing", "none")
 
 
@@ -49,11 +51,6 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--report", type=str, default="", help="write the counts and settings as JSON")
     return p
-
-
-def _fail(msg: str) -> int:
-    print("cloud_normals.py: " + " ".join(str(msg).split()), file=sys.stderr)
-    return 2
 
 
 def resolve_orient(args) -> str:
@@ -92,27 +89,21 @@ def camera_centres(folder: str):
 def normals_file(src: str, dst: str, args, mode: str, views, device):
     """Normals for one file; returns (its report entry, the device in use)."""
     import numpy as np
-    import torch
-    from patchmatchnet_amd import _lib, ply, pointcloud as PC
+    from patchmatchnet_amd import _lib, pointcloud as PC
     from patchmatchnet_amd._lib import PmnError
 
-    model = ply.read_ply_model(src)
-    if model["faces"] is not None:
-        raise PmnError(f"{src}: a mesh ({len(model['faces'])} faces), not a cloud; mesh.py writes vertex normals from the faces")
+    model = cloud_tool.load_cloud(src, mesh_hint="mesh.py writes vertex normals from the faces")
     n = len(model["vertices"])
-    if n < 1:
-        raise PmnError(f"{src}: no points")
     if mode == "existing" and model["normals"] is None:
         raise PmnError(f"{src}: --orient existing needs normals (nx ny nz) in the input file")
     if views is not None and len(views) > _lib.NORMAL_MAX_VIEWPOINTS:
         raise PmnError(f"{len(views)} cameras: at most {_lib.NORMAL_MAX_VIEWPOINTS} viewpoints")
-    if device is None:  # everything that can be refused without the GPU has been
-        device = torch.device(args.device)
+    device = cloud_tool.device_of(args, device)
     t0 = time.perf_counter()
-    pts = torch.from_numpy(np.ascontiguousarray(model["vertices"], np.float32)).to(device)
+    pts = cloud_tool.upload(model["vertices"], np.float32, device)
     cell = PC.default_cell(pts) if args.cell is None else float(args.cell)
     max_dist = PC.CLEAN_MAX_DIST_CELLS * cell if args.max_dist is None else float(args.max_dist)
-    like = torch.from_numpy(np.ascontiguousarray(model["normals"], np.float32)).to(device) if mode == "existing" else None
+    like = cloud_tool.upload(model["normals"], np.float32, device) if mode == "existing" else None
     normal, variation, count = PC.estimate_normals(pts, k=args.k, max_dist=max_dist, cell=cell, viewpoints=views, orient_like=like,
                                                    line_ratio=args.line_ratio, return_variation=True, return_count=True)
     has = (normal != 0).any(1)
@@ -122,8 +113,7 @@ def normals_file(src: str, dst: str, args, mode: str, views, device):
     normal, has = normal.cpu().numpy(), has.cpu().numpy()
     seconds = time.perf_counter() - t0  # the upload, the cell search, the grid, the kernel, the counts and the copy back
     keep = has if args.drop_degenerate else np.ones(n, bool)
-    colors = model["colors"] if model["colors"] is not None else np.full((n, 3), 255, np.uint8)
-    ply.write_ply(dst, model["vertices"][keep], colors[keep], normal[keep])
+    cloud_tool.write_kept(dst, model, keep, normals=normal)
     out = {"input": src, "output": dst, "n": n, "k": args.k, "cell": cell, "max_dist": max_dist, "orient": mode,
            "viewpoints": 0 if views is None else len(views), "zero_normals": zero, "capped": capped, "written": int(keep.sum()),
            "mean_variation": mean_variation, "seconds_device": seconds}
@@ -132,63 +122,44 @@ def normals_file(src: str, dst: str, args, mode: str, views, device):
     return out, device
 
 
-def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("cloud_normals.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
-        return 2
+def check_args(args) -> str:
+    """The orientation mode; ValueError for what can be refused before any file is read."""
     if not 1 <= args.k <= 32:
-        return _fail(f"--k must be in 1..32, got {args.k}")
+        raise ValueError(f"--k must be in 1..32, got {args.k}")
     if not (args.line_ratio >= 0.0 and args.line_ratio < float("inf")):
-        return _fail(f"--line_ratio must be finite and >= 0, got {args.line_ratio}")
+        raise ValueError(f"--line_ratio must be finite and >= 0, got {args.line_ratio}")
     for name in ("max_dist", "cell"):
         v = getattr(args, name)
         if v is not None and not (v > 0.0 and v < float("inf")):
-            return _fail(f"--{name} must be positive and finite, got {v}")
-    try:
-        mode = resolve_orient(args)
-    except ValueError as e:
-        return _fail(e)
-    if args.scan_list:
-        if not os.path.isdir(args.input):
-            return _fail(f"--scan_list needs --input to be a folder, got {args.input}")
-        if not os.path.isfile(args.scan_list):
-            return _fail(f"invalid scan list file: {args.scan_list}")
-        with open(args.scan_list) as f:
-            scans = [ln.strip() for ln in f if ln.strip()]
-        jobs = [(os.path.join(args.input, s, "fused.ply"), os.path.join(args.output or args.input, s, "fused_normals.ply"),
-                 os.path.join(args.mvs_folder, s)) for s in scans]
-    else:
-        if not args.output:
-            return _fail("--output is required for a single file")
-        jobs = [(args.input, args.output, args.mvs_folder)]
-    for src, _, _ in jobs:
-        if not os.path.isfile(src):
-            return _fail(f"no such file: {src}")
-    import numpy as np
+            raise ValueError(f"--{name} must be positive and finite, got {v}")
+    return resolve_orient(args)
 
-    from patchmatchnet_amd import _lib
-    files, device = [], None
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    if cloud_tool.refuse_torchrun(TOOL):
+        return 2
     try:
-        for src, dst, cams in jobs:
-            views = None
-            if mode == "cameras":
-                try:
-                    views = camera_centres(cams)
-                except FileNotFoundError as e:
-                    return _fail(f"no camera files: {e}")
-            elif mode == "viewpoint":
-                views = np.asarray([args.viewpoint], np.float64)
-            one, device = normals_file(src, dst, args, mode, views, device)
-            files.append(one)
-    except _lib.PmnError as e:
-        return _fail(e)
-    if args.report:
-        settings = {"k": args.k, "line_ratio": args.line_ratio, "orient": mode, "drop_degenerate": bool(args.drop_degenerate)}
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as f:
-            json.dump({"abi": _lib.ABI_VERSION, **settings, "files": files}, f, indent=1)
-    return 0
+        mode = check_args(args)
+        jobs = cloud_tool.jobs(args, "fused.ply", "fused_normals.ply")
+    except ValueError as e:
+        return cloud_tool.fail(TOOL, e)
+
+    def per_file(src, dst, scan, device):  # the scan's cameras are read before the file is opened
+        import numpy as np
+        from patchmatchnet_amd._lib import PmnError
+        views = None
+        if mode == "cameras":
+            try:
+                views = camera_centres(os.path.join(args.mvs_folder, scan) if scan else args.mvs_folder)
+            except FileNotFoundError as e:
+                raise PmnError(f"no camera files: {e}") from e
+        elif mode == "viewpoint":
+            views = np.asarray([args.viewpoint], np.float64)
+        return normals_file(src, dst, args, mode, views, device)
+
+    settings = {"k": args.k, "line_ratio": args.line_ratio, "orient": mode, "drop_degenerate": bool(args.drop_degenerate)}
+    return cloud_tool.run(TOOL, jobs, per_file, settings, args.report)
 
 
 if __name__ == "__main__":

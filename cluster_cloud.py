@@ -20,11 +20,12 @@ and in their order with ply.write_ply: x y z [nx ny nz] red green blue, normals 
 --labels writes the int32 label of EVERY input point (-1 noise; clusters numbered by descending size).  --cell changes the time only.
 One process on one ROCm GPU; torchrun is not supported."""
 import argparse
-import json
-import os
 import sys
 import time
 
+import cloud_tool
+
+TOOL = "cluster_cloud.py"
 NOISE_GREY = 128
 
 
@@ -54,11 +55,6 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def _fail(msg: str) -> int:
-    print("cluster_cloud.py: " + " ".join(str(msg).split()), file=sys.stderr)
-    return 2
-
-
 def cluster_colors(labels):
     """uint8 [n,3]: a fixed colour per label, the low three bytes of the splitmix64 finaliser (csrc/meshops.hip's mesh_mix) of
     (label + 1) * 0x9E3779B97F4A7C15, each byte lifted into 64..255 so that no cluster is dark; noise (-1) is grey."""
@@ -79,20 +75,14 @@ def cluster_file(src: str, dst: str, args, device):
     """Clusters one file; returns (its report entry, the device in use)."""
     import numpy as np
     import torch
-    from patchmatchnet_amd import ply, pointcloud as PC
+    from patchmatchnet_amd import pointcloud as PC
     from patchmatchnet_amd._lib import PmnError
 
-    model = ply.read_ply_model(src)
-    if model["faces"] is not None:
-        raise PmnError(f"{src}: a mesh ({len(model['faces'])} faces), not a cloud; drop a mesh's floaters with mesh.py "
-                       f"--keep_components / --min_component_faces")
+    model = cloud_tool.load_cloud(src, mesh_hint="drop a mesh's floaters with mesh.py --keep_components / --min_component_faces")
     n = len(model["vertices"])
-    if n < 1:
-        raise PmnError(f"{src}: no points")
-    if device is None:  # everything that can be refused without the GPU has been
-        device = torch.device(args.device)
+    device = cloud_tool.device_of(args, device)
     t0 = time.perf_counter()
-    pts = torch.from_numpy(np.ascontiguousarray(model["vertices"], np.float32)).to(device)
+    pts = cloud_tool.upload(model["vertices"], np.float32, device)
     out = {"input": src, "output": dst, "points": n}
     eps = args.eps
     if eps is None:
@@ -107,14 +97,9 @@ def cluster_file(src: str, dst: str, args, device):
         keep = keep | (labels < 0)
     keep, labels, core = keep.cpu().numpy(), labels.cpu().numpy().astype(np.int32), core.cpu().numpy()
     out["seconds_search"] = time.perf_counter() - t0
-    if args.color_by_cluster:
-        colors = cluster_colors(labels[keep])
-    else:
-        colors = model["colors"][keep] if model["colors"] is not None else np.full((int(keep.sum()), 3), 255, np.uint8)
-    ply.write_ply(dst, model["vertices"][keep], colors, model["normals"][keep] if model["normals"] is not None else None)
+    cloud_tool.write_kept(dst, model, keep, colors=cluster_colors(labels) if args.color_by_cluster else None)
     if args.labels:
-        os.makedirs(os.path.dirname(os.path.abspath(args.labels)), exist_ok=True)
-        np.save(args.labels, labels)
+        cloud_tool.save_side_file(args.labels, lambda path: np.save(path, labels))
     noise = int((labels < 0).sum())
     out.update(eps=float(eps), core=int(core.sum()), border=int(n - noise - core.sum()), noise=noise, clusters=int(sizes.numel()),
                clusters_kept=kept_clusters, kept=int(keep.sum()), largest=[int(v) for v in sizes[:8].cpu().tolist()])
@@ -123,54 +108,33 @@ def cluster_file(src: str, dst: str, args, device):
     return out, device
 
 
+def check_args(args) -> None:
+    """ValueError for what can be refused before any file is read."""
+    if args.eps is not None and not (args.eps >= 0.0 and args.eps < float("inf")):
+        raise ValueError(f"--eps must be finite and >= 0, got {args.eps}")
+    if not (args.eps_spacings >= 0.0 and args.eps_spacings < float("inf")):
+        raise ValueError(f"--eps_spacings must be finite and >= 0, got {args.eps_spacings}")
+    if args.min_points < 1:
+        raise ValueError(f"--min_points must be >= 1, got {args.min_points}")
+    if args.min_cluster_points < 0 or args.keep_clusters < 0:
+        raise ValueError(f"--min_cluster_points and --keep_clusters must be >= 0, got {args.min_cluster_points} and {args.keep_clusters}")
+    if args.cell is not None and not (args.cell > 0.0 and args.cell < float("inf")):
+        raise ValueError(f"--cell must be positive and finite, got {args.cell}")
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("cluster_cloud.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
+    if cloud_tool.refuse_torchrun(TOOL):
         return 2
-    if args.eps is not None and not (args.eps >= 0.0 and args.eps < float("inf")):
-        return _fail(f"--eps must be finite and >= 0, got {args.eps}")
-    if not (args.eps_spacings >= 0.0 and args.eps_spacings < float("inf")):
-        return _fail(f"--eps_spacings must be finite and >= 0, got {args.eps_spacings}")
-    if args.min_points < 1:
-        return _fail(f"--min_points must be >= 1, got {args.min_points}")
-    if args.min_cluster_points < 0 or args.keep_clusters < 0:
-        return _fail(f"--min_cluster_points and --keep_clusters must be >= 0, got {args.min_cluster_points} and {args.keep_clusters}")
-    if args.cell is not None and not (args.cell > 0.0 and args.cell < float("inf")):
-        return _fail(f"--cell must be positive and finite, got {args.cell}")
-    if args.scan_list:
-        if not os.path.isdir(args.input):
-            return _fail(f"--scan_list needs --input to be a folder, got {args.input}")
-        if not os.path.isfile(args.scan_list):
-            return _fail(f"invalid scan list file: {args.scan_list}")
-        if args.labels:
-            return _fail("--labels names one file; it cannot be combined with --scan_list")
-        with open(args.scan_list) as f:
-            scans = [ln.strip() for ln in f if ln.strip()]
-        jobs = [(os.path.join(args.input, s, args.ply_name), os.path.join(args.output or args.input, s, "fused_clusters.ply"))
-                for s in scans]
-    else:
-        if not args.output:
-            return _fail("--output is required for a single file")
-        jobs = [(args.input, args.output)]
-    for src, _ in jobs:
-        if not os.path.isfile(src):
-            return _fail(f"no such file: {src}")
-    from patchmatchnet_amd import _lib
-    files, device = [], None
     try:
-        for src, dst in jobs:
-            one, device = cluster_file(src, dst, args, device)
-            files.append(one)
-    except _lib.PmnError as e:
-        return _fail(e)
-    if args.report:
-        settings = {k: getattr(args, k) for k in ("eps", "eps_spacings", "min_points", "min_cluster_points", "keep_clusters", "keep_noise",
-                                                  "color_by_cluster", "cell")}
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as f:
-            json.dump({"abi": _lib.ABI_VERSION, **settings, "files": files}, f, indent=1)
-    return 0
+        check_args(args)
+        jobs = cloud_tool.jobs(args, args.ply_name, "fused_clusters.ply",
+                               single_only="--labels names one file; it cannot be combined with --scan_list" if args.labels else "")
+    except ValueError as e:
+        return cloud_tool.fail(TOOL, e)
+    settings = {k: getattr(args, k) for k in ("eps", "eps_spacings", "min_points", "min_cluster_points", "keep_clusters", "keep_noise",
+                                              "color_by_cluster", "cell")}
+    return cloud_tool.run(TOOL, jobs, lambda src, dst, scan, device: cluster_file(src, dst, args, device), settings, args.report)
 
 
 if __name__ == "__main__":

@@ -9,9 +9,9 @@ distance is the exact point-to-triangle distance (meshops.point_mesh_distance) w
 nearest point (pointcloud.nn_distance); both are capped at --max_dist (default: twice the diagonal of the two files' common bounding box,
 which no distance reaches).  One process on one ROCm GPU; torchrun is not supported."""
 import argparse
-import json
-import os
 import sys
+
+import cloud_tool
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -41,8 +41,7 @@ def statistics(d) -> dict:
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("compare_mesh.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
+    if cloud_tool.refuse_torchrun("compare_mesh.py"):
         return 2
     import torch
 
@@ -82,9 +81,7 @@ def main(argv=None) -> int:
     out["hausdorff"] = max(out["a_to_b"]["max"], out["b_to_a"]["max"])
     print("hausdorff: %.9g" % out["hausdorff"])
     if args.report:
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as f:
-            json.dump(out, f, indent=1)
+        cloud_tool.write_report(args.report, out)
     return 0
 
 

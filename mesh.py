@@ -20,6 +20,7 @@ import os
 import sys
 import time
 
+import cloud_tool
 
 # pmn_mt_emit winds its triangles so that (B - A) x (C - A) points WITH the TSDF gradient it writes as the normal, from inside to outside
 # (measured on a meshed sphere: DESIGN.md section 30, tests/test_smooth_gpu.py), so normals recomputed from the faces are not flipped.
@@ -213,8 +214,7 @@ def mesh_scan(args, scan, device):
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("mesh.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
+    if cloud_tool.refuse_torchrun("mesh.py"):
         return 2
     if not args.input_folder or not os.path.isdir(args.input_folder):
         raise Exception("Invalid input folder: {}".format(args.input_folder))
@@ -244,8 +244,7 @@ def main(argv=None) -> int:
     if args.scan_list:
         if not os.path.isfile(args.scan_list):
             raise PmnError("Invalid scan list file: {}".format(args.scan_list))
-        with open(args.scan_list) as f:
-            scans = [ln.strip() for ln in f if ln.strip()]
+        scans = cloud_tool.read_scan_list(args.scan_list)
     else:
         scans = [""]
     with torch.no_grad():

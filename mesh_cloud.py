@@ -20,10 +20,12 @@ normals (nx ny nz): cloud_normals.py adds them.  --min_component_faces / --keep_
 written with ply.write_ply_mesh; render.py, eval_dtu.py --mesh_distance 1, eval_tnt.py --mesh_distance 1, compare_mesh.py,
 simplify_mesh.py and smooth_mesh.py read it.  One process on one ROCm GPU; torchrun is not supported."""
 import argparse
-import json
-import os
 import sys
 import time
+
+import cloud_tool
+
+TOOL = "mesh_cloud.py"
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -53,11 +55,6 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def _fail(msg) -> int:
-    print("mesh_cloud.py: " + " ".join(str(msg).split()), file=sys.stderr)
-    return 2
-
-
 def check_args(args) -> None:
     """ValueError for what can be refused before any file is read."""
     if not 1 <= args.k <= 32:
@@ -76,46 +73,25 @@ def check_args(args) -> None:
 
 def jobs_of(args):
     """[(source, destination)] of the arguments; ValueError where they do not name existing files."""
-    if args.scan_list:
-        if not os.path.isdir(args.input):
-            raise ValueError(f"--scan_list needs --input to be a folder, got {args.input}")
-        if not os.path.isfile(args.scan_list):
-            raise ValueError(f"invalid scan list file: {args.scan_list}")
-        with open(args.scan_list) as f:
-            scans = [ln.strip() for ln in f if ln.strip()]
-        jobs = [(os.path.join(args.input, s, args.ply_name), os.path.join(args.output or args.input, s, "mesh_cloud.ply")) for s in scans]
-    else:
-        if not args.output:
-            raise ValueError("--output is required for a single file")
-        jobs = [(args.input, args.output)]
-    for src, _ in jobs:
-        if not os.path.isfile(src):
-            raise ValueError(f"no such file: {src}")
-    return jobs
+    return [(src, dst) for src, dst, _ in cloud_tool.jobs(args, args.ply_name, "mesh_cloud.ply")]
 
 
 def mesh_file(src: str, dst: str, args, device):
     """The mesh of one file; returns (its report entry, the device in use)."""
     import numpy as np
-    import torch
     from patchmatchnet_amd import meshops, ply, pointcloud as PC
     from patchmatchnet_amd._lib import PmnError
 
-    model = ply.read_ply_model(src)
-    if model["faces"] is not None:
-        raise PmnError(f"{src}: a mesh ({len(model['faces'])} faces), not a cloud")
-    if len(model["vertices"]) < 1:
-        raise PmnError(f"{src}: no points")
+    model = cloud_tool.load_cloud(src)
     if model["normals"] is None:
         raise PmnError(f"{src}: the cloud has no normals (nx ny nz); cloud_normals.py --input {src} --output B.ply estimates them")
-    if device is None:  # everything that can be refused without the GPU has been
-        device = torch.device(args.device)
+    device = cloud_tool.device_of(args, device)
     t0 = time.perf_counter()
-    pts = torch.from_numpy(np.ascontiguousarray(model["vertices"], np.float32)).to(device)
-    nrm = torch.from_numpy(np.ascontiguousarray(model["normals"], np.float32)).to(device)
+    pts = cloud_tool.upload(model["vertices"], np.float32, device)
+    nrm = cloud_tool.upload(model["normals"], np.float32, device)
     col = None
     if model["colors"] is not None and not args.no_color:
-        col = torch.from_numpy(np.ascontiguousarray(model["colors"], np.uint8)).to(device)
+        col = cloud_tool.upload(model["colors"], np.uint8, device)
     kw = {} if args.max_blocks is None else {"max_blocks": args.max_blocks}
     vertices, faces, colors, normals, info = PC.mesh_from_cloud(pts, nrm, col, voxel=args.voxel, radius=args.radius, trunc=args.trunc,
                                                                 k=args.k, boundary=args.boundary, min_neighbors=args.min_neighbors,
@@ -145,27 +121,15 @@ def mesh_file(src: str, dst: str, args, device):
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("mesh_cloud.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
+    if cloud_tool.refuse_torchrun(TOOL):
         return 2
     try:
         check_args(args)
         jobs = jobs_of(args)
     except ValueError as e:
-        return _fail(e)
-    from patchmatchnet_amd import _lib
-    files, device = [], None
-    try:
-        for src, dst in jobs:
-            one, device = mesh_file(src, dst, args, device)
-            files.append(one)
-    except (_lib.PmnError, ValueError) as e:
-        return _fail(e)
-    if args.report:
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as f:
-            json.dump({"abi": _lib.ABI_VERSION, "files": files}, f, indent=1)
-    return 0
+        return cloud_tool.fail(TOOL, e)
+    return cloud_tool.run(TOOL, jobs, lambda src, dst, device: mesh_file(src, dst, args, device), {}, args.report,
+                          also_catch=(ValueError,))
 
 
 if __name__ == "__main__":

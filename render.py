@@ -15,6 +15,8 @@ import os
 import sys
 import time
 
+import cloud_tool
+
 WRITES = ("depth_gt", "masks", "images", "normals")
 
 
@@ -122,8 +124,7 @@ def render_scan(args, scan, device, renderer, cache):
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("render.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
+    if cloud_tool.refuse_torchrun("render.py"):
         return 2
     from patchmatchnet_amd import PmnError
     if args.input_folder and not os.path.isdir(args.input_folder):
@@ -157,8 +158,7 @@ def main(argv=None) -> int:
     if args.scan_list:
         if not os.path.isfile(args.scan_list):
             raise PmnError("Invalid scan list file: {}".format(args.scan_list))
-        with open(args.scan_list) as f:
-            scans = [ln.strip() for ln in f if ln.strip()]
+        scans = cloud_tool.read_scan_list(args.scan_list)
     else:
         scans = [""]
     from patchmatchnet_amd import render

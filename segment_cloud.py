@@ -25,10 +25,13 @@ rest, for render.py; --labels the int32 label of EVERY input point (-1, or the p
 with field P, [k][4] float64 -- [4] with one plane, which pointcloud.load_plane and so eval_dtu.py read.
 One process on one ROCm GPU; torchrun is not supported."""
 import argparse
-import json
 import os
 import sys
 import time
+
+import cloud_tool
+
+TOOL = "segment_cloud.py"
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -64,11 +67,6 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def _fail(msg: str) -> int:
-    print("segment_cloud.py: " + " ".join(str(msg).split()), file=sys.stderr)
-    return 2
-
-
 def camera_side(plane, threshold: float, centres):
     """+1 or -1: the side of ``plane`` that holds the MAJORITY of the camera ``centres`` ([V,3] float64); a side is the sign of
     r = a x + b y + c z + d where |r| > threshold, centres inside the band count for neither.  ValueError on an even split."""
@@ -84,17 +82,12 @@ def camera_side(plane, threshold: float, centres):
 def segment_file(src: str, dst: str, cams: str, args, device):
     """Segments one file; returns (its report entry, the device in use)."""
     import numpy as np
-    import torch
-    from patchmatchnet_amd import ply, pointcloud as PC
+    from patchmatchnet_amd import pointcloud as PC
     from patchmatchnet_amd._lib import PmnError
     from cluster_cloud import cluster_colors
 
-    model = ply.read_ply_model(src)
-    if model["faces"] is not None:
-        raise PmnError(f"{src}: a mesh ({len(model['faces'])} faces), not a cloud")
+    model = cloud_tool.load_cloud(src, min_points=3, few_points_msg="a plane needs 3")
     n = len(model["vertices"])
-    if n < 3:
-        raise PmnError(f"{src}: {n} points; a plane needs 3")
     if args.normal_angle is not None and model["normals"] is None:
         raise PmnError(f"{src}: --normal_angle needs normals in the file (cloud_normals.py writes them)")
     centres = None
@@ -104,13 +97,10 @@ def segment_file(src: str, dst: str, cams: str, args, device):
             centres = camera_centres(cams)
         except FileNotFoundError as e:
             raise PmnError(f"--drop_beyond: no cameras: {e}") from e
-    if device is None:  # everything that can be refused without the GPU has been
-        device = torch.device(args.device)
+    device = cloud_tool.device_of(args, device)
     t0 = time.perf_counter()
-    pts = torch.from_numpy(np.ascontiguousarray(model["vertices"], np.float32)).to(device)
-    nrm = None
-    if args.normal_angle is not None:
-        nrm = torch.from_numpy(np.ascontiguousarray(model["normals"], np.float32)).to(device)
+    pts = cloud_tool.upload(model["vertices"], np.float32, device)
+    nrm = cloud_tool.upload(model["normals"], np.float32, device) if args.normal_angle is not None else None
     out = {"input": src, "output": dst, "points": n}
     threshold = args.threshold
     if threshold is None:
@@ -138,17 +128,12 @@ def segment_file(src: str, dst: str, cams: str, args, device):
         out["camera_side"] = side
     keep = (on_plane if args.keep == "planes" else ~on_plane) & ~dropped
     out["seconds_search"] = time.perf_counter() - t0
-    if args.color_by_plane:
-        colors = cluster_colors(labels[keep])
-    else:
-        colors = model["colors"][keep] if model["colors"] is not None else np.full((int(keep.sum()), 3), 255, np.uint8)
-    ply.write_ply(dst, model["vertices"][keep], colors, model["normals"][keep] if model["normals"] is not None else None)
+    cloud_tool.write_kept(dst, model, keep, colors=cluster_colors(labels) if args.color_by_plane else None)
     if args.labels:
-        os.makedirs(os.path.dirname(os.path.abspath(args.labels)), exist_ok=True)
-        np.save(args.labels, labels)
+        cloud_tool.save_side_file(args.labels, lambda path: np.save(path, labels))
     if args.planes:
-        os.makedirs(os.path.dirname(os.path.abspath(args.planes)), exist_ok=True)
-        np.savez(args.planes, P=res["planes"][0] if len(res["counts"]) == 1 else res["planes"])
+        planes = res["planes"][0] if len(res["counts"]) == 1 else res["planes"]
+        cloud_tool.save_side_file(args.planes, lambda path: np.savez(path, P=planes))
     out.update(threshold=float(threshold), min_inliers=int(min_inliers), dropped_beyond=int(dropped.sum()), kept=int(keep.sum()),
                planes=[{"plane": [float(v) for v in r["plane"]], "inliers": r["count"], "rmse": r["rmse"], "hypothesis": r["hypothesis"],
                         "refits": r["refits"]} for r in res["results"]])
@@ -161,68 +146,51 @@ def segment_file(src: str, dst: str, cams: str, args, device):
     return out, device
 
 
-def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("segment_cloud.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
-        return 2
+def check_args(args) -> None:
+    """ValueError for what can be refused before any file is read."""
     inf = float("inf")
     if args.threshold is not None and args.threshold_spacings is not None:
-        return _fail("--threshold and --threshold_spacings exclude each other")
+        raise ValueError("--threshold and --threshold_spacings exclude each other")
     if args.threshold is not None and not (args.threshold >= 0.0 and args.threshold < inf):
-        return _fail(f"--threshold must be finite and >= 0, got {args.threshold}")
+        raise ValueError(f"--threshold must be finite and >= 0, got {args.threshold}")
     if args.threshold_spacings is not None and not (args.threshold_spacings >= 0.0 and args.threshold_spacings < inf):
-        return _fail(f"--threshold_spacings must be finite and >= 0, got {args.threshold_spacings}")
+        raise ValueError(f"--threshold_spacings must be finite and >= 0, got {args.threshold_spacings}")
     if args.hypotheses < 1 or args.max_planes < 1:
-        return _fail(f"--hypotheses and --max_planes must be >= 1, got {args.hypotheses} and {args.max_planes}")
+        raise ValueError(f"--hypotheses and --max_planes must be >= 1, got {args.hypotheses} and {args.max_planes}")
     if args.seed < 0 or args.refine < 0:
-        return _fail(f"--seed and --refine must be >= 0, got {args.seed} and {args.refine}")
+        raise ValueError(f"--seed and --refine must be >= 0, got {args.seed} and {args.refine}")
     if args.min_inliers is not None and args.min_inlier_share is not None:
-        return _fail("--min_inliers and --min_inlier_share exclude each other")
+        raise ValueError("--min_inliers and --min_inlier_share exclude each other")
     if args.min_inliers is not None and args.min_inliers < 1:
-        return _fail(f"--min_inliers must be >= 1, got {args.min_inliers}")
+        raise ValueError(f"--min_inliers must be >= 1, got {args.min_inliers}")
     if args.min_inlier_share is not None and not (0.0 < args.min_inlier_share <= 1.0):
-        return _fail(f"--min_inlier_share must lie in (0, 1], got {args.min_inlier_share}")
+        raise ValueError(f"--min_inlier_share must lie in (0, 1], got {args.min_inlier_share}")
     if args.normal_angle is not None and not (0.0 <= args.normal_angle <= 90.0):
-        return _fail(f"--normal_angle must lie in [0, 90] degrees, got {args.normal_angle}")
+        raise ValueError(f"--normal_angle must lie in [0, 90] degrees, got {args.normal_angle}")
     if args.drop_beyond and not args.mvs_folder:
-        return _fail("--drop_beyond needs --mvs_folder, the scan folder with cams/*_cam.txt")
+        raise ValueError("--drop_beyond needs --mvs_folder, the scan folder with cams/*_cam.txt")
     if args.mvs_folder and not args.drop_beyond:
-        return _fail("--mvs_folder is read by --drop_beyond only")
-    if args.scan_list:
-        if not os.path.isdir(args.input):
-            return _fail(f"--scan_list needs --input to be a folder, got {args.input}")
-        if not os.path.isfile(args.scan_list):
-            return _fail(f"invalid scan list file: {args.scan_list}")
-        if args.labels or args.planes:
-            return _fail("--labels and --planes name one file each; they cannot be combined with --scan_list")
-        with open(args.scan_list) as f:
-            scans = [ln.strip() for ln in f if ln.strip()]
-        jobs = [(os.path.join(args.input, s, args.ply_name), os.path.join(args.output or args.input, s, "fused_noplane.ply"),
-                 os.path.join(args.mvs_folder, s) if args.mvs_folder else "") for s in scans]
-    else:
-        if not args.output:
-            return _fail("--output is required for a single file")
-        jobs = [(args.input, args.output, args.mvs_folder)]
-    for src, _, _ in jobs:
-        if not os.path.isfile(src):
-            return _fail(f"no such file: {src}")
-    from patchmatchnet_amd import _lib
-    files, device = [], None
+        raise ValueError("--mvs_folder is read by --drop_beyond only")
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    if cloud_tool.refuse_torchrun(TOOL):
+        return 2
+    one_file = "--labels and --planes name one file each; they cannot be combined with --scan_list" if args.labels or args.planes else ""
     try:
-        for src, dst, cams in jobs:
-            one, device = segment_file(src, dst, cams, args, device)
-            files.append(one)
-    except _lib.PmnError as e:
-        return _fail(e)
-    if args.report:
-        settings = {k: getattr(args, k) for k in ("threshold", "threshold_spacings", "hypotheses", "seed", "refine", "max_planes",
-                                                  "min_inliers", "min_inlier_share", "normal_angle", "keep", "drop_beyond",
-                                                  "color_by_plane")}
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as f:
-            json.dump({"abi": _lib.ABI_VERSION, **settings, "files": files}, f, indent=1)
-    return 0
+        check_args(args)
+        jobs = cloud_tool.jobs(args, args.ply_name, "fused_noplane.ply", single_only=one_file)
+    except ValueError as e:
+        return cloud_tool.fail(TOOL, e)
+    settings = {k: getattr(args, k) for k in ("threshold", "threshold_spacings", "hypotheses", "seed", "refine", "max_planes",
+                                              "min_inliers", "min_inlier_share", "normal_angle", "keep", "drop_beyond",
+                                              "color_by_plane")}
+
+    def per_file(src, dst, scan, device):
+        return segment_file(src, dst, os.path.join(args.mvs_folder, scan) if scan else args.mvs_folder, args, device)
+
+    return cloud_tool.run(TOOL, jobs, per_file, settings, args.report)
 
 
 if __name__ == "__main__":

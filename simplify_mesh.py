@@ -14,11 +14,14 @@ the most faces that does not exceed N (else the one with the fewest): it reports
 promises no more.  The output is a function of the input file and the flags alone.  One process on one ROCm GPU; torchrun is not
 supported."""
 import argparse
-import json
 import math
 import os
 import sys
 import time
+
+import cloud_tool
+
+TOOL = "simplify_mesh.py"
 
 TARGET_CALLS = 12
 
@@ -37,11 +40,6 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--report", type=str, default="", help="write the counts and settings as JSON")
     p.add_argument("--device", type=str, default="cuda:0")
     return p
-
-
-def _fail(msg: str) -> int:
-    print("simplify_mesh.py: " + " ".join(str(msg).split()), file=sys.stderr)
-    return 2
 
 
 def choose_cell(simplify, n_faces_in: int, target: int, diagonal: float):
@@ -69,24 +67,23 @@ def choose_cell(simplify, n_faces_in: int, target: int, diagonal: float):
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("simplify_mesh.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
+    if cloud_tool.refuse_torchrun(TOOL):
         return 2
     if args.cell is not None and args.target_faces is not None:
-        return _fail("give --cell or --target_faces, not both")
+        return cloud_tool.fail(TOOL, "give --cell or --target_faces, not both")
     if args.cell is not None and not (args.cell > 0.0 and math.isfinite(args.cell)):
-        return _fail(f"--cell must be positive and finite, got {args.cell}")
+        return cloud_tool.fail(TOOL, f"--cell must be positive and finite, got {args.cell}")
     if args.target_faces is not None and args.target_faces < 1:
-        return _fail(f"--target_faces must be at least 1, got {args.target_faces}")
+        return cloud_tool.fail(TOOL, f"--target_faces must be at least 1, got {args.target_faces}")
     if not (args.stiffness > 0.0 and math.isfinite(args.stiffness)):
-        return _fail(f"--stiffness must be positive and finite, got {args.stiffness}")
+        return cloud_tool.fail(TOOL, f"--stiffness must be positive and finite, got {args.stiffness}")
     if args.min_component_faces < 0 or args.keep_components < 0:
-        return _fail("--min_component_faces and --keep_components must be >= 0")
+        return cloud_tool.fail(TOOL, "--min_component_faces and --keep_components must be >= 0")
     cleaning = args.min_component_faces > 0 or args.keep_components > 0
     if args.cell is None and args.target_faces is None and not cleaning:
-        return _fail("nothing to do: give --cell, --target_faces, --min_component_faces or --keep_components")
+        return cloud_tool.fail(TOOL, "nothing to do: give --cell, --target_faces, --min_component_faces or --keep_components")
     if not os.path.isfile(args.input):
-        return _fail(f"no such file: {args.input}")
+        return cloud_tool.fail(TOOL, f"no such file: {args.input}")
     import torch
     from patchmatchnet_amd import _lib, meshops, ply
     try:
@@ -132,11 +129,9 @@ def main(argv=None) -> int:
         print(f"{args.input}: {len(v)} vertices, {len(f)} faces -> {mesh[0].shape[0]} vertices, {mesh[1].shape[0]} faces"
               + (f" at cell {report['cell']:.9g} ({args.placement})" if "cell" in report else "") + f" -> {args.output}")
     except _lib.PmnError as e:
-        return _fail(e)
+        return cloud_tool.fail(TOOL, e)
     if args.report:
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as fh:
-            json.dump(report, fh, indent=1)
+        cloud_tool.write_report(args.report, report)
     return 0
 
 

@@ -12,11 +12,14 @@ area-weighted normals of the new geometry by the right-hand rule of the faces' w
 normals unchanged, drop writes none.  --iterations 0 --normals recompute only gives a file normals.  The output is a function of the
 input file and the flags alone.  One process on one ROCm GPU; torchrun is not supported."""
 import argparse
-import json
 import math
 import os
 import sys
 import time
+
+import cloud_tool
+
+TOOL = "smooth_mesh.py"
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -35,24 +38,18 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def _fail(msg: str) -> int:
-    print("smooth_mesh.py: " + " ".join(str(msg).split()), file=sys.stderr)
-    return 2
-
-
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        print("smooth_mesh.py: single process, single GPU -- running under torchrun (WORLD_SIZE > 1) is not supported", file=sys.stderr)
+    if cloud_tool.refuse_torchrun(TOOL):
         return 2
     if args.iterations < 0:
-        return _fail(f"--iterations must be >= 0, got {args.iterations}")
+        return cloud_tool.fail(TOOL, f"--iterations must be >= 0, got {args.iterations}")
     if not (args.lam > 0.0 and args.lam <= 1.0):
-        return _fail(f"--lambda must be in (0, 1], got {args.lam}")
+        return cloud_tool.fail(TOOL, f"--lambda must be in (0, 1], got {args.lam}")
     if args.method == "taubin" and not (math.isfinite(args.mu) and args.mu < -args.lam):
-        return _fail(f"--mu must be finite and < -lambda = {-args.lam}, got {args.mu}")
+        return cloud_tool.fail(TOOL, f"--mu must be finite and < -lambda = {-args.lam}, got {args.mu}")
     if not os.path.isfile(args.input):
-        return _fail(f"no such file: {args.input}")
+        return cloud_tool.fail(TOOL, f"no such file: {args.input}")
     import torch
     from patchmatchnet_amd import _lib, meshops, ply
     try:
@@ -86,11 +83,9 @@ def main(argv=None) -> int:
               f"{args.method}, {args.iterations} iterations: displacement mean {report['displacement_mean']:.6g}, max "
               f"{report['displacement_max']:.6g}; normals {args.normals} -> {args.output}")
     except _lib.PmnError as e:
-        return _fail(e)
+        return cloud_tool.fail(TOOL, e)
     if args.report:
-        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
-        with open(args.report, "w") as fh:
-            json.dump(report, fh, indent=1)
+        cloud_tool.write_report(args.report, report)
     return 0
 
 
