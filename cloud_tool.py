@@ -76,16 +76,18 @@ def upload(array, dtype, device):
     return torch.from_numpy(np.ascontiguousarray(array, dtype)).to(device)
 
 
-def write_kept(dst: str, model, keep, colors=None, normals=None) -> None:
+def write_kept(dst: str, model, keep, colors=None, normals=None, vertices=None) -> None:
     """Writes the points of ``model`` under the mask ``keep``, unchanged and in order: white where the file had no colours, normals
-    when it had them.  ``colors`` / ``normals``, one row per point of the file, take the place of the file's."""
+    when it had them.  ``colors`` / ``normals`` / ``vertices``, one row per point of the file, take the place of the file's."""
     import numpy as np
     from patchmatchnet_amd import ply
     if colors is None:
         colors = model["colors"] if model["colors"] is not None else np.full((len(keep), 3), 255, np.uint8)
     if normals is None:
         normals = model["normals"]
-    ply.write_ply(dst, model["vertices"][keep], colors[keep], None if normals is None else normals[keep])
+    if vertices is None:
+        vertices = model["vertices"]
+    ply.write_ply(dst, vertices[keep], colors[keep], None if normals is None else normals[keep])
 
 
 def save_side_file(path: str, saver) -> None:

@@ -919,6 +919,54 @@ int pmn_cloud_sdf_blocks(const float *to_xyz, const long long *to_keys, long lon
                          const int *volume_dims_host, const float *volume_origin_host, float voxel, float trunc, int k, double radius,
                          double boundary, float *tsdf, float *weight, float *rgb, float *cweight, void *stream);
 
+/* Added under ABI 25 (purely additive: the version number did not move).  Moving least squares on a point cloud: every query is
+ * projected onto a plane (degree 1) or a quadric (degree 2) fitted to its neighbourhood, which takes the noise along the viewing rays
+ * out of a fused cloud (pointcloud.knn_mls / smooth_mls, smooth_cloud.py; tests/mls_ref.py is the numpy form; PCL's
+ * MovingLeastSquares is the filter meant, the reference has no counterpart).  The grid, query, order, n_from, k and same_cloud are
+ * pmn_knn_distance's, and so is the search with max_dist = radius.  radius and radius * radius positive and finite, degree 1 or 2,
+ * line_ratio finite and >= 0, position not NULL, else PMN_ERR_ARG.  Everything below is float64, IEEE, without contraction, from the
+ * float32 coordinates widened to float64; sums of three products are (x + y) + z.
+ *
+ * Neighbourhood: the slots of pmn_knn_distance's list that hold a point: the k nearest with d2 < R2 = radius * radius strictly, in rank
+ * order j = 0 .. c - 1 (ascending (d2, sorted index)); count = c.  Under same_cloud the query's own index is not in the list, and the
+ * query is a MEMBER of the fit: the delta 0 with weight 1, before rank 0.  Otherwise the query is a position and no member.  m = the
+ * number of members, c + 1 or c.
+ * Weights: u = 1 - d2_j / R2, u2 = u * u, w_j = u2 * u2 (pmn_cloud_sdf_blocks' weight; no exponential: the host model is exact).
+ * Moments: d_j = p_j - q per axis.  W starts at 1 under same_cloud (the query's weight; its delta adds nothing to the other sums) and at
+ * 0 otherwise; the other nine sums start at 0.  Per neighbour in rank order, with wd_a = w_j * d_ja:  W += w_j;  s_a += wd_a;
+ * M_ab += wd_a * d_jb for ab = xx xy xz yy yz zz.  Centroid c_a = s_a / W.  Covariance A_ab = M_ab - (s_a * s_b) / W.
+ * Frame: pmn_knn_normals' eigen-solver on A, unchanged: V = I, PMN_NORMAL_SWEEPS sweeps over (0, 1), (0, 2), (1, 2), a pair with
+ * A_pq == 0 skipped, the ascending sort with equal values in column order.  (l0, n), (l1, e1), (l2, e2) are the eigenpairs; each of the
+ * three vectors gets the canonical sign: its component of largest magnitude positive, the lowest axis among equal magnitudes.
+ * Validity: m >= 3 and W > 0 and l2 != 0 and l1 > line_ratio * l2.  Otherwise status = 0, position = the query's float32 coordinates
+ * as they are, normal = 0 0 0, displacement = 0.
+ * Plane step (both degrees): t = (n.x * c.x + n.y * c.y) + n.z * c.z;  x0 = t * n per axis;  delta = x0, normal = n, status = 1.
+ * Quadric step, only for degree == 2 and m >= PMN_MLS_QUADRIC_MIN: per member in the same order (the query first under same_cloud, with
+ * r = 0 - x0 and w = 1), r = d_j - x0 per axis,  a = ((e1.x * r.x + e1.y * r.y) + e1.z * r.z) / radius,  b likewise with e2,
+ * h = (n.x * r.x + n.y * r.y) + n.z * r.z,  phi = (1, a, b, a * a, a * b, b * b).  With wp_0 = w and wp_j = w * phi_j for j > 0:
+ * g_j += wp_j * h, and G_ij += wp_j * phi_i for j <= i (21 sums, all started at 0).
+ * Cholesky G = L L^T by columns j = 0 .. 5:  v = G_jj, then v = v - L_jk * L_jk for k = 0 .. j - 1;  the pivot v must be
+ * > PMN_MLS_PIVOT_MIN * W;  L_jj = sqrt(v);  for i = j + 1 .. 5:  u = G_ij, then u = u - L_ik * L_jk for k = 0 .. j - 1;  L_ij = u / L_jj.
+ * Forward, i = 0 .. 5:  v = g_i, then v = v - L_ik * y_k for k = 0 .. i - 1;  y_i = v / L_ii.  Back, i = 5 .. 0:  v = y_i, then
+ * v = v - L_ki * c_k for k = i + 1 .. 5;  c_i = v / L_ii.
+ * delta = x0 + c_0 * n per axis.  The step is taken when every pivot passed and (delta.x * delta.x + delta.y * delta.y) + delta.z *
+ * delta.z <= R2; then status = 2 and the normal is u = (n - (c_1 / radius) * e1) - (c_2 / radius) * e2 per axis, divided by
+ * sqrt((u.x * u.x + u.y * u.y) + u.z * u.z) (u . n = 1 before the division: the side of n is kept).  Otherwise the plane step stands:
+ * status = 1.  (The plane step cannot leave the radius: |t| <= |c| < radius.)
+ * Outputs, indexed as query, for status > 0: position_a = (float)(q_a + delta_a); normal_a = (float) of the component; displacement =
+ * sqrt((delta.x * delta.x + delta.y * delta.y) + delta.z * delta.z).  position [n_from][3] float32; normal [n_from][3] float32 or NULL;
+ * displacement [n_from] float64 or NULL; status [n_from] int32 or NULL; count [n_from] int32 or NULL.
+ * PMN_MLS_PIVOT_MIN is a SETTING, not a measured optimum: with a and b scaled by 1 / radius the entries of G are of the order of W, a
+ * pivot below 1e-10 W leaves fewer than six of float64's digits in the coefficients, and a fit that loose is not worth taking.
+ * One launch of ceil(n_from / 64) one-wave workgroups, one lane per query, kernels specialised on the list's capacity (8, 16, 32) and
+ * on the degree; the quadric's sums are a second pass over the list; no LDS, no atomics, the lists are never written. */
+#define PMN_MLS_QUADRIC_MIN 6
+#define PMN_MLS_PIVOT_MIN 1e-10
+int pmn_knn_mls(const float *to_xyz, const long long *to_keys, long long n_to, const double *origin_host, double cell,
+                const int *dims_host, const float *query, const int *order, long long n_from, int k, double radius, int same_cloud,
+                int degree, double line_ratio, float *position, float *normal, double *displacement, int *status, int *count,
+                void *stream);
+
 /* Added under ABI 25 (purely additive: the version number did not move).  The exact distance from points to a triangle mesh
  * (patchmatchnet_amd/meshops.py build_face_grid / point_mesh_distance; tests/mesh_distance_ref.py is the numpy
  * form; the reference has no counterpart).  vertices, faces, n_vertices, n_faces and invalid as in the mesh entry points above: a face

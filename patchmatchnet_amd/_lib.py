@@ -39,6 +39,8 @@ PLANE_MAX_HYPOTHESES = 4096
 PLANE_SUMS = 10
 PLANE_LIMBS = 5
 PLANE_BLOCK_POINTS = 1024
+MLS_QUADRIC_MIN = 6
+MLS_PIVOT_MIN = 1e-10
 
 _fp = ctypes.c_void_p  # device float* (passed as integer address)
 _ip = ctypes.c_void_p
@@ -132,6 +134,8 @@ SIGNATURES = {
                           _fp, _s],
     "pmn_cloud_sdf_blocks": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, _ip, _i, _hp, _hp, _f, _f, _i,
                              ctypes.c_double, ctypes.c_double, _fp, _fp, _fp, _fp, _s],
+    "pmn_knn_mls": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _fp, _ip, ctypes.c_longlong, _i, ctypes.c_double, _i, _i,
+                    ctypes.c_double, _fp, _fp, _fp, _ip, _ip, _s],
     "pmn_mesh_distance": [_fp, _ip, ctypes.c_longlong, _hp, ctypes.c_double, _hp, _ip, ctypes.c_double, _fp, _i, _ip, _i, _fp, _ip,
                           ctypes.c_longlong, ctypes.c_double, _fp, _ip, _fp, _ip, _s],
     "pmn_mesh_remap_faces": [_ip, _i, _i, _ip, _i, _ip, _ip, _ip, _ip, _s],

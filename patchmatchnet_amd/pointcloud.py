@@ -11,7 +11,8 @@ The same grid serves cloud cleaning (clean_cloud.py): pmn_knn_dist
 neighbours and the number of points within a radius, and statistical_outliers / radius_outliers the two filters built on them.
 cluster_dbscan (cluster_cloud.py) takes a cloud apart into its dense pieces over the same grid: pmn_cloud_core and
 pmn_cloud_dbscan (csrc/cloud_cluster.hip).  segment_plane / segment_planes (segment_cloud.py) find the dominant planes
-by seeded RANSAC: pmn_plane_score and pmn_plane_inliers (csrc/cloud_plane.hip) need no grid.
+by seeded RANSAC: pmn_plane_score and pmn_plane_inliers (csrc/cloud_plane.hip) need no grid.  knn_mls / smooth_mls (smooth_cloud.py,
+DESIGN.md 36) move every point onto a surface fitted to its neighbourhood, moving least squares: pmn_knn_mls (csrc/cloud_mls.hip).
 
 Semantics: every distance is sqrt(dx*dx + dy*dy + dz*dz) of the float32 PLY coordinates widened to float64; the visiting
 order of the reduction is an explicit, seeded permutation (the MATLAB draws an unseeded randperm), and for a given order the result is
@@ -741,6 +742,84 @@ def estimate_normals(points: torch.Tensor, k: int = 16, max_dist: Optional[float
         normal = torch.where(against[:, None], -normal, normal)
         out = (normal,) + out[1:] if isinstance(out, tuple) else normal
     return out
+
+
+# ---- moving least squares ------------------------------------------------------------------------------------------------
+# A SETTING, not a measurement: three spacings hold about 28 neighbours of a point of a regularly sampled surface (pi * 3^2), the k
+# the tool defaults to; no sweep stands behind the figure.  It is an argument of smooth_mls and a flag of smooth_cloud.py.
+MLS_RADIUS_SPACINGS = 3.0   # default radius of smooth_mls = this times cloud_spacing
+
+
+def knn_mls(query: Optional[torch.Tensor], grid: Grid, k: int, radius: float, same_cloud: bool = False, degree: int = 2,
+            line_ratio: float = 1e-6, return_normal: bool = False, return_displacement: bool = False, return_status: bool = False,
+            return_count: bool = False):
+    """pmn_knn_mls: float32 [n,3], every query point projected onto the surface fitted to its ``k`` (1..32) nearest points of ``grid``
+    nearer than ``radius`` (knn_distance's search), weighted by (1 - d2 / radius^2)^4: the plane through the weighted centroid along
+    the two directions of largest variance (``degree`` 1), or the quadric over that plane (``degree`` 2, from 6 members on; it falls
+    back to the plane when its normal equations are too ill-conditioned or when it would move the point beyond ``radius``), float64 on
+    the device (include/pmn_hip.h states every operation).  A point with fewer than three members, or whose neighbourhood lies on a
+    line (second eigenvalue <= ``line_ratio`` times the largest), stays where it is.  ``return_normal``: also float32 [n,3], the fitted
+    surface's unit normal at the projection, its largest component positive (0 0 0 where the point stayed); ``return_displacement``:
+    also float64 [n], how far the point moved; ``return_status``: also int32 [n], 0 not fitted, 1 plane, 2 quadric; ``return_count``:
+    also int32 [n], the neighbours in range.  ``same_cloud``: as knn_distance; the point itself then joins the fit with weight 1."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
+        raise PmnError(f"knn_mls: k must be an integer in 1..32, got {k!r}")
+    square = float(radius) * float(radius)  # (** raises OverflowError where the product is infinite)
+    if not (radius > 0.0 and np.isfinite(radius) and np.isfinite(square) and square > 0.0):
+        raise PmnError(f"knn_mls: radius and its square must be positive and finite, got {radius}")
+    if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)) or int(degree) not in (1, 2):
+        raise PmnError(f"knn_mls: degree must be 1 or 2, got {degree!r}")
+    if not (line_ratio >= 0.0 and np.isfinite(line_ratio)):
+        raise PmnError(f"knn_mls: line_ratio must be finite and >= 0, got {line_ratio}")
+    query, order = _search_query("knn_mls", query, grid, same_cloud)
+    n, k, dev = int(query.shape[0]), int(k), query.device
+    position = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    normal = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_normal else None
+    displacement = torch.empty(n, dtype=torch.float64, device=dev) if return_displacement else None
+    status = torch.empty(n, dtype=torch.int32, device=dev) if return_status else None
+    count = torch.empty(n, dtype=torch.int32, device=dev) if return_count else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().pmn_knn_mls(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n, k,
+                                     float(radius), int(bool(same_cloud)), int(degree), float(line_ratio), position.data_ptr(),
+                                     *(t.data_ptr() if t is not None else None for t in (normal, displacement, status, count)),
+                                     _stream(query)), "pmn_knn_mls")
+    out = [_unsort(t, grid, same_cloud) for t in (position, normal, displacement, status, count) if t is not None]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def smooth_mls(points: torch.Tensor, radius: Optional[float] = None, k: int = 32, degree: int = 2, iterations: int = 1,
+               cell: Optional[float] = None, return_normals: bool = False, radius_spacings: float = MLS_RADIUS_SPACINGS):
+    """Moving-least-squares smoothing of a cloud by its own neighbourhoods (PCL MovingLeastSquares without upsampling): (positions
+    float32 [n,3] in the order of ``points``, report dict), with ``return_normals`` (positions, normals float32 [n,3], report).
+    Every iteration builds the cleaning grid (default_cell, or ``cell``) from the current positions and calls knn_mls with
+    same_cloud; ``radius`` defaults to ``radius_spacings`` (MLS_RADIUS_SPACINGS) times cloud_spacing(points) of the INPUT and is
+    the same in every iteration.  The number and the order of the points never change; a point that could not be fitted stays where it was.  report:
+    radius, spacing (None when the radius was given and the cloud has none), k, degree, iterations, status = the points that were
+    [not fitted, projected onto a plane, projected onto a quadric] in the last iteration, and mean_displacement / max_displacement
+    from the input position to the final one, in scene units and (``_spacings``) in units of the spacing."""
+    points = _points(points, "points")
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 1:
+        raise PmnError(f"smooth_mls: iterations must be an integer >= 1, got {iterations!r}")
+    if cell is not None and not (float(cell) > 0.0 and np.isfinite(float(cell))):
+        raise PmnError(f"smooth_mls: cell must be positive and finite, got {cell}")
+    if not (float(radius_spacings) > 0.0 and np.isfinite(float(radius_spacings))):
+        raise PmnError(f"smooth_mls: radius_spacings must be positive and finite, got {radius_spacings}")
+    spacing = cloud_spacing(points) if int(points.shape[0]) > 1 else 0.0
+    if radius is None:
+        radius = float(radius_spacings) * spacing
+        if not (radius > 0.0 and np.isfinite(radius)):
+            raise PmnError(f"smooth_mls: the cloud's spacing is {spacing}; give radius")
+    current, normal, status = points, None, None
+    for _ in range(int(iterations)):
+        grid = _clean_grid(current, cell)
+        current, normal, status = knn_mls(None, grid, k, radius, same_cloud=True, degree=degree, return_normal=True, return_status=True)
+    moved = (current.double() - points.double()).norm(dim=1)
+    mean, largest = float(moved.mean()), float(moved.max())
+    unit = spacing if spacing > 0.0 and np.isfinite(spacing) else None
+    report = {"radius": float(radius), "spacing": unit, "k": int(k), "degree": int(degree), "iterations": int(iterations),
+              "status": torch.bincount(status.long(), minlength=3).cpu().tolist(), "mean_displacement": mean, "max_displacement": largest,
+              "mean_displacement_spacings": mean / unit if unit else None, "max_displacement_spacings": largest / unit if unit else None}
+    return (current, normal, report) if return_normals else (current, report)
 
 
 # ---- a surface from an oriented cloud (DESIGN.md 32) -------------------------------------------------------------------------------
