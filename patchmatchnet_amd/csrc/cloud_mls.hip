@@ -18,11 +18,8 @@
 
 struct MlsArgs {
     GridArgs g;
-    const float* query;  // [n_from][3]
-    const int* order;    // [n_from] or null (identity)
-    int n_from;
+    QueryArgs q;
     int k;
-    int same_cloud;
     double radius;
     double line_ratio;
     float* position;       // [n_from][3]
@@ -31,16 +28,6 @@ struct MlsArgs {
     int* status;           // [n_from] or null
     int* count;            // [n_from] or null
 };
-
-// canonical sign of a vector: the component of largest magnitude positive, the lowest axis among equals (pmn_knn_normals' rule)
-__device__ __forceinline__ void mls_canonical(double& x, double& y, double& z) {
-    const double ax = fabs(x), ay = fabs(y), az = fabs(z);
-    const double lead = (ax >= ay && ax >= az) ? x : (ay >= az ? y : z);
-    const bool flip = lead < 0.0;
-    x = flip ? -x : x;
-    y = flip ? -y : y;
-    z = flip ? -z : z;
-}
 
 // entry (i, j), j <= i, of a symmetric or lower-triangular 6 x 6 matrix stored by rows
 __device__ __forceinline__ constexpr int mls_at(int i, int j) { return i * (i + 1) / 2 + j; }
@@ -109,57 +96,25 @@ struct MlsQuadric {
 
 template <int CAP, int DEGREE>
 __global__ __launch_bounds__(64) void knn_mls_kernel(MlsArgs a) {
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.n_from) return;
-    const int q = a.order ? a.order[t] : t;
-    const float qfx = a.query[(size_t)q * 3], qfy = a.query[(size_t)q * 3 + 1], qfz = a.query[(size_t)q * 3 + 2];
-    const double qx = (double)qfx, qy = (double)qfy, qz = (double)qfz;
+    PC_QUERY_OR_RETURN(a.q);
     const double R2 = a.radius * a.radius;
     KBest<CAP> b;
-    b.init(a.k, R2, a.same_cloud ? q : -1);
+    b.init(a.k, R2, self);
     pc_walk(a.g, qx, qy, qz, b);
     // the weighted moments of the deltas, members in rank order; under same_cloud the query comes first: the zero delta, weight 1
-    double W = a.same_cloud ? 1.0 : 0.0;
-    double sx = 0.0, sy = 0.0, sz = 0.0, mxx = 0.0, mxy = 0.0, mxz = 0.0, myy = 0.0, myz = 0.0, mzz = 0.0;
-    int used = 0;
-#pragma unroll
-    for (int s = 0; s < CAP; ++s) {  // static register; a sentinel (-2) or capped (-1) slot is no neighbour
-        const int i = b.idx[s];
-        if (i < 0) continue;
-        const float* p = a.g.xyz + (size_t)i * 3;
-        const double dx = (double)p[0] - qx, dy = (double)p[1] - qy, dz = (double)p[2] - qz;
-        const double u = 1.0 - b.d2[s] / R2, u2 = u * u, w = u2 * u2;
-        const double wx = w * dx, wy = w * dy, wz = w * dz;
-        W += w;
-        sx += wx;
-        sy += wy;
-        sz += wz;
-        mxx += wx * dx;
-        mxy += wx * dy;
-        mxz += wx * dz;
-        myy += wy * dy;
-        myz += wy * dz;
-        mzz += wz * dz;
-        ++used;
-    }
-    const int m = used + (a.same_cloud ? 1 : 0);
+    double W = a.q.same_cloud ? 1.0 : 0.0, sx, sy, sz, mxx, mxy, mxz, myy, myz, mzz;
+    const int used = pc_moments<true>(b, a.g.xyz, qx, qy, qz, R2, W, sx, sy, sz, mxx, mxy, mxz, myy, myz, mzz);
+    const int m = used + (a.q.same_cloud ? 1 : 0);
     const double cx = sx / W, cy = sy / W, cz = sz / W;
     double a00 = mxx - (sx * sx) / W, a01 = mxy - (sx * sy) / W, a02 = mxz - (sx * sz) / W;
     double a11 = myy - (sy * sy) / W, a12 = myz - (sy * sz) / W, a22 = mzz - (sz * sz) / W;
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;  // v[row][column]
-    for (int sweep = 0; sweep < PMN_NORMAL_SWEEPS; ++sweep) {
-        pc_jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0, 1)
-        pc_jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0, 2)
-        pc_jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1, 2)
-    }
-    pc_eigen_order(a00, v00, v10, v20, a11, v01, v11, v21);
-    pc_eigen_order(a11, v01, v11, v21, a22, v02, v12, v22);
-    pc_eigen_order(a00, v00, v10, v20, a11, v01, v11, v21);
+    double v00, v01, v02, v10, v11, v12, v20, v21, v22;  // v[row][column]
+    pc_eigen3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
     const double l1 = a11, l2 = a22;
     double nx = v00, ny = v10, nz = v20, e1x = v01, e1y = v11, e1z = v21, e2x = v02, e2y = v12, e2z = v22;
-    mls_canonical(nx, ny, nz);
-    mls_canonical(e1x, e1y, e1z);
-    mls_canonical(e2x, e2y, e2z);
+    pc_flip(pc_canonical_flip(nx, ny, nz), nx, ny, nz);  // pmn_knn_normals' sign rule, for every axis of the frame
+    pc_flip(pc_canonical_flip(e1x, e1y, e1z), e1x, e1y, e1z);
+    pc_flip(pc_canonical_flip(e2x, e2y, e2z), e2x, e2y, e2z);
     const bool valid = m >= 3 && W > 0.0 && l2 != 0.0 && l1 > a.line_ratio * l2;
     // the plane step
     const double tn = (nx * cx + ny * cy) + nz * cz;
@@ -169,7 +124,7 @@ __global__ __launch_bounds__(64) void knn_mls_kernel(MlsArgs a) {
     if (DEGREE == 2 && valid && m >= PMN_MLS_QUADRIC_MIN) {
         MlsQuadric f;
         f.init();
-        if (a.same_cloud) f.add(1.0, 0.0 - x0x, 0.0 - x0y, 0.0 - x0z, nx, ny, nz, e1x, e1y, e1z, e2x, e2y, e2z, a.radius);
+        if (a.q.same_cloud) f.add(1.0, 0.0 - x0x, 0.0 - x0y, 0.0 - x0z, nx, ny, nz, e1x, e1y, e1z, e2x, e2y, e2z, a.radius);
 #pragma unroll
         for (int s = 0; s < CAP; ++s) {
             const int i = b.idx[s];
@@ -196,7 +151,8 @@ __global__ __launch_bounds__(64) void knn_mls_kernel(MlsArgs a) {
             status = 2;
         }
     }
-    float px = qfx, py = qfy, pz = qfz, fnx = 0.0f, fny = 0.0f, fnz = 0.0f;
+    const float* qf = a.q.query + (size_t)q * 3;  // a point that stays keeps its float32 bits
+    float px = qf[0], py = qf[1], pz = qf[2], fnx = 0.0f, fny = 0.0f, fnz = 0.0f;
     double disp = 0.0;
     if (status > 0) {
         px = (float)(qx + mvx);
@@ -222,10 +178,7 @@ __global__ __launch_bounds__(64) void knn_mls_kernel(MlsArgs a) {
 
 template <int DEGREE>
 static void mls_launch(const MlsArgs& a, hipStream_t stream) {
-    const dim3 grid((unsigned)((a.n_from + 63) / 64));
-    if (a.k <= 8) PMN_LAUNCH((knn_mls_kernel<8, DEGREE>), grid, dim3(64), 0, stream, a);
-    else if (a.k <= 16) PMN_LAUNCH((knn_mls_kernel<16, DEGREE>), grid, dim3(64), 0, stream, a);
-    else PMN_LAUNCH((knn_mls_kernel<32, DEGREE>), grid, dim3(64), 0, stream, a);
+    PMN_LAUNCH_KBEST(a.k, (knn_mls_kernel<CAP, DEGREE>), dim3((unsigned)((a.q.n_from + 63) / 64)), dim3(64), 0, stream, a);
 }
 
 extern "C" int pmn_knn_mls(const float* to_xyz, const long long* to_keys, long long n_to, const double* origin_host, double cell,
@@ -235,16 +188,11 @@ extern "C" int pmn_knn_mls(const float* to_xyz, const long long* to_keys, long l
     MlsArgs a;
     const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
     if (rc != PMN_OK) return rc;
-    if (!query || !position || n_from < 1 || n_from >= (1LL << 31) - 64 || k < 1 || k > 32) return PMN_ERR_ARG;
-    if (!(radius > 0.0) || !std::isfinite(radius) || !std::isfinite(radius * radius) || !(radius * radius > 0.0)) return PMN_ERR_ARG;
-    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
+    if (query_args(a.q, query, order, n_from, same_cloud, n_to) != PMN_OK) return PMN_ERR_ARG;
+    if (!position || !pc_k_ok(k) || !pc_reach_square_ok(radius)) return PMN_ERR_ARG;
     if (degree != 1 && degree != 2) return PMN_ERR_ARG;
     if (!(line_ratio >= 0.0) || !std::isfinite(line_ratio)) return PMN_ERR_ARG;
-    a.query = query;
-    a.order = order;
-    a.n_from = (int)n_from;
     a.k = k;
-    a.same_cloud = same_cloud ? 1 : 0;
     a.radius = radius;
     a.line_ratio = line_ratio;
     a.position = position;

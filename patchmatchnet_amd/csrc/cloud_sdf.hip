@@ -107,11 +107,10 @@ extern "C" int pmn_cloud_sdf_blocks(const float* to_xyz, const long long* to_key
     CloudSdfArgs a;
     const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
     if (rc != PMN_OK) return rc;
-    if (!normals || !blocks || !volume_dims_host || !volume_origin_host || !tsdf || !weight || k < 1 || k > 32) return PMN_ERR_ARG;
+    if (!normals || !blocks || !volume_dims_host || !volume_origin_host || !tsdf || !weight || !pc_k_ok(k)) return PMN_ERR_ARG;
     if ((rgb == nullptr) != (cweight == nullptr) || (colors == nullptr) != (rgb == nullptr)) return PMN_ERR_ARG;
     if (!(voxel > 0.0f) || !std::isfinite(voxel) || !(trunc > 0.0f) || !std::isfinite(trunc)) return PMN_ERR_ARG;
-    if (!(radius > 0.0) || !std::isfinite(radius) || !std::isfinite(radius * radius) || !(radius * radius > 0.0)) return PMN_ERR_ARG;
-    if (!(boundary > 0.0) || !std::isfinite(boundary) || !std::isfinite(boundary * boundary)) return PMN_ERR_ARG;
+    if (!pc_reach_square_ok(radius) || !pc_reach_ok(boundary)) return PMN_ERR_ARG;
     for (int c = 0; c < 3; ++c)
         if (!std::isfinite(volume_origin_host[c])) return PMN_ERR_ARG;
     // the virtual lattice and the pool, with tsdf.hip's limits
@@ -141,9 +140,7 @@ extern "C" int pmn_cloud_sdf_blocks(const float* to_xyz, const long long* to_key
     a.rgb = rgb;
     a.cweight = cweight;
     const dim3 grid((unsigned)n_blocks * SDF_SB);  // < 2^25
-    if (k <= 8) PMN_LAUNCH(cloud_sdf_blocks_kernel<8>, grid, dim3(64), 0, (hipStream_t)stream, a);
-    else if (k <= 16) PMN_LAUNCH(cloud_sdf_blocks_kernel<16>, grid, dim3(64), 0, (hipStream_t)stream, a);
-    else PMN_LAUNCH(cloud_sdf_blocks_kernel<32>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    PMN_LAUNCH_KBEST(k, cloud_sdf_blocks_kernel<CAP>, grid, dim3(64), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }

@@ -198,6 +198,57 @@ struct RadiusCount {
     __device__ __forceinline__ void offer(double c, int i) { count += (i != self && sqrt(c) <= radius) ? 1 : 0; }
 };
 
+// ---- what every query search repeats around the walk ---------------------------------------------------------------------------------
+// One lane per query, 64-lane workgroups, queries taken in the caller's order.
+struct QueryArgs {
+    const float* query;  // [n_from][3]
+    const int* order;    // [n_from] or null (identity)
+    int n_from;
+    int same_cloud;      // query i IS grid point i
+};
+
+// The prologue of a query kernel `(XArgs a)` with a QueryArgs a.q: lanes past the end return; the others get q (the row of the query
+// and of every output), its coordinates widened, and self, the sorted index a search must not report (q itself under same_cloud,
+// else -1).  A macro and not a function: with the bound inside a function the compiler lays the kernels out around a second branch,
+// and the plain searches were measurably slower for it.
+#define PC_QUERY_OR_RETURN(qa)                                                                                                  \
+    const int t_ = blockIdx.x * 64 + threadIdx.x;                                                                               \
+    if (t_ >= (qa).n_from) return;                                                                                              \
+    const int q = (qa).order ? (qa).order[t_] : t_;                                                                             \
+    const double qx = (double)(qa).query[(size_t)q * 3], qy = (double)(qa).query[(size_t)q * 3 + 1],                            \
+                 qz = (double)(qa).query[(size_t)q * 3 + 2];                                                                    \
+    [[maybe_unused]] const int self = (qa).same_cloud ? q : -1
+
+static inline int query_args(QueryArgs& a, const float* query, const int* order, long long n_from, int same_cloud, long long n_to) {
+    if (!query || n_from < 1 || n_from >= (1LL << 31) - 64) return PMN_ERR_ARG;
+    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
+    a.query = query;
+    a.order = order;
+    a.n_from = (int)n_from;
+    a.same_cloud = same_cloud ? 1 : 0;
+    return PMN_OK;
+}
+
+// the two checks of a reach (max_dist, radius, boundary) that caps a KBest list: its square is the cap and, where a kernel divides
+// by it (the weight 1 - d2 / R2), must not have underflowed to 0
+static inline bool pc_reach_ok(double r) { return r > 0.0 && std::isfinite(r) && std::isfinite(r * r); }
+static inline bool pc_reach_square_ok(double r) { return pc_reach_ok(r) && r * r > 0.0; }
+
+// PMN_LAUNCH of a kernel specialised on the capacity of its KBest list, for k in 1..32 (pc_k_ok): `kernel` is written with CAP where
+// the capacity goes, as in PMN_LAUNCH_KBEST(k, knn_distance_kernel<CAP>, grid, ...) or (knn_mls_kernel<CAP, DEGREE>) in parentheses.
+static inline bool pc_k_ok(int k) { return k >= 1 && k <= 32; }
+#define PMN_LAUNCH_CAP(cap, kernel, ...) \
+    {                                    \
+        constexpr int CAP = cap;         \
+        PMN_LAUNCH(kernel, __VA_ARGS__); \
+    }
+#define PMN_LAUNCH_KBEST(k, kernel, ...)                                \
+    do {                                                                \
+        if ((k) <= 8) PMN_LAUNCH_CAP(8, kernel, __VA_ARGS__)            \
+        else if ((k) <= 16) PMN_LAUNCH_CAP(16, kernel, __VA_ARGS__)     \
+        else PMN_LAUNCH_CAP(32, kernel, __VA_ARGS__)                    \
+    } while (0)
+
 static inline int grid_args(GridArgs& g, const float* xyz, const long long* keys, long long n, const double* origin_host, double cell,
                             const int* dims_host) {
     if (!xyz || !keys || !origin_host || !dims_host || n < 1 || n >= (1LL << 31)) return PMN_ERR_ARG;

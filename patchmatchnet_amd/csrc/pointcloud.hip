@@ -27,9 +27,7 @@
 // neighbours, not 255, and the hardware schedules the many short waves around it.
 struct NnArgs {
     GridArgs g;
-    const float* query;  // [n_from][3]
-    const int* order;    // [n_from] or null (identity)
-    int n_from;
+    QueryArgs q;         // same_cloud is 0: the nearest point may be the query's twin
     double max_dist;
     double* dist;        // [n_from], indexed as query
     int* index;          // [n_from] or null
@@ -37,10 +35,7 @@ struct NnArgs {
 
 __global__ __launch_bounds__(64) void nn_distance_kernel(NnArgs a) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.n_from) return;
-    const int q = a.order ? a.order[t] : t;
-    const double qx = (double)a.query[(size_t)q * 3], qy = (double)a.query[(size_t)q * 3 + 1], qz = (double)a.query[(size_t)q * 3 + 2];
+    PC_QUERY_OR_RETURN(a.q);
     const NnBest b = nn_search(a.g, qx, qy, qz, a.max_dist);  // pc_grid.hpp: the shell walk, shared with registration.hip
     a.dist[q] = b.idx < 0 ? a.max_dist : sqrt(b.d2);
     if (a.index) a.index[q] = b.idx;
@@ -113,11 +108,8 @@ __global__ __launch_bounds__(256) void reduce_round_kernel(ReduceArgs a) {
 // specialised on its capacity (8 / 16 / 32, k rounded up): 3 VGPRs per slot, and a small k does not pay for 32 slots.
 struct KnnArgs {
     GridArgs g;
-    const float* query;  // [n_from][3]
-    const int* order;    // [n_from] or null (identity)
-    int n_from;
+    QueryArgs q;
     int k;
-    int same_cloud;      // query i IS grid point i
     double max_dist;
     double* d2;          // [n_from][k] or null
     int* index;          // [n_from][k] or null
@@ -127,12 +119,9 @@ struct KnnArgs {
 template <int CAP>
 __global__ __launch_bounds__(64) void knn_distance_kernel(KnnArgs a) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.n_from) return;
-    const int q = a.order ? a.order[t] : t;
-    const double qx = (double)a.query[(size_t)q * 3], qy = (double)a.query[(size_t)q * 3 + 1], qz = (double)a.query[(size_t)q * 3 + 2];
+    PC_QUERY_OR_RETURN(a.q);
     KBest<CAP> b;
-    b.init(a.k, a.max_dist * a.max_dist, a.same_cloud ? q : -1);
+    b.init(a.k, a.max_dist * a.max_dist, self);
     pc_walk(a.g, qx, qy, qz, b);
     const size_t row = (size_t)q * a.k;
     double sum = 0.0;
@@ -149,22 +138,16 @@ __global__ __launch_bounds__(64) void knn_distance_kernel(KnnArgs a) {
 
 struct RadiusArgs {
     GridArgs g;
-    const float* query;
-    const int* order;
-    int n_from;
-    int same_cloud;
+    QueryArgs q;
     double radius;
     int* count;  // [n_from]
 };
 
 __global__ __launch_bounds__(64) void radius_count_kernel(RadiusArgs a) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.n_from) return;
-    const int q = a.order ? a.order[t] : t;
-    const double qx = (double)a.query[(size_t)q * 3], qy = (double)a.query[(size_t)q * 3 + 1], qz = (double)a.query[(size_t)q * 3 + 2];
+    PC_QUERY_OR_RETURN(a.q);
     RadiusCount b;
-    b.init(a.radius, a.same_cloud ? q : -1);
+    b.init(a.radius, self);
     pc_walk(a.g, qx, qy, qz, b);
     a.count[q] = b.count;
 }
@@ -177,11 +160,8 @@ __global__ __launch_bounds__(64) void radius_count_kernel(RadiusArgs a) {
 
 struct NormalArgs {
     GridArgs g;
-    const float* query;  // [n_from][3]
-    const int* order;    // [n_from] or null (identity)
-    int n_from;
+    QueryArgs q;
     int k;
-    int same_cloud;
     double max_dist;
     const double* viewpoints;  // [n_viewpoints][3] or null
     int n_viewpoints;
@@ -191,51 +171,23 @@ struct NormalArgs {
     int* count;          // [n_from] or null
 };
 
-// pc_jacobi_rotate and pc_eigen_order: pc_jacobi.hpp, shared with cloud_mls.hip
+// pc_moments, pc_eigen3 and the canonical sign: pc_jacobi.hpp, shared with cloud_mls.hip
 
 template <int CAP>
 __global__ __launch_bounds__(64) void knn_normals_kernel(NormalArgs a) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.n_from) return;
-    const int q = a.order ? a.order[t] : t;
-    const double qx = (double)a.query[(size_t)q * 3], qy = (double)a.query[(size_t)q * 3 + 1], qz = (double)a.query[(size_t)q * 3 + 2];
+    PC_QUERY_OR_RETURN(a.q);
     KBest<CAP> b;
-    b.init(a.k, a.max_dist * a.max_dist, a.same_cloud ? q : -1);
+    b.init(a.k, a.max_dist * a.max_dist, self);
     pc_walk(a.g, qx, qy, qz, b);
-    // the moments of the deltas, neighbours in rank order (ascending slot); the query is the zero delta and counts in m alone
-    double sx = 0.0, sy = 0.0, sz = 0.0, mxx = 0.0, mxy = 0.0, mxz = 0.0, myy = 0.0, myz = 0.0, mzz = 0.0;
-    int used = 0;
-#pragma unroll
-    for (int s = 0; s < CAP; ++s) {  // static register; a sentinel (-2) or capped (-1) slot is no neighbour
-        const int i = b.idx[s];
-        if (i < 0) continue;
-        const float* p = a.g.xyz + (size_t)i * 3;
-        const double dx = (double)p[0] - qx, dy = (double)p[1] - qy, dz = (double)p[2] - qz;
-        sx += dx;
-        sy += dy;
-        sz += dz;
-        mxx += dx * dx;
-        mxy += dx * dy;
-        mxz += dx * dz;
-        myy += dy * dy;
-        myz += dy * dz;
-        mzz += dz * dz;
-        ++used;
-    }
+    // the moments of the deltas, neighbours in rank order; the query is the zero delta and counts in m alone
+    double W = 0.0, sx, sy, sz, mxx, mxy, mxz, myy, myz, mzz;
+    const int used = pc_moments<false>(b, a.g.xyz, qx, qy, qz, 0.0, W, sx, sy, sz, mxx, mxy, mxz, myy, myz, mzz);
     const double m = (double)(used + 1);
     double a00 = mxx - (sx * sx) / m, a01 = mxy - (sx * sy) / m, a02 = mxz - (sx * sz) / m;
     double a11 = myy - (sy * sy) / m, a12 = myz - (sy * sz) / m, a22 = mzz - (sz * sz) / m;
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;  // v[row][column]
-    for (int sweep = 0; sweep < PMN_NORMAL_SWEEPS; ++sweep) {
-        pc_jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0, 1)
-        pc_jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0, 2)
-        pc_jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1, 2)
-    }
-    // eigenpairs (value, column of v) ascending, equal values by column
-    pc_eigen_order(a00, v00, v10, v20, a11, v01, v11, v21);
-    pc_eigen_order(a11, v01, v11, v21, a22, v02, v12, v22);
-    pc_eigen_order(a00, v00, v10, v20, a11, v01, v11, v21);
+    double v00, v01, v02, v10, v11, v12, v20, v21, v22;  // v[row][column]
+    pc_eigen3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
     const double l0 = a00, l1 = a11, l2 = a22;
     double nx = 0.0, ny = 0.0, nz = 0.0, var = 0.0;
     if (used >= 2 && l2 != 0.0 && l1 > a.line_ratio * l2) {
@@ -243,10 +195,7 @@ __global__ __launch_bounds__(64) void knn_normals_kernel(NormalArgs a) {
         ny = v10;
         nz = v20;
         var = l0 / (l0 + l1 + l2);
-        // canonical sign: the component of largest magnitude positive, the lowest axis among equals
-        const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
-        const double lead = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
-        bool flip = lead < 0.0;
+        bool flip = pc_canonical_flip(nx, ny, nz);
         if (a.n_viewpoints > 0) {  // towards the nearest viewpoint, the lowest index among equals
             double best = 0.0, bx = 0.0, by = 0.0, bz = 0.0;
             bool have = false;
@@ -266,9 +215,7 @@ __global__ __launch_bounds__(64) void knn_normals_kernel(NormalArgs a) {
             const double dot = cnx * bx + cny * by + cnz * bz;
             flip = flip != (dot < 0.0);
         }
-        nx = flip ? -nx : nx;
-        ny = flip ? -ny : ny;
-        nz = flip ? -nz : nz;
+        pc_flip(flip, nx, ny, nz);
     }
     a.normal[(size_t)q * 3] = (float)nx;
     a.normal[(size_t)q * 3 + 1] = (float)ny;
@@ -284,16 +231,11 @@ extern "C" int pmn_knn_normals(const float* to_xyz, const long long* to_keys, lo
     NormalArgs a;
     const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
     if (rc != PMN_OK) return rc;
-    if (!query || !normal || n_from < 1 || n_from >= (1LL << 31) - 64 || k < 1 || k > 32) return PMN_ERR_ARG;
-    if (!(max_dist > 0.0) || !std::isfinite(max_dist) || !std::isfinite(max_dist * max_dist)) return PMN_ERR_ARG;
-    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
+    if (query_args(a.q, query, order, n_from, same_cloud, n_to) != PMN_OK) return PMN_ERR_ARG;
+    if (!normal || !pc_k_ok(k) || !pc_reach_ok(max_dist)) return PMN_ERR_ARG;
     if (n_viewpoints < 0 || n_viewpoints > PMN_NORMAL_MAX_VIEWPOINTS || (n_viewpoints > 0 && !viewpoints)) return PMN_ERR_ARG;
     if (!(line_ratio >= 0.0) || !std::isfinite(line_ratio)) return PMN_ERR_ARG;
-    a.query = query;
-    a.order = order;
-    a.n_from = (int)n_from;
     a.k = k;
-    a.same_cloud = same_cloud ? 1 : 0;
     a.max_dist = max_dist;
     a.viewpoints = viewpoints;
     a.n_viewpoints = n_viewpoints;
@@ -301,10 +243,7 @@ extern "C" int pmn_knn_normals(const float* to_xyz, const long long* to_keys, lo
     a.normal = normal;
     a.variation = variation;
     a.count = count;
-    const dim3 grid((unsigned)((n_from + 63) / 64));
-    if (k <= 8) PMN_LAUNCH(knn_normals_kernel<8>, grid, dim3(64), 0, (hipStream_t)stream, a);
-    else if (k <= 16) PMN_LAUNCH(knn_normals_kernel<16>, grid, dim3(64), 0, (hipStream_t)stream, a);
-    else PMN_LAUNCH(knn_normals_kernel<32>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    PMN_LAUNCH_KBEST(k, knn_normals_kernel<CAP>, dim3((unsigned)((n_from + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
@@ -315,22 +254,14 @@ extern "C" int pmn_knn_distance(const float* to_xyz, const long long* to_keys, l
     KnnArgs a;
     const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
     if (rc != PMN_OK) return rc;
-    if (!query || n_from < 1 || n_from >= (1LL << 31) - 64 || k < 1 || k > 32) return PMN_ERR_ARG;
-    if (!(max_dist > 0.0) || !std::isfinite(max_dist) || !std::isfinite(max_dist * max_dist)) return PMN_ERR_ARG;
-    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
-    a.query = query;
-    a.order = order;
-    a.n_from = (int)n_from;
+    if (query_args(a.q, query, order, n_from, same_cloud, n_to) != PMN_OK) return PMN_ERR_ARG;
+    if (!pc_k_ok(k) || !pc_reach_ok(max_dist)) return PMN_ERR_ARG;
     a.k = k;
-    a.same_cloud = same_cloud ? 1 : 0;
     a.max_dist = max_dist;
     a.d2 = d2;
     a.index = index;
     a.mean = mean;
-    const dim3 grid((unsigned)((n_from + 63) / 64));
-    if (k <= 8) PMN_LAUNCH(knn_distance_kernel<8>, grid, dim3(64), 0, (hipStream_t)stream, a);
-    else if (k <= 16) PMN_LAUNCH(knn_distance_kernel<16>, grid, dim3(64), 0, (hipStream_t)stream, a);
-    else PMN_LAUNCH(knn_distance_kernel<32>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    PMN_LAUNCH_KBEST(k, knn_distance_kernel<CAP>, dim3((unsigned)((n_from + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     PMN_CHECK_LAUNCH();
     return PMN_OK;
 }
@@ -341,13 +272,8 @@ extern "C" int pmn_radius_count(const float* to_xyz, const long long* to_keys, l
     RadiusArgs a;
     const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
     if (rc != PMN_OK) return rc;
-    if (!query || !count || n_from < 1 || n_from >= (1LL << 31) - 64) return PMN_ERR_ARG;
-    if (!(radius >= 0.0) || !std::isfinite(radius) || !std::isfinite(radius * radius)) return PMN_ERR_ARG;
-    if (same_cloud && n_from != n_to) return PMN_ERR_ARG;
-    a.query = query;
-    a.order = order;
-    a.n_from = (int)n_from;
-    a.same_cloud = same_cloud ? 1 : 0;
+    if (query_args(a.q, query, order, n_from, same_cloud, n_to) != PMN_OK || !count) return PMN_ERR_ARG;
+    if (!(radius >= 0.0) || !std::isfinite(radius) || !std::isfinite(radius * radius)) return PMN_ERR_ARG;  // 0 is a radius
     a.radius = radius;
     a.count = count;
     PMN_LAUNCH(radius_count_kernel, dim3((unsigned)((n_from + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
@@ -361,11 +287,8 @@ extern "C" int pmn_nn_distance(const float* to_xyz, const long long* to_keys, lo
     NnArgs a;
     const int rc = grid_args(a.g, to_xyz, to_keys, n_to, origin_host, cell, dims_host);
     if (rc != PMN_OK) return rc;
-    if (!query || !dist || n_from < 1 || n_from >= (1LL << 31) - 64) return PMN_ERR_ARG;
-    if (!(max_dist > 0.0) || !std::isfinite(max_dist)) return PMN_ERR_ARG;
-    a.query = query;
-    a.order = order;
-    a.n_from = (int)n_from;
+    if (query_args(a.q, query, order, n_from, 0, n_to) != PMN_OK || !dist) return PMN_ERR_ARG;
+    if (!(max_dist > 0.0) || !std::isfinite(max_dist)) return PMN_ERR_ARG;  // the square is only ever a bound here and may be infinite
     a.max_dist = max_dist;
     a.dist = dist;
     a.index = index;

@@ -118,6 +118,13 @@ def _cells(points: torch.Tensor, origin, cell: float) -> torch.Tensor:
     return torch.floor((points.double() - o) / cell).clamp_(-2.0 ** 30, 2.0 ** 30).long()
 
 
+def _keys(points: torch.Tensor, origin, cell: float):
+    """(keys int64 [n], dims): the key (c.z * dims.y + c.y) * dims.x + c.x of every point's cell and the cells per axis."""
+    c = _cells(points, origin, cell)
+    dims = (c.max(0).values + 1).cpu().tolist()
+    return (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0], dims
+
+
 def build_grid(points: torch.Tensor, cell: float, origin=None) -> Grid:
     """Sorts ``points`` ([n,3] float32 on the device) into the cells of a uniform grid of side ``cell`` whose corner is ``origin``
     (default: the per-axis minimum of the points; a given origin must not exceed it)."""
@@ -134,11 +141,9 @@ def _sort_into_grid(points: torch.Tensor, cell: float, origin=None, what: str = 
     origin = lo if origin is None else np.asarray(origin, np.float64).reshape(3)
     if not np.isfinite(origin).all() or (origin > lo).any():
         raise PmnError(f"{what}: origin {origin.tolist()} must be finite and not above the points' minimum {lo.tolist()}")
-    c = _cells(points, origin.tolist(), cell)
-    dims = (c.max(0).values + 1).cpu().tolist()
+    keys, dims = _keys(points, origin.tolist(), cell)
     if max(dims) > 2 ** 30 or dims[0] * dims[1] * dims[2] >= 2 ** 62:
         raise PmnError(f"{what}: a grid of {dims} cells does not fit a 63-bit key (PMN_ERR_SHAPE); use a larger cell")
-    keys = (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
     keys, perm = torch.sort(keys)
     return Grid(points[perm].contiguous(), keys, perm, tuple(float(v) for v in origin), cell, tuple(int(d) for d in dims))
 
@@ -202,6 +207,43 @@ def _unsort(t: torch.Tensor, grid: Grid, same_cloud: bool) -> torch.Tensor:
     return out
 
 
+def _check_int(what: str, name: str, v, lo: int) -> None:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+        raise PmnError(f"{what}: {name} must be an integer >= {lo}, got {v!r}")
+
+
+def _check_k(what: str, k) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
+        raise PmnError(f"{what}: k must be an integer in 1..32, got {k!r}")
+    return int(k)
+
+
+def _check_reach(what: str, name: str, v, positive_square: bool = False) -> None:
+    """The cap of a k-nearest search.  The kernels compare squares, and where they divide by the cap's it must not have underflowed."""
+    square = float(v) * float(v)  # (** raises OverflowError where the product is infinite)
+    if not (v > 0.0 and np.isfinite(v) and np.isfinite(square) and (square > 0.0 or not positive_square)):
+        raise PmnError(f"{what}: {name} {'and its square must be' if positive_square else 'must be'} positive and finite, got {v}")
+
+
+def _query_search(entry: str, grid: Grid, query: Optional[torch.Tensor], same_cloud: bool, scalars, outputs) -> list:
+    """The C entry ``entry`` ("pmn_" + the public function's name) on the checked query: ``scalars`` are its arguments between n_from
+    and the outputs (a tensor goes as its pointer), or a function of the query's device that returns them; ``outputs`` its outputs as
+    (shape of a row, dtype, wanted).  Returns the wanted ones, rows in the caller's order; the others are passed as null."""
+    query, order = _search_query(entry[4:], query, grid, same_cloud)
+    n, dev = int(query.shape[0]), query.device
+    args = scalars(dev) if callable(scalars) else scalars
+    outs = [torch.empty((n,) + shape, dtype=dtype, device=dev) if wanted else None for shape, dtype, wanted in outputs]
+    with torch.cuda.device(dev):
+        check(getattr(_lib.lib(), entry)(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n,
+                                         *(a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args),
+                                         *(t.data_ptr() if t is not None else None for t in outs), _stream(query)), entry)
+    return [_unsort(t, grid, same_cloud) for t in outs if t is not None]
+
+
+def _one_or_tuple(out: list):
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def knn_distance(query: Optional[torch.Tensor], grid: Grid, k: int, max_dist: float, same_cloud: bool = False,
                  return_d2: bool = False, return_index: bool = False):
     """pmn_knn_distance: float64 [n], the mean distance from every query point to its ``k`` (1..32) nearest points of ``grid``; a
@@ -211,27 +253,14 @@ def knn_distance(query: Optional[torch.Tensor], grid: Grid, k: int, max_dist: fl
     first in the grid's sorted order).  The lists cost 8 k n and 4 k n bytes: the cleaning filters ask for the mean alone.
     ``same_cloud``: the queries are the grid's own points (``query`` must be None); a point is never its own neighbour (excluded by
     index: an exact duplicate at distance 0 is a neighbour), and row i of every result belongs to point i of the original cloud."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
-        raise PmnError(f"knn_distance: k must be an integer in 1..32, got {k!r}")
-    if not (max_dist > 0.0 and np.isfinite(max_dist) and np.isfinite(float(max_dist) ** 2)):
-        raise PmnError(f"knn_distance: max_dist must be positive and finite, got {max_dist}")
-    query, order = _search_query("knn_distance", query, grid, same_cloud)
-    n, k, dev = int(query.shape[0]), int(k), query.device
-    mean = torch.empty(n, dtype=torch.float64, device=dev)
-    d2 = torch.empty((n, k), dtype=torch.float64, device=dev) if return_d2 else None
-    index = torch.empty((n, k), dtype=torch.int32, device=dev) if return_index else None
-    with torch.cuda.device(dev):
-        check(_lib.lib().pmn_knn_distance(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n, k,
-                                          float(max_dist), int(bool(same_cloud)), d2.data_ptr() if return_d2 else None,
-                                          index.data_ptr() if return_index else None, mean.data_ptr(), _stream(query)),
-              "pmn_knn_distance")
-    out = [_unsort(mean, grid, same_cloud)]
-    if return_d2:
-        out.append(_unsort(d2, grid, same_cloud))
-    if return_index:
-        idx = index.long()
-        out.append(_unsort(torch.where(idx >= 0, grid.perm[idx.clamp_min(0)], idx), grid, same_cloud))
-    return out[0] if len(out) == 1 else tuple(out)
+    k = _check_k("knn_distance", k)
+    _check_reach("knn_distance", "max_dist", max_dist)
+    out = _query_search("pmn_knn_distance", grid, query, same_cloud, (k, float(max_dist), int(bool(same_cloud))),
+                        [((k,), torch.float64, return_d2), ((k,), torch.int32, return_index), ((), torch.float64, True)])
+    if return_index:  # sorted positions -> indices into the points the grid was built from
+        idx = out[-2].long()
+        out[-2] = torch.where(idx >= 0, grid.perm[idx.clamp_min(0)], idx)
+    return _one_or_tuple(out[-1:] + out[:-1])  # the mean comes first
 
 
 def radius_count(query: Optional[torch.Tensor], grid: Grid, radius: float, same_cloud: bool = False) -> torch.Tensor:
@@ -239,13 +268,8 @@ def radius_count(query: Optional[torch.Tensor], grid: Grid, radius: float, same_
     the float64 distance).  ``same_cloud``: as knn_distance; the point itself is not counted."""
     if not (radius >= 0.0 and np.isfinite(radius) and np.isfinite(float(radius) ** 2)):
         raise PmnError(f"radius_count: radius must be finite and >= 0, got {radius}")
-    query, order = _search_query("radius_count", query, grid, same_cloud)
-    n = int(query.shape[0])
-    count = torch.empty(n, dtype=torch.int32, device=query.device)
-    with torch.cuda.device(query.device):
-        check(_lib.lib().pmn_radius_count(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n,
-                                          float(radius), int(bool(same_cloud)), count.data_ptr(), _stream(query)), "pmn_radius_count")
-    return _unsort(count, grid, same_cloud)
+    return _query_search("pmn_radius_count", grid, query, same_cloud, (float(radius), int(bool(same_cloud))),
+                         [((), torch.int32, True)])[0]
 
 
 def default_cell(points: torch.Tensor, target: float = CLEAN_CELL_POINTS) -> float:
@@ -262,10 +286,7 @@ def default_cell(points: torch.Tensor, target: float = CLEAN_CELL_POINTS) -> flo
     cell = extent * max(min(target / n, 1.0) / 2.0, 2.0 ** -20)
     origin = lo.cpu().tolist()
     while cell < extent:
-        c = _cells(points, origin, cell)
-        dims = (c.max(0).values + 1).cpu().tolist()
-        keys = (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
-        if n / int(torch.unique(keys).numel()) >= target:
+        if n / int(torch.unique(_keys(points, origin, cell)[0]).numel()) >= target:
             break
         cell *= 2.0
     return cell
@@ -303,8 +324,7 @@ def radius_outliers(points: torch.Tensor, radius: float, min_neighbors: int, cel
     [n]); count[i] is the number of OTHER points within ``radius`` (<=) of point i and keep = count >= min_neighbors.  ``cell``
     (default: default_cell, but not below radius / 8 so that the walk stays within a few shells) changes the time only."""
     points = _points(points, "points")
-    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or min_neighbors < 0:
-        raise PmnError(f"radius_outliers: min_neighbors must be an integer >= 0, got {min_neighbors!r}")
+    _check_int("radius_outliers", "min_neighbors", min_neighbors, 0)
     if not (radius >= 0.0 and np.isfinite(radius)):
         raise PmnError(f"radius_outliers: radius must be finite and >= 0, got {radius}")
     if cell is None:
@@ -330,8 +350,7 @@ def cluster_dbscan(points: torch.Tensor, eps: float, min_points: int, cell: Opti
     within a few shells) changes the time only, and so do the sort inside the grid, the launch shape and the run.  The relabelling from
     the kernels' roots to size ranks is a handful of torch ops on the device."""
     points = _points(points, "points")
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or min_points < 1:
-        raise PmnError(f"cluster_dbscan: min_points must be an integer >= 1, got {min_points!r}")
+    _check_int("cluster_dbscan", "min_points", min_points, 1)
     if not (eps >= 0.0 and np.isfinite(eps) and np.isfinite(float(eps) * float(eps))):
         raise PmnError(f"cluster_dbscan: eps must be finite and >= 0, got {eps}")
     if cell is None:
@@ -364,9 +383,8 @@ def select_clusters(labels: torch.Tensor, sizes: torch.Tensor, min_cluster_point
     """bool [n]: the points of cluster_dbscan's clusters that hold at least ``min_cluster_points`` points and, with ``keep_largest`` > 0,
     are among the ``keep_largest`` first (labels are size ranks, so those are the largest, ties as cluster_dbscan breaks them).  Noise
     (label -1) is never kept."""
-    for name, v in (("min_cluster_points", min_cluster_points), ("keep_largest", keep_largest)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
-            raise PmnError(f"select_clusters: {name} must be an integer >= 0, got {v!r}")
+    _check_int("select_clusters", "min_cluster_points", min_cluster_points, 0)
+    _check_int("select_clusters", "keep_largest", keep_largest, 0)
     for name, t in (("labels", labels), ("sizes", sizes)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1:
             raise PmnError(f"select_clusters: {name}: expected a 1-D int64 tensor on a ROCm GPU (no CPU fallback)")
@@ -565,8 +583,7 @@ def _min_cos(what: str, normals, normal_angle) -> float:
 
 def _plane_settings(what: str, points, threshold, hypotheses, seed, refine):
     for name, v, lo in (("hypotheses", hypotheses, 1), ("seed", seed, 0), ("refine", refine, 0)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-            raise PmnError(f"{what}: {name} must be an integer >= {lo}, got {v!r}")
+        _check_int(what, name, v, lo)
     return PLANE_THRESHOLD_SPACINGS * cloud_spacing(points) if threshold is None else threshold
 
 
@@ -635,9 +652,8 @@ def segment_planes(points: torch.Tensor, threshold: Optional[float] = None, max_
     not accepted), or when fewer than 3 active points are left.  Returns a dict: ``labels`` int64 [n] on the device (-1, or the plane's
     index in order of extraction), ``planes`` float64 [k,4], ``counts`` (list of k) and ``results`` (segment_plane's dict per plane)."""
     threshold = _plane_settings("segment_planes", points, threshold, hypotheses, seed, refine)
-    for name, v in (("max_planes", max_planes), ("min_inliers", min_inliers)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-            raise PmnError(f"segment_planes: {name} must be an integer >= 1, got {v!r}")
+    _check_int("segment_planes", "max_planes", max_planes, 1)
+    _check_int("segment_planes", "min_inliers", min_inliers, 1)
     min_cos = _min_cos("segment_planes", normals, normal_angle)
     points, normals, active = _plane_inputs("segment_planes", points, normals, active, threshold, min_cos)
     n, dev = int(points.shape[0]), points.device
@@ -688,30 +704,17 @@ def knn_normals(query: Optional[torch.Tensor], grid: Grid, k: int, max_dist: flo
     a point.  Unlike the C entry, which only enqueues, this wrapper waits for the device when viewpoints are given: it checks them
     for non-finite values (one host read) and uploads host numbers first.  ``return_variation``: also float64 [n], the surface variation l0 / (l0 + l1 + l2), 0 where the normal is;
     ``return_count``: also int32 [n], the neighbours used (less than k where slots were capped).  ``same_cloud``: as knn_distance."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
-        raise PmnError(f"knn_normals: k must be an integer in 1..32, got {k!r}")
-    if not (max_dist > 0.0 and np.isfinite(max_dist) and np.isfinite(float(max_dist) ** 2)):
-        raise PmnError(f"knn_normals: max_dist must be positive and finite, got {max_dist}")
+    k = _check_k("knn_normals", k)
+    _check_reach("knn_normals", "max_dist", max_dist)
     if not (line_ratio >= 0.0 and np.isfinite(line_ratio)):
         raise PmnError(f"knn_normals: line_ratio must be finite and >= 0, got {line_ratio}")
-    query, order = _search_query("knn_normals", query, grid, same_cloud)
-    n, k, dev = int(query.shape[0]), int(k), query.device
-    views = _viewpoints("knn_normals", viewpoints, dev)
-    normal = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    variation = torch.empty(n, dtype=torch.float64, device=dev) if return_variation else None
-    count = torch.empty(n, dtype=torch.int32, device=dev) if return_count else None
-    with torch.cuda.device(dev):
-        check(_lib.lib().pmn_knn_normals(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n, k,
-                                         float(max_dist), int(bool(same_cloud)), views.data_ptr() if views is not None else None,
-                                         int(views.shape[0]) if views is not None else 0, float(line_ratio), normal.data_ptr(),
-                                         variation.data_ptr() if return_variation else None,
-                                         count.data_ptr() if return_count else None, _stream(query)), "pmn_knn_normals")
-    out = [_unsort(normal, grid, same_cloud)]
-    if return_variation:
-        out.append(_unsort(variation, grid, same_cloud))
-    if return_count:
-        out.append(_unsort(count, grid, same_cloud))
-    return out[0] if len(out) == 1 else tuple(out)
+
+    def scalars(dev):  # the viewpoints go to the query's device, and are checked after the query
+        views = _viewpoints("knn_normals", viewpoints, dev)
+        return k, float(max_dist), int(bool(same_cloud)), views, int(views.shape[0]) if views is not None else 0, float(line_ratio)
+
+    return _one_or_tuple(_query_search("pmn_knn_normals", grid, query, same_cloud, scalars,
+                                       [((3,), torch.float32, True), ((), torch.float64, return_variation), ((), torch.int32, return_count)]))
 
 
 def estimate_normals(points: torch.Tensor, k: int = 16, max_dist: Optional[float] = None, cell: Optional[float] = None,
@@ -762,29 +765,17 @@ def knn_mls(query: Optional[torch.Tensor], grid: Grid, k: int, radius: float, sa
     surface's unit normal at the projection, its largest component positive (0 0 0 where the point stayed); ``return_displacement``:
     also float64 [n], how far the point moved; ``return_status``: also int32 [n], 0 not fitted, 1 plane, 2 quadric; ``return_count``:
     also int32 [n], the neighbours in range.  ``same_cloud``: as knn_distance; the point itself then joins the fit with weight 1."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
-        raise PmnError(f"knn_mls: k must be an integer in 1..32, got {k!r}")
-    square = float(radius) * float(radius)  # (** raises OverflowError where the product is infinite)
-    if not (radius > 0.0 and np.isfinite(radius) and np.isfinite(square) and square > 0.0):
-        raise PmnError(f"knn_mls: radius and its square must be positive and finite, got {radius}")
+    k = _check_k("knn_mls", k)
+    _check_reach("knn_mls", "radius", radius, positive_square=True)
     if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)) or int(degree) not in (1, 2):
         raise PmnError(f"knn_mls: degree must be 1 or 2, got {degree!r}")
     if not (line_ratio >= 0.0 and np.isfinite(line_ratio)):
         raise PmnError(f"knn_mls: line_ratio must be finite and >= 0, got {line_ratio}")
-    query, order = _search_query("knn_mls", query, grid, same_cloud)
-    n, k, dev = int(query.shape[0]), int(k), query.device
-    position = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    normal = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_normal else None
-    displacement = torch.empty(n, dtype=torch.float64, device=dev) if return_displacement else None
-    status = torch.empty(n, dtype=torch.int32, device=dev) if return_status else None
-    count = torch.empty(n, dtype=torch.int32, device=dev) if return_count else None
-    with torch.cuda.device(dev):
-        check(_lib.lib().pmn_knn_mls(*_grid_args(grid), query.data_ptr(), order.data_ptr() if order is not None else None, n, k,
-                                     float(radius), int(bool(same_cloud)), int(degree), float(line_ratio), position.data_ptr(),
-                                     *(t.data_ptr() if t is not None else None for t in (normal, displacement, status, count)),
-                                     _stream(query)), "pmn_knn_mls")
-    out = [_unsort(t, grid, same_cloud) for t in (position, normal, displacement, status, count) if t is not None]
-    return out[0] if len(out) == 1 else tuple(out)
+    return _one_or_tuple(_query_search("pmn_knn_mls", grid, query, same_cloud,
+                                       (k, float(radius), int(bool(same_cloud)), int(degree), float(line_ratio)),
+                                       [((3,), torch.float32, True), ((3,), torch.float32, return_normal),
+                                        ((), torch.float64, return_displacement), ((), torch.int32, return_status),
+                                        ((), torch.int32, return_count)]))
 
 
 def smooth_mls(points: torch.Tensor, radius: Optional[float] = None, k: int = 32, degree: int = 2, iterations: int = 1,
@@ -798,8 +789,7 @@ def smooth_mls(points: torch.Tensor, radius: Optional[float] = None, k: int = 32
     [not fitted, projected onto a plane, projected onto a quadric] in the last iteration, and mean_displacement / max_displacement
     from the input position to the final one, in scene units and (``_spacings``) in units of the spacing."""
     points = _points(points, "points")
-    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 1:
-        raise PmnError(f"smooth_mls: iterations must be an integer >= 1, got {iterations!r}")
+    _check_int("smooth_mls", "iterations", iterations, 1)
     if cell is not None and not (float(cell) > 0.0 and np.isfinite(float(cell))):
         raise PmnError(f"smooth_mls: cell must be positive and finite, got {cell}")
     if not (float(radius_spacings) > 0.0 and np.isfinite(float(radius_spacings))):
@@ -857,13 +847,11 @@ def cloud_sdf(volume, grid: Grid, normals: torch.Tensor, colors: Optional[torch.
     if not isinstance(volume, SparseTsdfVolume):
         raise PmnError("cloud_sdf: volume must be a tsdf.SparseTsdfVolume")
     volume._allocated("cloud_sdf")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
-        raise PmnError(f"cloud_sdf: k must be an integer in 1..32, got {k!r}")
+    k = _check_k("cloud_sdf", k)
     radius = float(grid.cell) if radius is None else float(radius)
     boundary = SDF_BOUNDARY_RADII * radius if boundary is None else float(boundary)
-    for name, v in (("radius", radius), ("boundary", boundary)):
-        if not (v > 0.0 and np.isfinite(v) and np.isfinite(v * v) and v * v > 0.0):
-            raise PmnError(f"cloud_sdf: {name} and its square must be positive and finite, got {v}")
+    _check_reach("cloud_sdf", "radius", radius, positive_square=True)
+    _check_reach("cloud_sdf", "boundary", boundary, positive_square=True)
     if not isinstance(grid.xyz, torch.Tensor) or not grid.xyz.is_cuda or grid.xyz.device != volume.tsdf.device:
         raise PmnError(f"cloud_sdf: the grid is on {getattr(grid.xyz, 'device', None)}, the volume on {volume.tsdf.device} "
                        f"(no CPU fallback)")
@@ -883,7 +871,7 @@ def cloud_sdf(volume, grid: Grid, normals: torch.Tensor, colors: Optional[torch.
     with torch.cuda.device(dev):
         check(_lib.lib().pmn_cloud_sdf_blocks(*_grid_args(grid), nrm.data_ptr(), col.data_ptr() if col is not None else None,
                                               volume.blocks.data_ptr(), int(volume.blocks.shape[0]), dims, origin, volume.voxel,
-                                              volume.trunc, int(k), radius, boundary, volume.tsdf.data_ptr(), volume.weight.data_ptr(),
+                                              volume.trunc, k, radius, boundary, volume.tsdf.data_ptr(), volume.weight.data_ptr(),
                                               volume.rgb.data_ptr() if col is not None else None,
                                               volume.cweight.data_ptr() if col is not None else None, _stream(grid.xyz)),
               "pmn_cloud_sdf_blocks")
@@ -914,9 +902,8 @@ def mesh_from_cloud(points: torch.Tensor, normals: torch.Tensor, colors: Optiona
     normals = _per_point(normals, "normals", "mesh_from_cloud", torch.float32, n, dev)
     if colors is not None:
         colors = _per_point(colors, "colors", "mesh_from_cloud", torch.uint8, n, dev)
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
-        raise PmnError(f"mesh_from_cloud: k must be an integer in 1..32, got {k!r}")
-    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or not 1 <= int(min_neighbors) <= int(k):
+    k = _check_k("mesh_from_cloud", k)
+    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or not 1 <= int(min_neighbors) <= k:
         raise PmnError(f"mesh_from_cloud: min_neighbors must be an integer in 1..k, got {min_neighbors!r}")
     for name, v in (("voxel", voxel), ("radius", radius), ("trunc", trunc), ("boundary", boundary)):
         if v is not None and not (float(v) > 0.0 and np.isfinite(float(v))):
