@@ -276,6 +276,17 @@ int pmn_stem_f16s(const float *img, const float *w0, const float *s0, const void
 int pmn_stem_f16s_views(const float *const *img_table, int views, const float *w0, const float *s0, const void *w1a,
                         const float *s1, float *out, int B, int H, int W, void *stream);
 
+/* Added under ABI 25 (purely additive: tests of the existing suite pin the number).  pmn_stem_f16s followed by pmn_conv2d_f16s for
+ * FeatureNet's conv2 (8 -> 16, 5x5, stride 2, ReLU) in ONE launch: conv1's full-resolution map [N,H,W,8] stays in LDS and never
+ * reaches memory.  img, w0, s0, w1a, s1 as pmn_stem_f16s; w2b / s2 = conv2 as pmn_conv2d_f16s takes it (params.py pack_conv_f16s)
+ * -> out [N,Ho,Wo,16] channels-last, Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1: the same BITS as the two calls. */
+int pmn_stem_conv2_f16s(const float *img, const float *w0, const float *s0, const void *w1a, const float *s1, const void *w2b,
+                        const float *s2, float *out, int N, int H, int W, void *stream);
+
+/* The same through a device table of image addresses, as pmn_stem_f16s_views: out [views*B,Ho,Wo,16] view-major. */
+int pmn_stem_conv2_f16s_views(const float *const *img_table, int views, const float *w0, const float *s0, const void *w1a,
+                              const float *s1, const void *w2b, const float *s2, float *out, int B, int H, int W, void *stream);
+
 /* Stand-alone differentiable_warping (reference models/module.py:130-181) for API completeness and unit
  * parity: src_nchw [B,C,hs,ws], rel_proj [B,4,4], depth [B,D,h,w] -> warped [B,C,D,h,w].  Not on the fast path. */
 int pmn_differentiable_warping(const float *src_nchw, const float *rel_proj, const float *depth, int B, int C,

@@ -77,6 +77,8 @@ SIGNATURES = {
     "pmn_stem": [_fp] * 6 + [_i] * 3 + [_s],
     "pmn_stem_f16s": [_fp] * 6 + [_i] * 3 + [_s],
     "pmn_stem_f16s_views": [_fp, _i] + [_fp] * 5 + [_i] * 3 + [_s],
+    "pmn_stem_conv2_f16s": [_fp] * 8 + [_i] * 3 + [_s],
+    "pmn_stem_conv2_f16s_views": [_fp, _i] + [_fp] * 7 + [_i] * 3 + [_s],
     "pmn_differentiable_warping": [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _s],
     "pmn_fuse_view": [_fp, ctypes.c_longlong, _i, _hp, _hp, _i, _fp, _i, _i, _f, _f, _i, _f, _fp, _fp, _fp, _ip, _s],
     "pmn_fuse_view_merged": [_fp, ctypes.c_longlong, _i, _hp, _hp, _i, _fp, _i, _i, _f, _f, _i, _f, _fp, _fp, _fp, _ip, _fp,

@@ -696,3 +696,281 @@ extern "C" int pmn_stem_f16s_views(const float* const* img_table, int views, con
     if (!img_table || !w0 || !s0 || !w1a || !s1 || !out || views < 1 || B < 1 || H < 1 || W < 1) return PMN_ERR_ARG;
     return launch_stem_f16s(nullptr, img_table, B, W % 4 == 0, w0, s0, w1a, s1, out, views * B, H, W, stream);
 }
+
+
+// =================================================================================================================================
+// conv0 + conv1 + conv2 in one launch: the stem above followed by conv_f16s_kernel<8, 16, 5, 2, 8, 8, 2, ...> (reference
+// models/net.py:17-20, 51-52) without conv1's full-resolution map [N,H,W,8] (369 MB written and read back per six 1600x1200 views,
+// and read by nothing else).  Every value is produced by the operations of those two kernels in their order -- conv0's fma chain,
+// conv1's k-steps and epilogue, the split conv_f16s_kernel applies to what it loads, its k-steps, accumulators and epilogue -- so
+// the output holds the BITS of pmn_stem_f16s + pmn_conv2d_f16s (tests/test_stem_conv2_gpu.py).
+//
+// Workgroup = 512 threads = 16 x 16 half-resolution outputs.  Patches, origin in full-resolution pixels (y, x) = 2 (oy0, ox0) - ..:
+//   P1  image, origin -4: 3 x 39 rows of 40 floats (ten aligned float4 with W % 4 == 0)                                 18,720 B
+//   P2  conv0 + BN + ReLU, origin -3: 37 x 37 pixels, ZERO outside the image (conv1 pads conv0's map) -> hi / lo planes M0  43,808 B
+//   P3  conv1, origin -2: 35 x 35 pixels as 16-pixel M-tiles in LINEAR pixel order (a column of the MFMA depends on its own pixel
+//       only), three tiles per wave at a time; + shift, ReLU, ZERO outside the image (conv2 pads conv1's map), split -> M1    39,200 B
+//   P4  conv2 from M1: wave w owns output rows 2 w, 2 w + 1 (MT = 2 of the single-layer kernel); channels-last float4 stores.
+// LDS.  M0 and M1 are both live in P3 and are 83,008 B together -- 1,088 B more than half a CU's 160 KB.  M1's first three rows
+// (105 pixels, 1,680 B of its hi plane) therefore lie over the END of M0's lo plane (pixels 1264.., rows 34-36), and P3 runs in two
+// parts behind a barrier: pixels 105..1224 first (70 tiles; they read conv0 rows 3..36), then pixels 0..104 (7 tiles; conv0 rows
+// 0..4, which nothing has overwritten).  The image patch lives where M1 will be.  81,328 B: two workgroups = 4 waves per SIMD.
+// =================================================================================================================================
+template <int J>
+__device__ __forceinline__ void stem_conv2_conv1_tiles(const _Float16* __restrict__ m0h, _Float16* __restrict__ m1h, const f16x8 (&wa)[3][2],
+                                                       const f32x4_t sh1, const int first, const int ntiles, const int lim, const int g0,
+                                                       const int wave, const int li, const int kb, const int yc, const int xc, const int H,
+                                                       const int W) {
+    constexpr int C0 = 37, C1 = 35, M0PLANE = 37 * 37 * 8, M1PLANE = 35 * 35 * 8;
+    f32x4_t accM[J], accL[J];
+    const _Float16* pb[J];
+    int mm[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        accM[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        accL[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        const int t = wave + 8 * (g0 + j);  // tiles past the last one recompute it and store nothing
+        const int m = min(first + (t < ntiles ? t : ntiles - 1) * 16 + li, lim - 1);
+        mm[j] = t < ntiles && first + t * 16 + li < lim ? m : -1;
+        const int r = m / C1, c = m - r * C1;
+        pb[j] = m0h + (r * C0 + c) * 8;
+    }
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+        int q = 4 * ks + kb;
+        q = q < 8 ? q : 8;  // padding blocks 9..11 (zero weights) read tap 8
+        const int dy = q / 3, dx = q - dy * 3;
+        const int off = (dy * C0 + dx) * 8;  // rows up to 34 + 2, columns up to 34 + 2: inside M0's 37 x 37
+        f16x8 bh[J], blo[J];
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            bh[j] = *reinterpret_cast<const f16x8*>(pb[j] + off);
+            blo[j] = *reinterpret_cast<const f16x8*>(pb[j] + off + M0PLANE);
+        }
+#pragma unroll
+        for (int j = 0; j < J; ++j) accM[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[ks][0], bh[j], accM[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < J; ++j) accL[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[ks][0], blo[j], accL[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < J; ++j) accL[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[ks][1], bh[j], accL[j], 0, 0, 0);
+    }
+    // D rows 4 kb + e = output channels: lanes with kb < 2 hold channels [4 kb, 4 kb + 4) of pixel mm[j]
+    if (kb < 2) {
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const int m = mm[j];
+            if (m >= 0) {
+                const int r = m / C1, c = m - r * C1;
+                f16x4 hi = {0, 0, 0, 0}, lo = {0, 0, 0, 0};
+                if ((unsigned)(yc + r) < (unsigned)H && (unsigned)(xc + c) < (unsigned)W)  // stem_f16s_kernel's epilogue, conv_f16s_kernel's split
+                    f16s_split4(f16s_relu(f16s_epilogue(accM[j], accL[j], sh1)), hi, lo);
+                *reinterpret_cast<f16x4*>(m1h + m * 8 + 4 * kb) = hi;
+                *reinterpret_cast<f16x4*>(m1h + M1PLANE + m * 8 + 4 * kb) = lo;
+            }
+        }
+    }
+}
+
+template <bool VEC4>
+__global__ __launch_bounds__(512, 4) void stem_f16s_kernel_conv2(const float* __restrict__ img, const float* __restrict__ w0,
+                                                                const float* __restrict__ s0, const f16x8* __restrict__ w1A,
+                                                                const float* __restrict__ s1, const f16x8* __restrict__ w2B,
+                                                                const float* __restrict__ s2, float* __restrict__ out, const int N,
+                                                                const int H, const int W, const int Ho, const int Wo,
+                                                                const float* const* __restrict__ img_tab, const int BV) {
+    constexpr int TO = 16, NTHR = 512;
+    constexpr int IR = 39, IC = 40;  // image patch rows / floats per row
+    constexpr int R0 = 37, C0 = 37;  // conv0 patch (planes M0: 16 B per pixel)
+    constexpr int R1 = 35, C1 = 35;  // conv1 patch (planes M1)
+    constexpr int M0PLANE = R0 * C0 * 8, M1PLANE = R1 * C1 * 8;  // halves
+    constexpr int LATE = 3 * C1;     // M1's pixels [0, LATE) lie over the end of M0's lo plane and are produced last
+    static_assert((R1 * C1 - LATE) % 16 == 0, "the early part of conv1 is whole tiles");
+    extern __shared__ float4 sc2_lds4[];
+    _Float16* m0h = reinterpret_cast<_Float16*>(sc2_lds4);
+    _Float16* m1h = m0h + 2 * M0PLANE - LATE * 8;
+    float* xin = reinterpret_cast<float*>(m0h + 2 * M0PLANE);  // 18,720 B inside M1's 39,200 - 1,680: dead before M1 is written
+    typedef const float __attribute__((address_space(4))) cfloat;
+    const cfloat* cw0 = (const cfloat*)w0;  // [3][3][3][8]
+    const cfloat* cs0 = (const cfloat*)s0;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 15, kb = lane >> 4;
+    const int tiles_x = (Wo + TO - 1) / TO, tiles_y = (Ho + TO - 1) / TO;
+    const int bt = pmn_xcd_tile(blockIdx.x, N * tiles_x * tiles_y);
+    const int n = bt / (tiles_x * tiles_y), tr = bt - n * tiles_x * tiles_y;
+    const int oy0 = (tr / tiles_x) * TO, ox0 = (tr % tiles_x) * TO;
+    const int yi = 2 * oy0 - 4, xi = 2 * ox0 - 4;  // image patch origin; conv0's patch starts at + 1, conv1's at + 2
+    if (img_tab) img = img_tab[n / BV] + (ptrdiff_t)((n % BV) - n) * 3 * H * W;  // as stem_f16s_kernel (the indexing below adds n * 3 * H * W)
+
+    // conv1's weights (A operands of its three k-steps, hi | lo): in flight across P1 / P2
+    f16x8 wa[3][2];
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+        wa[ks][0] = w1A[(ks * 2 + 0) * 64 + lane];
+        wa[ks][1] = w1A[(ks * 2 + 1) * 64 + lane];
+    }
+    // ---- P1: image patch, a batch of the thread's loads in flight before its LDS writes.  Row R of 117 = (channel, patch row) --------
+    if constexpr (VEC4) {
+        constexpr int NU = (3 * IR + 31) / 32;  // passes of 32 rows
+        float4 v[NU];
+        const int j = tid & 15, gx = xi + 4 * j;  // float4 j of the row (10 used)
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int R = (tid >> 4) + 32 * u;
+            const int c = (R >= IR) + (R >= 2 * IR), r = R - IR * c, gy = yi + r;
+            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (j < 10 && R < 3 * IR && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
+                v[u] = *reinterpret_cast<const float4*>(img + (((size_t)n * 3 + c) * H + gy) * W + gx);
+        }
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int R = (tid >> 4) + 32 * u;
+            if (j < 10 && R < 3 * IR) *reinterpret_cast<float4*>(xin + R * IC + 4 * j) = v[u];
+        }
+    } else {  // any width / base alignment: one float per thread, 8 rows of 64 columns (40 used) per pass
+        const int q = tid & 63, gx = xi + q;
+#pragma unroll 1
+        for (int u0 = 0; u0 < 15; u0 += 5) {
+            float v[5];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const int R = (tid >> 6) + 8 * (u0 + u);
+                const int c = (R >= IR) + (R >= 2 * IR), r = R - IR * c, gy = yi + r;
+                v[u] = 0.0f;
+                if (q < IC && R < 3 * IR && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
+                    v[u] = img[(((size_t)n * 3 + c) * H + gy) * W + gx];
+            }
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const int R = (tid >> 6) + 8 * (u0 + u);
+                if (q < IC && R < 3 * IR) xin[R * IC + q] = v[u];
+            }
+        }
+    }
+    __syncthreads();
+    // ---- P2: conv0 + BN + ReLU on the 37 x 37 patch (fp32, stem_f16s_kernel's order of operations) -> hi / lo planes M0 --------------
+    for (int m = tid; m < R0 * C0; m += NTHR) {
+        const int r = m / C0, q = m - r * C0;
+        const int gy = yi + 1 + r, gx = xi + 1 + q;
+        f16x8 hi = {0, 0, 0, 0, 0, 0, 0, 0}, lo = {0, 0, 0, 0, 0, 0, 0, 0};
+        if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
+            float acc[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[c] = 0.0f;
+            const float* xp = xin + r * IC + q;  // input (gy - 1 + ky, gx - 1 + kx) = patch (r + ky, q + kx)
+#pragma unroll 1
+            for (int ky = 0; ky < 3; ++ky) {
+                const cfloat* wq = cw0 + __builtin_amdgcn_readfirstlane(ky * 72);
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+                    for (int ci = 0; ci < 3; ++ci) {
+                        const float v = xp[(ci * IR + ky) * IC + kx];
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) acc[c] = fmaf(v, wq[(kx * 3 + ci) * 8 + c], acc[c]);
+                    }
+            }
+#pragma unroll
+            for (int c = 0; c < 8; c += 2) {
+                const f32x2_t x = {fmaxf(acc[c] + cs0[c], 0.0f), fmaxf(acc[c + 1] + cs0[c + 1], 0.0f)};
+                const f16x2_t h = f16s_hi2(x), l = f16s_lo2(x, h);
+                hi[c] = h[0];
+                hi[c + 1] = h[1];
+                lo[c] = l[0];
+                lo[c + 1] = l[1];
+            }
+        }
+        *reinterpret_cast<f16x8*>(m0h + m * 8) = hi;
+        *reinterpret_cast<f16x8*>(m0h + M0PLANE + m * 8) = lo;
+    }
+    __syncthreads();  // M0 complete; the image patch is dead: its region becomes M1
+    // ---- P3: conv1 on the 35 x 35 patch, pixels [LATE, 1225) = 70 tiles, then -- M0's last rows are dead -- pixels [0, LATE) ---------
+    {
+        const f32x4_t sh1 = *reinterpret_cast<const f32x4_t*>(s1 + 4 * (kb & 1));
+        constexpr int NT1 = (R1 * C1 - LATE) / 16;
+#pragma unroll 1
+        for (int g = 0; g * 8 < NT1; g += 3)
+            stem_conv2_conv1_tiles<3>(m0h, m1h, wa, sh1, LATE, NT1, R1 * C1, g, wave, li, kb, yi + 2, xi + 2, H, W);
+        __syncthreads();
+        stem_conv2_conv1_tiles<1>(m0h, m1h, wa, sh1, 0, (LATE + 15) / 16, LATE, 0, wave, li, kb, yi + 2, xi + 2, H, W);
+    }
+    __syncthreads();
+    // ---- P4: conv2 (8 -> 16, 5x5, stride 2) as conv_f16s_kernel<8, 16, 5, 2, 8, 8, 2, ..., SWAP = true>: wave w owns rows 2 w, 2 w + 1
+    {
+        constexpr int MT = 2, NQ = 25, KSTEPS = 7, S = 2, KS = 5;
+        f32x4_t accM[MT], accL[MT];
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+            accM[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            accL[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+        const f16x8* bl = w2B + lane;  // element (ks * 2 + split) * 64 + lane
+        f16x8 bq[2][2];
+        bq[0][0] = bl[0];
+        bq[0][1] = bl[64];
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+            const int cur = ks & 1, nxt = cur ^ 1;
+            const int sidx = ks + 1 < KSTEPS ? ks + 1 : KSTEPS - 1;
+            bq[nxt][0] = bl[(size_t)(sidx * 2 + 0) * 64];
+            bq[nxt][1] = bl[(size_t)(sidx * 2 + 1) * 64];
+            int q = 4 * ks + kb;
+            if (4 * ks + 3 >= NQ) q = q < NQ - 1 ? q : NQ - 1;
+            const int dy = q / KS, dx = q - dy * KS;
+            // rows up to 2 (2 * 7 + 1) + 4 = 34 and columns up to 2 * 15 + 4 = 34: inside M1's 35 x 35
+            const _Float16* pa = m1h + ((wave * MT * S + dy) * C1 + li * S + dx) * 8;
+            f16x8 ah[MT], al[MT];
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                ah[t] = *reinterpret_cast<const f16x8*>(pa + t * S * C1 * 8);
+                al[t] = *reinterpret_cast<const f16x8*>(pa + t * S * C1 * 8 + M1PLANE);
+            }
+#pragma unroll
+            for (int t = 0; t < MT; ++t) accM[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bq[cur][0], ah[t], accM[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) accL[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bq[cur][1], ah[t], accL[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) accL[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bq[cur][0], al[t], accL[t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const int ox = ox0 + li, oyw = oy0 + wave * MT;
+        if (ox < Wo) {
+            float* po = out + (((size_t)n * Ho + oyw) * Wo + ox) * 16 + 4 * kb;
+            const size_t rs = (size_t)Wo * 16;
+            const f32x4_t sh2 = *reinterpret_cast<const f32x4_t*>(s2 + 4 * kb);
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+                if (oyw + t < Ho) *reinterpret_cast<f32x4_t*>(po + t * rs) = f16s_relu(f16s_epilogue(accM[t], accL[t], sh2));
+        }
+    }
+}
+
+static int launch_stem_conv2_f16s(const float* img, const float* const* img_table, int B, bool vec4, const float* w0, const float* s0,
+                                  const void* w1a, const float* s1, const void* w2b, const float* s2, float* out, int N, int H, int W,
+                                  void* stream) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const size_t lds = ((size_t)2 * 37 * 37 + (size_t)2 * 35 * 35 - 3 * 35) * 8 * sizeof(_Float16);  // 81,328 B
+    const int blocks = N * ((Wo + 15) / 16) * ((Ho + 15) / 16);
+    auto kern = vec4 ? stem_f16s_kernel_conv2<true> : stem_f16s_kernel_conv2<false>;
+    if (pmn_raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds) != PMN_OK) return PMN_ERR_LAUNCH;
+    PMN_LAUNCH(kern, dim3(blocks), dim3(512), lds, (hipStream_t)stream, img, w0, s0, reinterpret_cast<const f16x8*>(w1a), s1,
+               reinterpret_cast<const f16x8*>(w2b), s2, out, N, H, W, Ho, Wo, img_table, B);
+    PMN_CHECK_LAUNCH();
+    return PMN_OK;
+}
+
+// pmn_stem_f16s followed by pmn_conv2d_f16s (8 -> 16, 5x5, stride 2, ReLU) in one launch, bit for bit: img, w0, s0, w1a, s1 as
+// pmn_stem_f16s; w2b DEVICE fp16 [1][7][1][2][64][8] / s2 [16] = params.pack_conv_f16s of conv2 -> out [N,Ho,Wo,16] channels-last
+// float32, Ho = (H - 1) / 2 + 1.
+extern "C" int pmn_stem_conv2_f16s(const float* img, const float* w0, const float* s0, const void* w1a, const float* s1, const void* w2b,
+                                   const float* s2, float* out, int N, int H, int W, void* stream) {
+    if (!img || !w0 || !s0 || !w1a || !s1 || !w2b || !s2 || !out || N < 1 || H < 1 || W < 1) return PMN_ERR_ARG;
+    const bool vec4 = W % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0;
+    return launch_stem_conv2_f16s(img, nullptr, 1, vec4, w0, s0, w1a, s1, w2b, s2, out, N, H, W, stream);
+}
+
+// The same through a device table of image addresses, as pmn_stem_f16s_views: out [views*B,Ho,Wo,16] view-major.
+extern "C" int pmn_stem_conv2_f16s_views(const float* const* img_table, int views, const float* w0, const float* s0, const void* w1a,
+                                         const float* s1, const void* w2b, const float* s2, float* out, int B, int H, int W,
+                                         void* stream) {
+    if (!img_table || !w0 || !s0 || !w1a || !s1 || !w2b || !s2 || !out || views < 1 || B < 1 || H < 1 || W < 1) return PMN_ERR_ARG;
+    return launch_stem_conv2_f16s(nullptr, img_table, B, W % 4 == 0, w0, s0, w1a, s1, w2b, s2, out, views * B, H, W, stream);
+}

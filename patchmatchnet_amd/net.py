@@ -55,6 +55,9 @@ class FeatureNet(nn.Module):
         self.fold_fpn = True
         # conv3 + conv4 as ONE launch (pmn_conv2d_f16s_pair, bit-identical to the two launches); False = one launch per layer
         self.fuse_conv34 = True
+        # conv0 + conv1 + conv2 as ONE launch (pmn_stem_conv2_f16s[_views], bit-identical to stem + conv2): conv1's full-resolution map
+        # [N,H,W,8] never reaches memory; False = the stem's launch, then conv2's
+        self.fuse_stem_conv2 = True
         # verification switch (test hook): the FPN's 1/8 level through the VALU kernel (pmn_fpn_level) instead of the fp32 matrix cores
         self.fpn8_valu = False
         # None in the product.  patchmatchnet_amd/research.py (PMN_EXPERIMENTAL=1 only) installs a callable (layer index, input) ->
@@ -127,18 +130,25 @@ class FeatureNet(nn.Module):
         in_place = image_table is not None
         if in_place and not (self.f16_split and "conv1_f16s" in pk):
             raise PmnError("image_table: only the fp16-split stem (FeatureNet.f16_split, weights inside its domain) reads images in place")
-        if in_place:
+        stem_conv2 = self.f16_split and self.fuse_stem_conv2 and "conv1_f16s" in pk and "conv2_f16s" in pk
+        if in_place and stem_conv2:
+            t = ops.stem_conv2_f16s_views(image_table, *pk["conv0"], *pk["conv1_f16s"], *pk["conv2_f16s"])
+        elif in_place:
             t = ops.stem_f16s_views(image_table, *pk["conv0"], *pk["conv1_f16s"])
+        elif stem_conv2:
+            t = torch.empty((B * len(imgs), (H - 1) // 2 + 1, (W - 1) // 2 + 1, 16), dtype=torch.float32, device=imgs[0].device)
         else:
             t = torch.empty((B * len(imgs), H, W, 8), dtype=torch.float32, device=imgs[0].device)
         for i, im in enumerate(() if in_place else imgs):  # conv0 + conv1 fused (pmn_stem_f16s: conv1 on the fp16 matrix cores; pmn_stem: all fp32 VALU)
-            if self.f16_split and "conv1_f16s" in pk:
+            if stem_conv2:  # ... and conv2 behind them in the same launch
+                ops.stem_conv2_f16s(im.contiguous(), *pk["conv0"], *pk["conv1_f16s"], *pk["conv2_f16s"], out=t[i * B:(i + 1) * B])
+            elif self.f16_split and "conv1_f16s" in pk:
                 ops.stem_f16s(im.contiguous(), *pk["conv0"], *pk["conv1_f16s"], out=t[i * B:(i + 1) * B])
             else:
                 ops.stem(im.contiguous(), *pk["conv0"], *pk["conv1"], out=t[i * B:(i + 1) * B])
         feats = {}
         for i, (k, s, p) in enumerate(self._SPEC):
-            if i < 2:
+            if i < 2 or (i == 2 and stem_conv2):
                 continue
             if i == 4 and self.f16_split and self.fuse_conv34 and "conv3_f16s" in pk and "conv4_f16s" in pk:
                 continue  # (done with conv3 below)

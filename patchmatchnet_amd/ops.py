@@ -951,6 +951,55 @@ def stem_f16s_views(images: "SourceTable", w0: torch.Tensor, s0: torch.Tensor, w
     return out
 
 
+def _stem_conv2_packs(what: str, w0: torch.Tensor, s0: torch.Tensor, w1a: torch.Tensor, s1: torch.Tensor, w2b: torch.Tensor,
+                      s2: torch.Tensor) -> None:
+    for n_, t_ in (("w0", w0), ("s0", s0), ("s1", s1), ("s2", s2)):
+        _dev(t_, n_)
+    if tuple(_dev_as(w1a, what + ": w1a", torch.float16).shape) != (3, 2, 64, 8) or tuple(w0.shape) != (3, 3, 3, 8):
+        raise PmnError(what + ": 3->8 conv0 weights and the float16 [3,2,64,8] tensor of params.pack_stem_conv1_f16s")
+    if tuple(_dev_as(w2b, what + ": w2b", torch.float16).shape) != (1, 7, 1, 2, 64, 8) or s2.numel() != 16:
+        raise PmnError(what + ": w2b / s2 must be params.pack_conv_f16s of a (5, 2, 8, 16) layer")
+
+
+def stem_conv2_f16s(img: torch.Tensor, w0: torch.Tensor, s0: torch.Tensor, w1a: torch.Tensor, s1: torch.Tensor, w2b: torch.Tensor,
+                    s2: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pmn_stem_conv2_f16s: FeatureNet conv0 + conv1 + conv2 in one launch, conv1's full-resolution map in LDS; img [N,3,H,W] ->
+    [N,Ho,Wo,16] channels-last (optionally into ``out``), the bits of ``stem_f16s`` followed by ``conv2d_f16s(.., 5, 2, relu=True)``."""
+    _dev(img, "img")
+    _stem_conv2_packs("stem_conv2_f16s", w0, s0, w1a, s1, w2b, s2)
+    N, c, H, W = img.shape
+    if c != 3:
+        raise PmnError("stem_conv2_f16s: expects a 3-channel image")
+    _f16_domain_probe(img)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = torch.empty((N, Ho, Wo, 16), dtype=torch.float32, device=img.device)
+    else:
+        _dev(out, "out")
+        if tuple(out.shape) != (N, Ho, Wo, 16):
+            raise PmnError("stem_conv2_f16s: bad `out` shape")
+    with torch.cuda.device(img.device):
+        check(_lib.lib().pmn_stem_conv2_f16s(img.data_ptr(), w0.data_ptr(), s0.data_ptr(), w1a.data_ptr(), s1.data_ptr(), w2b.data_ptr(),
+                                             s2.data_ptr(), out.data_ptr(), N, H, W, _stream(img)), "pmn_stem_conv2_f16s")
+    return out
+
+
+def stem_conv2_f16s_views(images: "SourceTable", w0: torch.Tensor, s0: torch.Tensor, w1a: torch.Tensor, s1: torch.Tensor,
+                          w2b: torch.Tensor, s2: torch.Tensor) -> torch.Tensor:
+    """pmn_stem_conv2_f16s_views: ``stem_conv2_f16s`` over ``views`` separately allocated [B,3,H,W] images found through a device
+    table of addresses (``images``: a SourceTable with shape (views, B, 3, H, W)) -> [views*B,Ho,Wo,16] view-major."""
+    if not isinstance(images, SourceTable) or len(images.shape) != 5 or images.shape[2] != 3:
+        raise PmnError("stem_conv2_f16s_views: a SourceTable of shape (views, B, 3, H, W)")
+    _stem_conv2_packs("stem_conv2_f16s_views", w0, s0, w1a, s1, w2b, s2)
+    V, B, _, H, W = images.shape
+    out = torch.empty((V * B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 16), dtype=torch.float32, device=images.device)
+    with torch.cuda.device(images.device):
+        check(_lib.lib().pmn_stem_conv2_f16s_views(images.table.data_ptr(), V, w0.data_ptr(), s0.data_ptr(), w1a.data_ptr(),
+                                                   s1.data_ptr(), w2b.data_ptr(), s2.data_ptr(), out.data_ptr(), B, H, W, _stream(out)),
+              "pmn_stem_conv2_f16s_views")
+    return out
+
+
 def fuse_view(maps: torch.Tensor, ref_slot: int, src_slots: Sequence[int], mats: torch.Tensor, geo_pixel_thres: float,
               geo_depth_thres: float, geo_mask_thres: int, photo_thres: float, want_depth_avg: bool = False,
               want_geo_sum: bool = False, sizes: Optional[Sequence[Tuple[int, int]]] = None):
