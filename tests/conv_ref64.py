@@ -137,6 +137,48 @@ def chain2(x, la, lb, relu=True, pad_input=False):
     return conv_bn(m, lb["w"], lb.get("bn"), lb.get("bias"), relu=relu, pad=1)
 
 
+def chain3(x, l0, l1, l2, conv1_off_image=False, conv0_off_image=False, origin=0, tile_roll=0, relu1=True):
+    """FeatureNet's front (reference models/net.py:17-20, 51-52): conv0 3 -> 8 and conv1 8 -> 8 (3x3, padding 1), conv2 8 -> 16 (5x5,
+    stride 2, padding 2), BatchNorm or bias and ReLU after each; every layer zero-pads ITS OWN input map -> (y, A) of conv2,
+    [N,16,(H-1)//2+1,(W-1)//2+1].  Keyword arguments: mistakes of a kernel that fuses the three layers over patches.
+    ``conv1_off_image``: conv1's map is not zeroed outside the image before conv2 -- conv1 is evaluated there, from the zero-padded
+    conv0 map, and conv2 reads ReLU(shift + ...) where it should read 0.  ``conv0_off_image``: the same one layer down (conv0 is
+    evaluated one pixel outside the image from the zero-padded image, and conv1 reads that).  ``origin`` = +-1: conv2 samples conv1
+    around 2 o + origin instead of 2 o.  ``tile_roll`` = t: outputs with o % 16 == 15 along an axis are computed from conv1's map
+    rolled by t pixels along that axis (a tile's last row / column taken from the neighbouring tile's patch).  ``relu1`` False: no
+    ReLU after conv1."""
+    def cb(m, l, **kw):
+        return conv_bn(m, l["w"], l.get("bn"), l.get("bias"), **kw)
+
+    def margin(m, before, after):
+        return np.pad(m, ((0, 0), (0, 0), (before, after), (before, after)))
+
+    def conv2(m1):  # m1 [N,8,H,W]: taps 2 o + origin - 2 .. 2 o + origin + 2
+        return cb(margin(m1, 2 - origin, 2 + origin), l2, relu=True, stride=2, pad=0)
+
+    x = f64(x)
+    if conv0_off_image:
+        m0, _ = cb(margin(x, 2, 2), l0, relu=True, pad=0)    # [H+2, W+2]: not zero in the one-pixel rim conv1 reads
+        m1, _ = cb(m0, l1, relu=relu1, pad=0)
+        return conv2(m1)
+    m0, _ = cb(x, l0, relu=True, pad=1)
+    if conv1_off_image:
+        m1, _ = cb(margin(m0, 3, 3), l1, relu=relu1, pad=0)  # [H+4, W+4]: not zero in the two-pixel rim conv2 reads
+        return cb(m1, l2, relu=True, stride=2, pad=0)
+    m1, _ = cb(m0, l1, relu=relu1, pad=1)
+    y, A = conv2(m1)
+    if tile_roll:
+        y = y.copy()
+        for ax in (2, 3):
+            rim = np.arange(y.shape[ax]) % 16 == 15
+            other = conv2(np.roll(m1, -tile_roll, axis=ax))[0]
+            if ax == 2:
+                y[:, :, rim, :] = other[:, :, rim, :]
+            else:
+                y[:, :, :, rim] = other[:, :, :, rim]
+    return y, A
+
+
 def fpn_tail(x, up, w_in, b_in, w_out, align_corners=False):
     """output3(bilinear_x2(up) + inner2(x)) (reference models/net.py:64-67) -> (y, A)."""
     inner, Ai = conv2d(x, w_in, b_in)

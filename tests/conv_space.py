@@ -1,8 +1,10 @@
 """The convolution kernel space: one row per call of the convolution-side entry points (pmn_conv2d, pmn_conv2d_mfma, pmn_conv2d_f16s,
 pmn_conv2d_f16s_pair, pmn_offset_heads_f16s, pmn_fpn_level, pmn_fpn_tail, pmn_deconv3x3s2, pmn_stem, pmn_stem_f16s,
-pmn_stem_f16s_views, pmn_refine_front, pmn_refine_tail, pmn_refine_fused), each naming the kernel instantiation its shape selects.
+pmn_stem_f16s_views, pmn_stem_conv2_f16s, pmn_stem_conv2_f16s_views, pmn_refine_front, pmn_refine_tail, pmn_refine_fused), each naming
+the kernel instantiation its shape selects.
 Rows use the smallest shapes at which these kernels can go wrong: 1x1 (2x2 where the ABI wants even sizes) and 3x5 images, exactly
-one tile / one pixel short / one past (16x16; 16x32 for the f16s stem; 14x14 for the pair kernel), odd and even sizes under stride 2,
+one tile / one pixel short / one past (16x16; 16x32 for the f16s stem; 14x14 for the pair kernel; 16x16 half-resolution outputs =
+32x32 input pixels for the fused conv0 + conv1 + conv2 kernel), odd and even sizes under stride 2,
 tile counts below, at and past the 8-way pmn_xcd_tile remap with N = 1, 2, 3, offset heads on images smaller than their dilation,
 relu 0 and 1, BatchNorm-folded and bias-only weights, image bases off by one float, two depth ranges.  Every row fits in 64x64
 pixels; the two conv_kernel<..., TP = 4, ...> rows need N*Ho*Wo >= 1,500,000 (launch_conv in csrc/conv.hip: `pix >= 1500000L`): the
@@ -40,7 +42,7 @@ ENVS = (E_S0C8, E_C8, E_S0)
 @dataclass(frozen=True)
 class Row:
     op: str                  # conv2d | mfma1x1 | f16s | pair | heads | fpn_level | fpn_tail | deconv | stem | stem_f16s | stem_views |
-    #                          refine_front | refine_tail | refine_fused
+    #                          stem_conv2 | stem_conv2_views | refine_front | refine_tail | refine_fused
     kernel: str              # the instantiation this row selects (readable form; mangle() gives the symbol)
     N: int = 1
     H: int = 16              # input size (deconv: the half-resolution input; refine: the full-resolution output)
@@ -58,7 +60,7 @@ class Row:
     nchw_in: bool = False
     planar: bool = False     # planar [N,C,H,W] output
     misalign: bool = False   # image base off by one float: the scalar-staging kernel, same bits as the aligned call
-    views: int = 0           # stem_views: N = views * B
+    views: int = 0           # stem_views, stem_conv2_views: N = views * B
     env: Env = ()            # PMN_CONV_SPLIT / PMN_CONV_CC5 of the process that runs the row (read once per process)
     large: bool = False      # the one large row
     res_max: float = 0.0     # refine_tail / refine_fused: conv3 and res weights are scaled so that max |res| is this, in normalised depth
@@ -177,6 +179,33 @@ def _rows() -> List[Row]:
         rows.append(Row("stem_f16s", SS, N=N, H=H, W=W, cin=3, cout=8, misalign=True))
     rows.append(Row("stem_views", SV, N=6, views=3, H=33, W=20, cin=3, cout=8))
     rows.append(Row("stem_views", SS, N=2, views=2, H=17, W=15, cin=3, cout=8))
+    # ---- pmn_stem_conv2_f16s[_views]: conv0 + conv1 + conv2 in one launch.  A workgroup is 16 x 16 half-resolution outputs = 32 x 32
+    #      input pixels; 81 KB of dynamic LDS, so the rows are device_only.  Sizes are the full-resolution input.  <true>: 1x4 the
+    #      smallest; 32x32 exactly one tile; 30x32 one output row short of it; 34x36 x 2 one past it both ways = 2 * 2 * 2 = 8 workgroups,
+    #      the pmn_xcd_tile boundary; 64x64 = 4, below it; 64x40 x 3 = 12, past it and no multiple of 8.  <false>: 1x1; 3x5 x 2; 31x31 =
+    #      16 x 16 outputs whose last stride-2 taps fall off the image; 33x33 x 2 = 8 workgroups; 63x9 a tall strip; 34x35 x 3 = 12.
+    #      BatchNorm-folded and bias-only weights (all three layers) alternate with the row's index among its kernel's rows, from
+    #      the hash add() uses ---------------------------------------------------------------------------------------------------------
+    C2V, C2S = "stem_f16s_kernel_conv2<true>", "stem_f16s_kernel_conv2<false>"
+    nth2: Dict[str, int] = {}
+
+    def conv2_row(op, kernel, H, W, N, **kw):
+        key = _key(op, kernel, (), kw.get("misalign", False))
+        j = nth2[key] = nth2.get(key, -1) + 1
+        rows.append(Row(op, kernel, N=N, H=H, W=W, cin=3, cout=16, K=5, S=2, pad=2, device_only=True,
+                        bn=((zlib.crc32(key.encode()) >> 9) + j) % 2 == 0, **kw))
+
+    for H, W, N in ((1, 4, 1), (32, 32, 1), (30, 32, 1), (34, 36, 2), (64, 64, 1), (64, 40, 3)):
+        conv2_row("stem_conv2", C2V, H, W, N)
+    for H, W, N in ((1, 1, 1), (3, 5, 2), (31, 31, 1), (33, 33, 2), (63, 9, 1), (34, 35, 3)):
+        conv2_row("stem_conv2", C2S, H, W, N)
+    for H, W, N in ((32, 32, 1), (34, 36, 2)):
+        conv2_row("stem_conv2", C2S, H, W, N, misalign=True)
+    # (views, B): 3 x 2 with the images allocated apart and in an order unrelated to the view index (run_device); 2 x 1 through the
+    # scalar staging; 2 x 2 at 3x4, where every pixel is a border pixel of all three layers
+    conv2_row("stem_conv2_views", C2V, 33, 20, 6, views=3)
+    conv2_row("stem_conv2_views", C2S, 17, 15, 2, views=2)
+    conv2_row("stem_conv2_views", C2V, 3, 4, 4, views=2)
     # ---- Refinement: B = 2 rows use both depth ranges (kernel_space.DEPTH_RANGES); every refine_tail / refine_fused row carries
     #      res_max = 0.25 (set below): case() scales the res weights so that max |res| is 0.25 in normalised depth units, inside
     #      [0.05, 0.5], so the residual is NOT small against dnorm in [0, 1] ----------------------------------------------------------
@@ -220,6 +249,7 @@ FAMILIES = {
     "fpn_tail_kernel": "PKfS1_S1_S1_S1_Pfiii",
     "deconv3x3s2_kernel": "PKfS1_S1_Pfiiii",
     "stem_f16s_kernel": "PKfS1_S1_PKDv8_DF16_S1_PfiiiPKS1_i",
+    "stem_f16s_kernel_conv2": "PKfS1_S1_PKDv8_DF16_S1_S4_S1_PfiiiiiPKS1_i",
     "refine_fused_kernel": "PKfS1_S1_S1_S1_S1_PKDv8_DF16_S1_S1_S1_S1_S1_Pfiii",
 }
 OTHER_KERNELS = {
@@ -233,11 +263,14 @@ def mangle(readable: str) -> str:
     return KS.mangle(readable, FAMILIES, OTHER_KERNELS)
 
 
+STEM_CONV2 = ("stem_conv2", "stem_conv2_views")  # input H x W -> output (H - 1) // 2 + 1 x (W - 1) // 2 + 1 x 16 (K = 5, S = 2, pad = 2)
+
+
 def out_hw(row: Row) -> Tuple[int, int]:
     if row.op == "deconv":
         return 2 * row.H, 2 * row.W
     f = lambda n: (n + 2 * row.pad - row.dil * (row.K - 1) - 1) // row.S + 1  # noqa: E731
-    return (f(row.H), f(row.W)) if row.op in ("conv2d", "mfma1x1", "f16s", "heads") else (row.H, row.W)
+    return (f(row.H), f(row.W)) if row.op in ("conv2d", "mfma1x1", "f16s", "heads") + STEM_CONV2 else (row.H, row.W)
 
 
 # ---- launch-plan recording ---------------------------------------------------------------------------------------------------------
@@ -278,6 +311,10 @@ def record(row: Row, L=None) -> Tuple[int, List[str]]:
             rc = L.pmn_stem_f16s(img, A, A, A, A, A, N, H, W, None)
         elif row.op == "stem_views":
             rc = L.pmn_stem_f16s_views(A, row.views, A, A, A, A, A, N // row.views, H, W, None)
+        elif row.op == "stem_conv2":
+            rc = L.pmn_stem_conv2_f16s(img, A, A, A, A, A, A, A, N, H, W, None)
+        elif row.op == "stem_conv2_views":
+            rc = L.pmn_stem_conv2_f16s_views(A, row.views, A, A, A, A, A, A, A, N // row.views, H, W, None)
         elif row.op == "refine_front":
             rc = L.pmn_refine_front(A, A, A, A, A, A, A, N, H, W, None)
         elif row.op == "refine_tail":
@@ -378,6 +415,9 @@ def case(row: Row) -> Dict:
     elif row.op in ("stem", "stem_f16s", "stem_views"):
         c["x"] = rng.random((N, 3, H, W)).astype(np.float32) * 2 - 1
         c["la"], c["lb"] = _layer(rng, 8, 3, 3, True), _layer(rng, 8, 8, 3, True)
+    elif row.op in STEM_CONV2:  # BatchNorm or bias on all three layers: a nonzero shift each, so ReLU(shift) != 0 outside the image
+        c["x"] = rng.random((N, 3, H, W)).astype(np.float32) * 2 - 1
+        c["la"], c["lb"], c["lc"] = _layer(rng, 8, 3, 3, row.bn), _layer(rng, 8, 8, 3, row.bn), _layer(rng, 16, 8, 5, row.bn)
     elif row.op.startswith("refine"):
         lo = np.array([KS.DEPTH_RANGES[b % 2][0] for b in range(N)], np.float32)
         hi = np.array([KS.DEPTH_RANGES[b % 2][1] for b in range(N)], np.float32)
@@ -414,6 +454,12 @@ def reference(row: Row, **mk) -> Dict[str, np.ndarray]:
         y, A = R.chain2(c["x"], c["la"], c["lb"], relu=relu or mk.pop("force_relu", False), **mk)
     elif row.op in ("stem", "stem_f16s", "stem_views"):
         y, A = R.chain2(c["x"], c["la"], c["lb"], relu=True, **mk)
+    elif row.op in STEM_CONV2:
+        x = c["x"]
+        if mk.pop("swap_view_batch", False):  # image n read at table entry n % views, sample n // views (n = view * B + sample is right)
+            V, B = row.views, row.N // row.views
+            x = x[[(n % V) * B + n // V for n in range(row.N)]]
+        y, A = R.chain3(x, c["la"], c["lb"], c["lc"], **mk)
     elif row.op == "fpn_level":
         y, A = R.fpn_level(c["x"], c.get("u"), c["w"], c["b"], **mk)
     elif row.op == "fpn_tail":
@@ -436,14 +482,15 @@ def reference(row: Row, **mk) -> Dict[str, np.ndarray]:
 
 METRIC = {"conv2d": "single", "mfma1x1": "single", "f16s": "single", "heads": "single", "fpn_level": "single", "deconv": "single",
           "refine_front": "single", "pair": "fused", "stem": "fused", "stem_f16s": "fused", "stem_views": "fused", "fpn_tail": "fused",
+          "stem_conv2": "fused", "stem_conv2_views": "fused",
           "refine_tail": "refine", "refine_fused": "refine"}
-F16S_OPS = ("f16s", "pair", "heads", "stem_f16s", "stem_views", "refine_fused")
+F16S_OPS = ("f16s", "pair", "heads", "stem_f16s", "stem_views", "stem_conv2", "stem_conv2_views", "refine_fused")
 
 
 def family(row: Row) -> str:
     if row.op == "conv2d":
         return row.kernel.split("<")[0]
-    return "stem_f16s" if row.op == "stem_views" else row.op
+    return "stem_f16s" if row.op == "stem_views" else "stem_conv2" if row.op == "stem_conv2_views" else row.op
 
 
 def error(row: Row, got, ref: Dict[str, np.ndarray]) -> float:
@@ -479,11 +526,12 @@ MEASURED: Dict[str, float] = {  # largest error over the family's rows (torch 2.
     "conv_kernel": 3.245e-07, "conv_tiled_kernel": 2.669e-07, "mfma1x1": 3.627e-07, "deconv": 2.063e-07, "fpn_level": 2.952e-07,
     "fpn_tail": 7.888e-07, "stem": 4.658e-07, "refine_front": 1.950e-07, "refine_tail": 6.594e-07,                # float32, x 8
     "f16s": 7.952e-08, "heads": 1.085e-07, "pair": 9.739e-07, "stem_f16s": 6.627e-07, "refine_fused": 5.815e-07,  # emulation, x 4
+    "stem_conv2": 1.035e-06,                                                                                      # emulation, x 4
 }
 TOL: Dict[str, float] = {
     "conv_kernel": 2.6e-6, "conv_tiled_kernel": 2.2e-6, "mfma1x1": 3.0e-6, "deconv": 1.7e-6, "fpn_level": 2.4e-6, "fpn_tail": 6.4e-6,
     "stem": 3.8e-6, "refine_front": 1.6e-6, "refine_tail": 5.3e-6,
-    "f16s": 3.2e-7, "heads": 4.4e-7, "pair": 3.9e-6, "stem_f16s": 2.7e-6, "refine_fused": 2.4e-6,
+    "f16s": 3.2e-7, "heads": 4.4e-7, "pair": 3.9e-6, "stem_f16s": 2.7e-6, "refine_fused": 2.4e-6, "stem_conv2": 4.2e-6,
 }
 
 
@@ -518,7 +566,7 @@ def _emu(x32, l, K, S, dil, CC, relu, **kw):
     return R.f16s_conv(np.asarray(x32, np.float32), w.astype(np.float32).astype(np.float64), sh.astype(np.float32), K, S, dil, CC, relu, **kw)
 
 
-def evaluate(row: Row, dtype="float32", drop_lo: bool = False) -> np.ndarray:
+def evaluate(row: Row, dtype="float32", drop_lo=False) -> np.ndarray:
     """The row in torch on the CPU, layer by layer with torch.nn.functional (conv2d, conv_transpose2d, interpolate, batch_norm), in
     ``dtype``.  float64: the check that conv_ref64 itself is right.  float32: what fp32 arithmetic costs; the split-fp16 layers of
     the f16s ops then go through the emulation conv_ref64.f16s_conv."""
@@ -553,6 +601,12 @@ def evaluate(row: Row, dtype="float32", drop_lo: bool = False) -> np.ndarray:
         if emu:
             return _emu(m.numpy(), c["lb"], 3, 1, 1, 8, True, drop_lo=drop_lo)
         return _tconv(m, L(c["lb"]), r, 1, 1).numpy()
+    if row.op in STEM_CONV2:  # the stem_f16s chain followed by the 8 -> 16, 5x5, stride 2 f16s layer; drop_lo: True, "conv1" or "conv2"
+        m = _tconv(T(c["x"]), L(c["la"]), True, 1, 1)
+        if emu:
+            m = _emu(m.numpy(), c["lb"], 3, 1, 1, 8, True, drop_lo=drop_lo in (True, "conv1"))
+            return _emu(m, c["lc"], 5, 2, 1, params.f16s_chunk(8, 5), True, drop_lo=drop_lo in (True, "conv2"))
+        return _tconv(_tconv(m, L(c["lb"]), True, 1, 1), L(c["lc"]), True, 2, 2).numpy()
     if row.op == "fpn_level":
         y = Fn.conv2d(T(c["x"]), T(c["w"].T[:, :, None, None]), T(c["b"]))
         return (up2(c["u"]) + y if row.up else y).numpy()
@@ -594,6 +648,23 @@ def mistakes(row: Row, ref: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
         out["bilinear up-sampling with aligned corners"] = reference(row, align_corners=True)["y"]
     if row.op in ("pair", "stem", "stem_f16s", "stem_views"):
         out["input padded instead of the intermediate map"] = reference(row, pad_input=True)["y"]
+    if row.op in STEM_CONV2:
+        # Exempt: nothing from M1, M2, M3, M5, M6 -- they differ on every row, the 1x1 image included (its one output has no interior
+        # taps, only rim ones).  M4 needs an output with o % 16 == 15 (Ho or Wo >= 16) along an axis that is not exactly the
+        # 32-pixel tile pitch long (rolling 32 pixels by 32 moves nothing), which leaves out the small rows, the 32x32 rows, and
+        # 30x32, whose 15 output rows have no such output and whose 32 columns roll onto themselves.  M7 is for the table entry and needs
+        # B > 1: with one sample per view n % views = n // B and the swapped lookup is the right one.
+        out["M1: conv1's map not zeroed outside the image"] = reference(row, conv1_off_image=True)["y"]
+        out["M2: conv0's map not zeroed outside the image"] = reference(row, conv0_off_image=True)["y"]
+        out["M3: conv2 samples conv1 at 2 o - 1"] = reference(row, origin=-1)["y"]
+        out["M3: conv2 samples conv1 at 2 o + 1"] = reference(row, origin=1)["y"]
+        if (Ho >= 16 and row.H != 32) or (Wo >= 16 and row.W != 32):
+            out["M4: a tile's last row / column from the neighbouring tile's patch"] = reference(row, tile_roll=32)["y"]
+        out["M5: lo terms dropped in conv1"] = evaluate(row, "float32", drop_lo="conv1").astype(np.float64)
+        out["M5: lo terms dropped in conv2"] = evaluate(row, "float32", drop_lo="conv2").astype(np.float64)
+        out["M6: no ReLU after conv1"] = reference(row, relu1=False)["y"]
+        if row.op == "stem_conv2_views" and row.N > row.views:
+            out["M7: view and sample index swapped in the table lookup"] = reference(row, swap_view_batch=True)["y"]
     if row.op == "deconv":
         out["last row and column missing"] = reference(row, short=True)["y"]
         out["parity classes swapped"] = reference(row, swap=True)["y"]
@@ -619,7 +690,9 @@ def mistakes(row: Row, ref: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
 
 def run_device(row: Row, want_aligned: bool = False):
     """The row through patchmatchnet_amd.ops on cuda:0 -> planar float32 numpy output (with ``want_aligned``: (output, the output of
-    the same call on an aligned base / through pmn_stem_f16s per view), for the same-bits checks)."""
+    the same call on an aligned base / through pmn_stem_f16s per view), for the same-bits checks; the stem_conv2 ops give a LIST of
+    outputs that must hold the same bits: pmn_stem_f16s + pmn_conv2d_f16s on the aligned image, per view for the table entry, and
+    for a base off by one float the aligned pmn_stem_conv2_f16s call too)."""
     import torch
 
     import patchmatchnet_amd as P
@@ -703,6 +776,29 @@ def run_device(row: Row, want_aligned: bool = False):
                     out = pl(ops.stem_f16s_views(tab, w0, s0, w1, s1))
                     if want_aligned:
                         other = np.concatenate([pl(ops.stem_f16s(i, w0, s0, w1, s1)) for i in imgs], 0)
+        elif row.op in STEM_CONV2:
+            w0, s0 = pk(params.pack_conv, c["la"])
+            w2, s2 = pk(params.pack_conv_f16s, c["lc"])
+            Lb = TW(c["lb"])  # (pack_stem_conv1_f16s takes BatchNorm tensors: a bias alone is scale 1, mean 0, variance 1 at eps 0)
+            bn1, eps = (Lb["bn"], R.BN_EPS) if "bn" in Lb else ((torch.ones(8), Lb["bias"], torch.zeros(8), torch.ones(8)), 0.0)
+            w1, s1 = (t(a) for a in params.pack_stem_conv1_f16s(Lb["w"], bn1, eps))
+            two = lambda im: ops.conv2d_f16s(ops.stem_f16s(im, w0, s0, w1, s1), w2, s2, 5, 2, relu=True)  # noqa: E731
+            if row.op == "stem_conv2":
+                out = pl(ops.stem_conv2_f16s(mis(c["x"]) if row.misalign else t(c["x"]), w0, s0, w1, s1, w2, s2))
+                if want_aligned:  # the two launches on the aligned image, and for a base off by one float the aligned call itself
+                    other = [pl(two(t(c["x"])))] + ([pl(ops.stem_conv2_f16s(t(c["x"]), w0, s0, w1, s1, w2, s2))] if row.misalign else [])
+            else:
+                V, B = row.views, row.N // row.views
+                imgs, spacers = {}, []
+                for v in reversed(range(V)):  # allocated apart and backwards: the table's order is unrelated to the addresses'
+                    spacers.append(torch.empty(1000 * (v + 1) + 4, device=dev))
+                    imgs[v] = t(c["x"][v * B:(v + 1) * B])
+                imgs = [imgs[v] for v in range(V)]
+                assert all(ops.SourceTable.image_in_place(i) for i in imgs)
+                tab = ops.SourceTable(torch.tensor([i.data_ptr() for i in imgs], dtype=torch.int64, device=dev), (V, B, 3, row.H, row.W))
+                out = pl(ops.stem_conv2_f16s_views(tab, w0, s0, w1, s1, w2, s2))
+                if want_aligned:
+                    other = [np.concatenate([pl(two(i)) for i in imgs], 0)]
         else:
             T0, Td, T3 = TW(c["c0"]), TW(c["dc"]), TW(c["c3"])
             w0, s0 = (t(a) for a in params.pack_conv(T0["w"], bn=T0["bn"]))

@@ -2,7 +2,10 @@
 recording, no device; rows that carry an environment record in a fresh child process with it), the rows jointly reach every
 instantiation of the convolution kernel families in the library's symbol table, the float64 reference (tests/conv_ref64.py) agrees with
 torch.nn.functional in float64 on every row, the tolerances are what float32 arithmetic (or the split-fp16 emulation) needs times a
-fixed margin, and each is far below the error of a plausible kernel mistake.  The device side is tests/test_conv_space_gpu.py."""
+fixed margin, and each is far below the error of a plausible kernel mistake.  The rows of pmn_stem_conv2_f16s and
+pmn_stem_conv2_f16s_views (stem_f16s_kernel_conv2: 16 x 16 half-resolution outputs = 32 x 32 input pixels per workgroup, 81 KB of LDS)
+record on a device only, like every form above 48 KB; their table, reference, emulation and mistakes (a fused intermediate map that
+is not zero outside the image among them) are checked here.  The device side is tests/test_conv_space_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -75,12 +78,56 @@ def test_table_holds_the_shapes_it_promises():
     for op in ("conv2d", "f16s", "pair", "deconv"):
         assert {r.relu for r in rows if r.op == op} == {0, 1}, op
     assert {r.bn for r in rows if r.op == "f16s"} == {True, False}
-    assert {r.op for r in rows if r.misalign} == {"stem_f16s", "refine_fused"} and all(r.W % 4 == 0 for r in rows if r.misalign)
+    assert {r.op for r in rows if r.misalign} == {"stem_f16s", "stem_conv2", "refine_fused"} and all(r.W % 4 == 0 for r in rows if r.misalign)
+    # the fused conv0 + conv1 + conv2 kernel: a workgroup is 16 x 16 half-resolution outputs; the family's own tile counts and weights
+    fc = [r for r in rows if CS.family(r) == "stem_conv2"]
+    assert {r.op for r in fc} == {"stem_conv2", "stem_conv2_views"} and all(r.device_only and max(r.H, r.W) <= 64 for r in fc)
+    assert {r.kernel for r in fc} == {"stem_f16s_kernel_conv2<true>", "stem_f16s_kernel_conv2<false>"}
+    assert all((r.kernel.endswith("<true>")) == (r.W % 4 == 0 and not r.misalign) for r in fc)
+    assert any(max(r.H, r.W) <= 5 for r in fc)
+    groups = {r.N * -(-CS.out_hw(r)[0] // 16) * -(-CS.out_hw(r)[1] // 16) for r in fc}
+    assert 8 in groups and any(g < 8 for g in groups) and any(g > 8 and g % 8 for g in groups)
+    assert {r.N for r in fc} >= {1, 2, 3} and {r.bn for r in fc} == {True, False}
+    assert any(CS.out_hw(r) == (16, 16) and (r.H, r.W) == (32, 32) for r in fc)  # exactly one tile
+    assert {(r.views, r.N // r.views) for r in fc if r.views} == {(3, 2), (2, 1), (2, 2)}
+    for r in fc:  # a nonzero shift on every layer, a positive one among them: ReLU(shift) != 0 where a layer's map must be ZERO
+        c = CS.case(r)
+        for l in (c["la"], c["lb"], c["lc"]):
+            sh = R.fold(l["w"], l.get("bn"), l.get("bias"))[1]
+            assert (sh != 0).all() and (sh > 0).any(), r.id
     for r in rows:
         if r.op.startswith("refine") and r.op != "refine_front":
             m = np.abs(CS.reference(r)["res"]).max()
             assert 0.05 <= m <= 0.5, (r.id, m)
     assert any(r.op == "refine_fused" and r.N == 2 for r in rows)
+
+
+def test_image_in_place_keeps_unaligned_images_out_of_the_table():
+    """pmn_stem_conv2_f16s_views (like pmn_stem_f16s_views) picks the float4 staging from W % 4 == 0 alone: it cannot see the
+    addresses in the table.  ops.SourceTable.image_in_place is what refuses an image whose base is not 16-byte aligned.  No device
+    here, so a real tensor's answers are passed on with is_cuda forced."""
+    from patchmatchnet_amd import ops
+
+    class OnDevice:
+        is_cuda = True
+
+        def __init__(self, t):
+            self.t, self.dtype = t, t.dtype
+
+        def is_contiguous(self):
+            return self.t.is_contiguous()
+
+        def data_ptr(self):
+            return self.t.data_ptr()
+
+    buf = torch.zeros(3 * 4 * 4 + 8)
+    first = (-buf.data_ptr() // 4) % 4  # the first float of buf on a 16-byte boundary
+    aligned, off_by_one = (buf[first + d:first + d + 48].view(1, 3, 4, 4) for d in (0, 1))
+    assert aligned.data_ptr() % 16 == 0 and off_by_one.data_ptr() % 16 == 4 and off_by_one.is_contiguous()
+    assert ops.SourceTable.image_in_place(OnDevice(aligned))
+    assert not ops.SourceTable.image_in_place(OnDevice(off_by_one))
+    assert not ops.SourceTable.image_in_place(OnDevice(aligned.double())) and not ops.SourceTable.image_in_place(OnDevice(aligned[:, :, ::2]))
+    assert not ops.SourceTable.image_in_place(aligned)  # (a host tensor is never read in place)
 
 
 def test_f16s_emulation_agrees_with_the_lane_level_one():

@@ -1,10 +1,13 @@
 """CPU-side checks of a launch plan's fork/join region (include/pmn_hip.h: pmn_plan_fork / _switch / _join / _entry_branch /
 _launch_part): recording touches no device, so the markers, their error paths and the branch tags are checked here through ctypes
-without a GPU, and so is the host-only overlap check of patchmatchnet_amd/ops.py.  Replay: tests/test_plan_branch_gpu.py; the recorder
-under sanitizers: tests/test_plan_host.py."""
+without a GPU, and so is the host-only overlap check of patchmatchnet_amd/ops.py.  Where a device is visible a replay launches for
+real, so the one replay of recorded launches here runs in a child process that sees no device (tests/nodevice.py).  Replay:
+tests/test_plan_branch_gpu.py; the recorder under sanitizers: tests/test_plan_host.py."""
 import ctypes
 
 import pytest
+
+import nodevice
 
 
 @pytest.fixture(scope="module")
@@ -90,8 +93,29 @@ def test_recorded_launches_take_the_current_branch(L):
     assert names[1] == "<fork>" and names[5] == "<join>"
     assert "nchw_to_nhwc_kernel" in names[0] and "normalize_depth_kernel" in names[2] and "nchw_to_nhwc_kernel" in names[3]
     assert "confidence" in names[4] and "normalize_depth_kernel" in names[6]
-    assert L.pmn_plan_launch_part(p, 1, None) == -3  # no device here: the side branch's launch itself fails, loudly
     assert L.pmn_plan_destroy(p) == 0
+    # Replaying a part LAUNCHES its kernels on those addresses wherever a device is visible: what the side branch's launch answers
+    # without one is asked of a child process that sees none (tests/nodevice.py), which records the fork region again.
+    got = nodevice.run("""
+        p = new_plan()
+        assert L.pmn_plan_begin(p) == 0
+        assert L.pmn_nchw_to_nhwc(0x1000, 0x2000, 1, 4, 4, 4, None) == 0
+        assert L.pmn_plan_fork(p) == 0
+        assert L.pmn_normalize_depth(0x1000, 0x2000, 0x3000, 2, 100, 0x4000, None) == 0
+        assert L.pmn_plan_switch(p, 1) == 0
+        assert L.pmn_nchw_to_nhwc(0x5000, 0x6000, 1, 4, 4, 4, None) == 0
+        assert L.pmn_plan_switch(p, 0) == 0
+        assert L.pmn_confidence(0x1000, 1, 8, 4, 4, 8, 8, 0x2000, None, None) == 0
+        assert L.pmn_plan_join(p) == 0
+        assert L.pmn_normalize_depth(0x1000, 0x2000, 0x3000, 2, 100, 0x4000, None) == 0
+        assert L.pmn_plan_end(p) == 0
+        tags = [L.pmn_plan_entry_branch(p, i) for i in range(L.pmn_plan_count(p))]
+        rc = L.pmn_plan_launch_part(p, 1, None)
+        L.pmn_plan_destroy(p)
+        print("NODEVICE_JSON " + json.dumps({"tags": tags, "launch_part": rc}))
+    """)
+    assert got["tags"] == tags
+    assert got["launch_part"] == -3  # no device there: the side branch's launch itself fails, loudly
 
 
 def test_fork_marks_do_nothing_outside_a_plan_recording():
