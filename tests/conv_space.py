@@ -12,10 +12,10 @@ cin = 1 row is THE large row (1 x 1200 x 1250 = exactly the threshold, Wo % 4 ==
 smaller workload either, so it gets a second row of that size, 379 images of 64x62 (1,503,872 pixels).
 
 Plain helper module (no tests here): tests/test_conv_space.py checks the table on the CPU, tests/test_conv_space_gpu.py runs every
-row on the device against tests/conv_ref64.py."""
+row on the device against tests/conv_ref64.py, tests/test_guard_band_gpu.py runs every row through the raw C ABI between guard
+bands (buffers(), arguments(), run_guard() below)."""
 from __future__ import annotations
 
-import ctypes
 import functools
 import json
 import os
@@ -29,6 +29,7 @@ import numpy as np
 
 import conv_ref64 as R
 import kernel_space as KS
+from guard_band import Buf, recording_addresses
 
 Env = Tuple[Tuple[str, str], ...]
 E_S0C8: Env = (("PMN_CONV_CC5", "8"), ("PMN_CONV_SPLIT", "0"))
@@ -275,59 +276,130 @@ def out_hw(row: Row) -> Tuple[int, int]:
 
 # ---- launch-plan recording ---------------------------------------------------------------------------------------------------------
 
+# op -> (entry point, its pointer arguments in the header's order and by the header's names).  The table entries take `views` after
+# the table; the images a table points to are buffers of the call (img0, img1, ...) but no arguments of it.
+_STEM = ("w0", "s0", "w1a", "s1")
+_FRONT = ("t2", "w0", "s0", "wd", "sd")
+_TAIL = ("wr", "dnorm", "depth_min", "depth_max", "out")
+ABI = {
+    "conv2d": ("pmn_conv2d", ("in", "weights", "shift", "up", "out")),
+    "mfma1x1": ("pmn_conv2d_mfma", ("in", "weights", "shift", "out", "out_b")),
+    "f16s": ("pmn_conv2d_f16s", ("in", "weights", "shift", "out")),
+    "pair": ("pmn_conv2d_f16s_pair", ("in", "weights_a", "shift_a", "weights_b", "shift_b", "out")),
+    "heads": ("pmn_offset_heads_f16s", ("in", "weights", "shift", "out_a", "out_b")),
+    "fpn_level": ("pmn_fpn_level", ("x", "u", "w", "b", "out_a", "out_b")),
+    "fpn_tail": ("pmn_fpn_tail", ("x", "up", "w_in", "b_in", "w_out", "out")),
+    "deconv": ("pmn_deconv3x3s2", ("in", "weights", "shift", "out")),
+    "stem": ("pmn_stem", ("img", "w0", "s0", "w1", "s1", "out")),
+    "stem_f16s": ("pmn_stem_f16s", ("img",) + _STEM + ("out",)),
+    "stem_views": ("pmn_stem_f16s_views", ("img_table",) + _STEM + ("out",)),
+    "stem_conv2": ("pmn_stem_conv2_f16s", ("img",) + _STEM + ("w2b", "s2", "out")),
+    "stem_conv2_views": ("pmn_stem_conv2_f16s_views", ("img_table",) + _STEM + ("w2b", "s2", "out")),
+    "refine_front": ("pmn_refine_front", ("img",) + _FRONT + ("x16",)),
+    "refine_tail": ("pmn_refine_tail", ("x16", "w3", "s3") + _TAIL),
+    "refine_fused": ("pmn_refine_fused", ("img",) + _FRONT + ("w3a", "s3") + _TAIL),
+}
+
+
+def buffers(row: Row) -> List[Buf]:
+    """The buffers of the row's call: name (include/pmn_hip.h's), role, dtype and element count exactly as the header documents it,
+    padded pack layouts included and nothing more."""
+    from patchmatchnet_amd import params
+    N, H, W, cin, cout, ca, K = row.N, row.H, row.W, row.cin, row.cout, row.ca, row.K
+    Ho, Wo = out_hw(row)
+    up = lambda c, m: -(-c // m) * m  # noqa: E731
+    I = lambda name, count, **kw: Buf(name, "in", "float32", count, **kw)  # noqa: E731,E741
+    P = lambda name, count, dtype="float32": Buf(name, "weights", dtype, count)  # noqa: E731
+    O = lambda name, count: Buf(name, "out", "float32", count)  # noqa: E731,E741
+    op = row.op
+    img = I("img", N * 3 * H * W, misalign=row.misalign)
+    stem = [P("w0", 3 * 3 * 3 * 8), P("s0", 8), P("w1a", 3 * 2 * 64 * 8, "float16"), P("s1", 8)]
+    conv2 = [P("w2b", 1 * 7 * 1 * 2 * 64 * 8, "float16"), P("s2", 16)]
+    front = [I("t2", N * (H // 2) * (W // 2) * 8), P("w0", 3 * 3 * 3 * 8), P("s0", 8), P("wd", 3 * 3 * 8 * 8), P("sd", 8)]
+    tail = [P("wr", 3 * 3 * 8), I("dnorm", N * (H // 2) * (W // 2)), I("depth_min", N), I("depth_max", N), O("out", N * H * W)]
+    if op == "conv2d":  # weights [K][K][cin][coutp], coutp = cout rounded up to 8 (cout <= 8) or to a multiple of 16
+        cp = 8 if cout <= 8 else up(cout, 16)
+        return [I("in", N * cin * H * W), P("weights", K * K * cin * cp), P("shift", cp)] + \
+            ([I("up", N * (Ho // 2) * (Wo // 2) * cout)] if row.up else []) + [O("out", N * Ho * Wo * cout)]
+    if op == "mfma1x1":  # weights [K*K][cin/8][coutp/32][64][4], coutp = cout rounded up to 32
+        cp = up(cout, 32)
+        return [I("in", N * H * W * 64), P("weights", (64 // 8) * (cp // 32) * 64 * 4), P("shift", cp), O("out", N * H * W * ca),
+                O("out_b", N * H * W * (cout - ca))]
+    if op == "f16s":  # weights float16 [cin/CC][k-steps][cout/16][2][64][8], k-steps = K*K*(CC/8) blocks of 8 channels, four per step
+        CC = params.f16s_chunk(cin, K)
+        return [I("in", N * H * W * cin), P("weights", (cin // CC) * up(K * K * (CC // 8), 4) // 4 * (cout // 16) * 2 * 64 * 8, "float16"),
+                P("shift", cout), O("out", N * Ho * Wo * cout)]
+    if op == "pair":  # two (k 3, stride 1, 16 -> 16) layers as pmn_conv2d_f16s takes them: [1][5][1][2][64][8]
+        return [I("in", N * H * W * 16), P("weights_a", 5 * 2 * 64 * 8, "float16"), P("shift_a", 16), P("weights_b", 5 * 2 * 64 * 8, "float16"),
+                P("shift_b", 16), O("out", N * H * W * 16)]
+    if op == "heads":  # weights float16 [cin/16][k-steps][coutp/16][2][64][8], coutp = cout rounded up to 16; 9 taps x 2 blocks = 5 steps
+        cp = up(cout, 16)
+        return [I("in", N * H * W * cin), P("weights", (cin // 16) * 5 * (cp // 16) * 2 * 64 * 8, "float16"), P("shift", cp),
+                O("out_a", N * ca * H * W)] + ([O("out_b", N * (cout - ca) * H * W)] if ca < cout else [])
+    if op == "fpn_level":
+        return [I("x", N * H * W * cin)] + ([I("u", N * (H // 2) * (W // 2) * cout)] if row.up else []) + \
+            [P("w", cin * cout), P("b", cout), O("out_a", N * H * W * ca)] + ([O("out_b", N * H * W * (cout - ca))] if ca < cout else [])
+    if op == "fpn_tail":
+        return [I("x", N * H * W * 16), I("up", N * (H // 2) * (W // 2) * 64), P("w_in", 16 * 64), P("b_in", 64), P("w_out", 64 * 16),
+                O("out", N * H * W * 16)]
+    if op == "deconv":
+        return [I("in", N * H * W * 8), P("weights", 3 * 3 * 8 * 8), P("shift", 8), O("out", N * 2 * H * 2 * W * 8)]
+    if op == "stem":
+        return [img, P("w0", 3 * 3 * 3 * 8), P("s0", 8), P("w1", 3 * 3 * 8 * 8), P("s1", 8), O("out", N * H * W * 8)]
+    if op == "stem_f16s":
+        return [img] + stem + [O("out", N * H * W * 8)]
+    if op == "stem_conv2":
+        return [img] + stem + conv2 + [O("out", N * Ho * Wo * 16)]
+    if op in ("stem_views", "stem_conv2_views"):  # a device table of `views` addresses, entry v = a dense [B,3,H,W] image of its own
+        names = tuple(f"img{v}" for v in range(row.views))
+        return [Buf("img_table", "in", "int64", row.views, table_of=names)] + [I(n, (N // row.views) * 3 * H * W) for n in names] + stem + \
+            (conv2 + [O("out", N * Ho * Wo * 16)] if op == "stem_conv2_views" else [O("out", N * H * W * 8)])
+    if op == "refine_front":
+        return [img] + front + [O("x16", N * H * W * 16)]
+    if op == "refine_tail":  # w3 [2][3][3][16][4]
+        return [I("x16", N * H * W * 16), P("w3", 2 * 3 * 3 * 16 * 4), P("s3", 8)] + tail
+    if op == "refine_fused":  # w3a float16 [5][2][64][8]
+        return [img] + front + [P("w3a", 5 * 2 * 64 * 8, "float16"), P("s3", 8)] + tail
+    raise ValueError(op)
+
+
+def arguments(row: Row, a: Dict[str, int]) -> Tuple[str, list]:
+    """The row's call through the C ABI with the addresses ``a`` (buffer name -> address; an absent name is NULL) -> (entry point, its
+    full argument list)."""
+    N, H, W = row.N, row.H, row.W
+    fn, names = ABI[row.op]
+    ptrs = [a.get(n) for n in names]
+    if row.op == "conv2d":
+        Ho, Wo = out_hw(row)
+        tail = [N, H, W, row.cin, row.cout, row.K, row.S, row.pad, row.dil, row.relu, int(row.nchw_in), int(row.planar),
+                Ho // 2 if row.up else 0, Wo // 2 if row.up else 0]
+    elif row.op == "mfma1x1":
+        tail = [N, H, W, 64, row.cout, row.ca, 1, 1, 0, 1, row.relu, 0]
+    elif row.op == "f16s":
+        tail = [N, H, W, row.cin, row.cout, row.K, row.S, row.relu]
+    elif row.op == "pair":
+        tail = [N, H, W, 16, row.relu]
+    elif row.op == "heads":
+        tail = [N, H, W, row.cin, row.cout, row.ca, row.dil]
+    elif row.op == "fpn_level":
+        tail = [N, H, W, row.cin, row.cout, row.ca]
+    elif row.op == "fpn_tail":
+        tail = [N, H, W, 16, 64, 16]
+    elif row.op == "deconv":
+        tail = [N, H, W, 8, 8, row.relu]
+    elif row.op in ("stem_views", "stem_conv2_views"):
+        ptrs.insert(1, row.views)
+        tail = [N // row.views, H, W]
+    else:
+        tail = [N, H, W]
+    return fn, ptrs + tail + [None]
+
+
 def record(row: Row, L=None) -> Tuple[int, List[str]]:
     """Records the row's call in THIS process (whatever its environment) -> (return code, recorded kernel names)."""
     from patchmatchnet_amd import _lib
-    L = L or _lib.lib()
-    A = 0x100000
-    img = A + 4 if row.misalign else A
-    N, H, W = row.N, row.H, row.W
-    p = ctypes.c_void_p()
-    assert L.pmn_plan_create(ctypes.byref(p)) == 0
-    assert L.pmn_plan_begin(p) == 0
-    try:
-        if row.op == "conv2d":
-            Ho, Wo = out_hw(row)
-            rc = L.pmn_conv2d(A, A, A, A if row.up else None, A, N, H, W, row.cin, row.cout, row.K, row.S, row.pad, row.dil, row.relu,
-                              int(row.nchw_in), int(row.planar), Ho // 2 if row.up else 0, Wo // 2 if row.up else 0, None)
-        elif row.op == "mfma1x1":
-            rc = L.pmn_conv2d_mfma(A, A, A, A, A, N, H, W, 64, row.cout, row.ca, 1, 1, 0, 1, row.relu, 0, None)
-        elif row.op == "f16s":
-            rc = L.pmn_conv2d_f16s(A, A, A, A, N, H, W, row.cin, row.cout, row.K, row.S, row.relu, None)
-        elif row.op == "pair":
-            rc = L.pmn_conv2d_f16s_pair(A, A, A, A, A, A, N, H, W, 16, row.relu, None)
-        elif row.op == "heads":
-            rc = L.pmn_offset_heads_f16s(A, A, A, A, A if row.ca < row.cout else None, N, H, W, row.cin, row.cout, row.ca, row.dil, None)
-        elif row.op == "fpn_level":
-            rc = L.pmn_fpn_level(A, A if row.up else None, A, A, A, A if row.ca < row.cout else None, N, H, W, row.cin, row.cout, row.ca,
-                                 None)
-        elif row.op == "fpn_tail":
-            rc = L.pmn_fpn_tail(A, A, A, A, A, A, N, H, W, 16, 64, 16, None)
-        elif row.op == "deconv":
-            rc = L.pmn_deconv3x3s2(A, A, A, A, N, H, W, 8, 8, row.relu, None)
-        elif row.op == "stem":
-            rc = L.pmn_stem(A, A, A, A, A, A, N, H, W, None)
-        elif row.op == "stem_f16s":
-            rc = L.pmn_stem_f16s(img, A, A, A, A, A, N, H, W, None)
-        elif row.op == "stem_views":
-            rc = L.pmn_stem_f16s_views(A, row.views, A, A, A, A, A, N // row.views, H, W, None)
-        elif row.op == "stem_conv2":
-            rc = L.pmn_stem_conv2_f16s(img, A, A, A, A, A, A, A, N, H, W, None)
-        elif row.op == "stem_conv2_views":
-            rc = L.pmn_stem_conv2_f16s_views(A, row.views, A, A, A, A, A, A, A, N // row.views, H, W, None)
-        elif row.op == "refine_front":
-            rc = L.pmn_refine_front(A, A, A, A, A, A, A, N, H, W, None)
-        elif row.op == "refine_tail":
-            rc = L.pmn_refine_tail(A, A, A, A, A, A, A, A, N, H, W, None)
-        elif row.op == "refine_fused":
-            rc = L.pmn_refine_fused(img, A, A, A, A, A, A, A, A, A, A, A, A, N, H, W, None)
-        else:
-            raise ValueError(row.op)
-    finally:
-        assert L.pmn_plan_end(p) == 0
-    names = [L.pmn_plan_kernel_name(p, i).decode() for i in range(L.pmn_plan_count(p))]
-    L.pmn_plan_destroy(p)
-    return rc, names
+    addr, _ = recording_addresses(buffers(row), 0x100000, {})  # (no host buffers on this side)
+    return KS.record_call(L or _lib.lib(), *arguments(row, addr))
 
 
 def child(env: Env, what: str, timeout: float) -> subprocess.CompletedProcess:
@@ -347,6 +419,9 @@ def child_main(what: str, env: Env) -> None:
             continue
         if what == "record":
             out[row.id] = record(row)
+        elif what == "guard":  # (an AssertionError of guard_band.check ends the child with its message and a non-zero code)
+            run_guard(row)
+            out[row.id] = "ok"
         else:
             rc, names = record(row)
             got, errs = run_device(row), {}
@@ -686,6 +761,95 @@ def mistakes(row: Row, ref: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     return out
 
 
+# ---- the row's buffers on the host, the row on the device --------------------------------------------------------------------------------
+
+def payloads(row: Row) -> Dict[str, np.ndarray]:
+    """The host array behind every input and weight buffer of buffers(row), in the layout the C ABI reads: case(row)'s planar maps
+    channels-last where the entry point wants them, the weights through their packers in patchmatchnet_amd.params."""
+    import torch
+
+    from patchmatchnet_amd import params
+    c = case(row)
+    cl = lambda a: np.asarray(a).transpose(0, 2, 3, 1)  # noqa: E731  planar -> channels-last
+
+    def TW(l):
+        return {k: (tuple(torch.from_numpy(a) for a in v) if k == "bn" else torch.from_numpy(v)) for k, v in l.items()}
+
+    def pk(fn, l, **kw):
+        L = TW(l)
+        return fn(L["w"], **({"bn": L["bn"]} if "bn" in L else {"bias": L["bias"]} if "bias" in L else {}), **kw)
+
+    p: Dict = {}
+    if row.op == "conv2d":
+        p["in"] = c["x"] if row.nchw_in else cl(c["x"])
+        p["weights"], p["shift"] = pk(params.pack_conv, c["l"])
+        if row.up:
+            p["up"] = cl(c["u"])
+    elif row.op in ("mfma1x1", "f16s"):
+        p["in"] = cl(c["x"])
+        p["weights"], p["shift"] = pk(params.pack_conv_mfma if row.op == "mfma1x1" else params.pack_conv_f16s, c["l"])
+    elif row.op == "pair":
+        p["in"] = cl(c["x"])
+        (p["weights_a"], p["shift_a"]), (p["weights_b"], p["shift_b"]) = pk(params.pack_conv_f16s, c["la"]), pk(params.pack_conv_f16s, c["lb"])
+    elif row.op == "heads":
+        L = TW(c["l"])
+        p["in"] = cl(c["x"])
+        p["weights"], p["shift"] = params.pack_offset_heads_f16s(L["w"], L["bias"])
+    elif row.op == "fpn_level":
+        p.update(x=cl(c["x"]), w=c["w"], b=c["b"])
+        if row.up:
+            p["u"] = cl(c["u"])
+    elif row.op == "fpn_tail":
+        p.update(x=cl(c["x"]), up=cl(c["u"]))
+        (p["w_in"], p["b_in"]), (p["w_out"], _) = pk(params.pack_conv, c["inner"]), pk(params.pack_conv, c["outer"])
+    elif row.op == "deconv":
+        L = TW(c["l"])
+        p["in"] = cl(c["x"])
+        p["weights"], p["shift"] = params.pack_deconv(L["w"], L.get("bn"))
+    elif row.op in ("stem", "stem_f16s", "stem_views") + STEM_CONV2:
+        if row.views:
+            B = row.N // row.views
+            p.update({f"img{v}": c["x"][v * B:(v + 1) * B] for v in range(row.views)})
+        else:
+            p["img"] = c["x"]
+        p["w0"], p["s0"] = pk(params.pack_conv, c["la"])
+        Lb = TW(c["lb"])
+        if row.op == "stem":
+            p["w1"], p["s1"] = pk(params.pack_conv, c["lb"])
+        elif row.op in STEM_CONV2:  # (pack_stem_conv1_f16s takes BatchNorm tensors: a bias alone is scale 1, mean 0, variance 1 at eps 0)
+            bn1, eps = (Lb["bn"], R.BN_EPS) if "bn" in Lb else ((torch.ones(8), Lb["bias"], torch.zeros(8), torch.ones(8)), 0.0)
+            p["w1a"], p["s1"] = params.pack_stem_conv1_f16s(Lb["w"], bn1, eps)
+            p["w2b"], p["s2"] = pk(params.pack_conv_f16s, c["lc"])
+        else:
+            p["w1a"], p["s1"] = params.pack_stem_conv1_f16s(Lb["w"], Lb["bn"])
+    else:
+        T0, Td, T3 = TW(c["c0"]), TW(c["dc"]), TW(c["c3"])
+        w3, s3, wr = params.pack_refine_tail(T3["w"], T3["bn"], torch.from_numpy(c["wr"]))
+        p.update(wr=wr, dnorm=c["dnorm"], depth_min=c["dmin"], depth_max=c["dmax"])
+        if row.op != "refine_tail":
+            p.update(img=c["img"], t2=cl(c["t2"]))
+            p["w0"], p["s0"] = params.pack_conv(T0["w"], bn=T0["bn"])
+            p["wd"], p["sd"] = params.pack_deconv(Td["w"], Td["bn"])
+        if row.op == "refine_tail":
+            p.update(x16=cl(c["x16"]), w3=w3, s3=s3)
+        elif row.op == "refine_fused":
+            p["w3a"], p["s3"] = params.pack_refine_conv3_f16s(T3["w"], T3["bn"])
+    return {b.name: np.ascontiguousarray(p[b.name]) for b in buffers(row) if b.role != "out" and not b.table_of}
+
+
+def abi_outputs(row: Row, y: np.ndarray) -> Dict[str, np.ndarray]:
+    """The planar output of the row (run_device's, or the reference's) as the arrays the call's output buffers hold."""
+    cl = lambda a: np.ascontiguousarray(a.transpose(0, 2, 3, 1))  # noqa: E731
+    ca = row.ca
+    if row.op in ("mfma1x1", "fpn_level"):
+        return dict({"out" if row.op == "mfma1x1" else "out_a": cl(y[:, :ca])}, **({"out_b": cl(y[:, ca:])} if ca < row.cout else {}))
+    if row.op == "heads":
+        return dict(out_a=np.ascontiguousarray(y[:, :ca]), **({"out_b": np.ascontiguousarray(y[:, ca:])} if ca < row.cout else {}))
+    if row.op == "refine_front":
+        return {"x16": cl(y)}
+    return {"out": y if row.planar or row.op in ("refine_tail", "refine_fused") else cl(y)}
+
+
 # ---- the row on the device -----------------------------------------------------------------------------------------------------------------
 
 def run_device(row: Row, want_aligned: bool = False):
@@ -696,16 +860,12 @@ def run_device(row: Row, want_aligned: bool = False):
     import torch
 
     import patchmatchnet_amd as P
-    from patchmatchnet_amd import params
     ops = P.ops
     dev = "cuda:0"
-    c = case(row)
+    host = payloads(row)
 
     def t(a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-    def cl(a):  # planar -> channels-last
-        return t(np.asarray(a).transpose(0, 2, 3, 1))
 
     def pl(x):  # channels-last device tensor -> planar numpy
         return x.permute(0, 3, 1, 2).contiguous().cpu().numpy()
@@ -717,103 +877,90 @@ def run_device(row: Row, want_aligned: bool = False):
         assert v.data_ptr() % 16 == 4
         return v
 
-    def TW(l):
-        return {k: (tuple(torch.from_numpy(a) for a in v) if k == "bn" else torch.from_numpy(v)) for k, v in l.items()}
-
-    def pk(fn, l, **kw):
-        L = TW(l)
-        return tuple(t(a) for a in fn(L["w"], **({"bn": L["bn"]} if "bn" in L else {"bias": L["bias"]} if "bias" in L else {}), **kw))
-
+    d = {k: t(v) for k, v in host.items() if not (row.op == "stem_conv2_views" and k.startswith("img"))}  # (those: allocated apart below)
+    g = lambda *names: tuple(d[n] for n in names)  # noqa: E731
     relu = bool(row.relu)
     other = None
     with torch.no_grad():
         if row.op == "conv2d":
-            w, s = pk(params.pack_conv, c["l"])
-            y = ops.conv2d(t(c["x"]) if row.nchw_in else cl(c["x"]), w, s, row.cout, row.K, row.S, row.pad, row.dil, relu,
-                           cl(c["u"]) if row.up else None, row.nchw_in, row.planar)
+            y = ops.conv2d(*g("in", "weights", "shift"), row.cout, row.K, row.S, row.pad, row.dil, relu, d.get("up"), row.nchw_in, row.planar)
             out = y.cpu().numpy() if row.planar else pl(y)
         elif row.op == "mfma1x1":
-            w, s = pk(params.pack_conv_mfma, c["l"])
-            a, b = ops.pointwise_split_mfma(cl(c["x"]), w, s, row.cout, row.ca)
+            a, b = ops.pointwise_split_mfma(*g("in", "weights", "shift"), row.cout, row.ca)
             out = np.concatenate([pl(a), pl(b)], 1)
         elif row.op == "f16s":
-            w, s = pk(params.pack_conv_f16s, c["l"])
-            out = pl(ops.conv2d_f16s(cl(c["x"]), w, s, row.K, row.S, relu))
+            out = pl(ops.conv2d_f16s(*g("in", "weights", "shift"), row.K, row.S, relu))
         elif row.op == "pair":
-            (wa, sa), (wb, sb) = pk(params.pack_conv_f16s, c["la"]), pk(params.pack_conv_f16s, c["lb"])
-            out = pl(ops.conv2d_f16s_pair(cl(c["x"]), wa, sa, wb, sb, relu))
+            out = pl(ops.conv2d_f16s_pair(*g("in", "weights_a", "shift_a", "weights_b", "shift_b"), relu))
         elif row.op == "heads":
-            L = TW(c["l"])
-            w, s = (t(a) for a in params.pack_offset_heads_f16s(L["w"], L["bias"]))
-            a, b = ops.offset_heads_f16s(cl(c["x"]), w, s, row.cout, row.ca, row.dil)
+            a, b = ops.offset_heads_f16s(*g("in", "weights", "shift"), row.cout, row.ca, row.dil)
             out = np.concatenate([a.cpu().numpy()] + ([b.cpu().numpy()] if b is not None else []), 1)
         elif row.op == "fpn_level":
-            a, b = ops.fpn_level(cl(c["x"]), cl(c["u"]) if row.up else None, t(c["w"]), t(c["b"]), row.ca)
+            a, b = ops.fpn_level(d["x"], d.get("u"), d["w"], d["b"], row.ca)
             out = np.concatenate([pl(a)] + ([pl(b)] if b is not None else []), 1)
         elif row.op == "fpn_tail":
-            (wi, bi), (wo, _) = pk(params.pack_conv, c["inner"]), pk(params.pack_conv, c["outer"])
-            out = pl(ops.fpn_tail(cl(c["x"]), cl(c["u"]), wi, bi, wo))
+            out = pl(ops.fpn_tail(*g("x", "up", "w_in", "b_in", "w_out")))
         elif row.op == "deconv":
-            L = TW(c["l"])
-            w, s = (t(a) for a in params.pack_deconv(L["w"], L.get("bn")))
-            out = pl(ops.deconv3x3s2(cl(c["x"]), w, s, relu))
-        elif row.op in ("stem", "stem_f16s", "stem_views"):
-            w0, s0 = pk(params.pack_conv, c["la"])
-            if row.op == "stem":
-                w1, s1 = pk(params.pack_conv, c["lb"])
-                out = pl(ops.stem(t(c["x"]), w0, s0, w1, s1))
-            else:
-                Lb = TW(c["lb"])
-                w1, s1 = (t(a) for a in params.pack_stem_conv1_f16s(Lb["w"], Lb["bn"]))
-                if row.op == "stem_f16s":
-                    out = pl(ops.stem_f16s(mis(c["x"]) if row.misalign else t(c["x"]), w0, s0, w1, s1))
-                    if want_aligned:
-                        other = pl(ops.stem_f16s(t(c["x"]), w0, s0, w1, s1))
-                else:
-                    V, B = row.views, row.N // row.views
-                    imgs = [t(c["x"][v * B:(v + 1) * B]) for v in range(V)]
-                    tab = ops.SourceTable(torch.tensor([i.data_ptr() for i in imgs], dtype=torch.int64, device=dev), (V, B, 3, row.H, row.W))
-                    out = pl(ops.stem_f16s_views(tab, w0, s0, w1, s1))
-                    if want_aligned:
-                        other = np.concatenate([pl(ops.stem_f16s(i, w0, s0, w1, s1)) for i in imgs], 0)
+            out = pl(ops.deconv3x3s2(*g("in", "weights", "shift"), relu))
+        elif row.op == "stem":
+            out = pl(ops.stem(*g("img", "w0", "s0", "w1", "s1")))
+        elif row.op == "stem_f16s":
+            w = g("w0", "s0", "w1a", "s1")
+            out = pl(ops.stem_f16s(mis(host["img"]) if row.misalign else d["img"], *w))
+            if want_aligned:
+                other = pl(ops.stem_f16s(d["img"], *w))
+        elif row.op == "stem_views":
+            w = g("w0", "s0", "w1a", "s1")
+            V, B = row.views, row.N // row.views
+            imgs = [d[f"img{v}"] for v in range(V)]
+            tab = ops.SourceTable(torch.tensor([i.data_ptr() for i in imgs], dtype=torch.int64, device=dev), (V, B, 3, row.H, row.W))
+            out = pl(ops.stem_f16s_views(tab, *w))
+            if want_aligned:
+                other = np.concatenate([pl(ops.stem_f16s(i, *w)) for i in imgs], 0)
         elif row.op in STEM_CONV2:
-            w0, s0 = pk(params.pack_conv, c["la"])
-            w2, s2 = pk(params.pack_conv_f16s, c["lc"])
-            Lb = TW(c["lb"])  # (pack_stem_conv1_f16s takes BatchNorm tensors: a bias alone is scale 1, mean 0, variance 1 at eps 0)
-            bn1, eps = (Lb["bn"], R.BN_EPS) if "bn" in Lb else ((torch.ones(8), Lb["bias"], torch.zeros(8), torch.ones(8)), 0.0)
-            w1, s1 = (t(a) for a in params.pack_stem_conv1_f16s(Lb["w"], bn1, eps))
-            two = lambda im: ops.conv2d_f16s(ops.stem_f16s(im, w0, s0, w1, s1), w2, s2, 5, 2, relu=True)  # noqa: E731
+            w = g("w0", "s0", "w1a", "s1", "w2b", "s2")
+            two = lambda im: ops.conv2d_f16s(ops.stem_f16s(im, *w[:4]), *w[4:], 5, 2, relu=True)  # noqa: E731
             if row.op == "stem_conv2":
-                out = pl(ops.stem_conv2_f16s(mis(c["x"]) if row.misalign else t(c["x"]), w0, s0, w1, s1, w2, s2))
+                out = pl(ops.stem_conv2_f16s(mis(host["img"]) if row.misalign else d["img"], *w))
                 if want_aligned:  # the two launches on the aligned image, and for a base off by one float the aligned call itself
-                    other = [pl(two(t(c["x"])))] + ([pl(ops.stem_conv2_f16s(t(c["x"]), w0, s0, w1, s1, w2, s2))] if row.misalign else [])
+                    other = [pl(two(d["img"]))] + ([pl(ops.stem_conv2_f16s(d["img"], *w))] if row.misalign else [])
             else:
                 V, B = row.views, row.N // row.views
                 imgs, spacers = {}, []
                 for v in reversed(range(V)):  # allocated apart and backwards: the table's order is unrelated to the addresses'
                     spacers.append(torch.empty(1000 * (v + 1) + 4, device=dev))
-                    imgs[v] = t(c["x"][v * B:(v + 1) * B])
+                    imgs[v] = t(host[f"img{v}"])
                 imgs = [imgs[v] for v in range(V)]
                 assert all(ops.SourceTable.image_in_place(i) for i in imgs)
                 tab = ops.SourceTable(torch.tensor([i.data_ptr() for i in imgs], dtype=torch.int64, device=dev), (V, B, 3, row.H, row.W))
-                out = pl(ops.stem_conv2_f16s_views(tab, w0, s0, w1, s1, w2, s2))
+                out = pl(ops.stem_conv2_f16s_views(tab, *w))
                 if want_aligned:
                     other = [np.concatenate([pl(two(i)) for i in imgs], 0)]
+        elif row.op == "refine_front":
+            out = pl(ops.refine_front(*g("img", "t2", "w0", "s0", "wd", "sd")))
+        elif row.op == "refine_tail":
+            out = ops.refine_tail(*g("x16", "w3", "s3", "wr", "dnorm", "depth_min", "depth_max")).cpu().numpy()
         else:
-            T0, Td, T3 = TW(c["c0"]), TW(c["dc"]), TW(c["c3"])
-            w0, s0 = (t(a) for a in params.pack_conv(T0["w"], bn=T0["bn"]))
-            wd, sd = (t(a) for a in params.pack_deconv(Td["w"], Td["bn"]))
-            w3, s3, wr = (t(a) for a in params.pack_refine_tail(T3["w"], T3["bn"], torch.from_numpy(c["wr"])))
-            tail = (t(c["dnorm"]), t(c["dmin"]), t(c["dmax"]))
-            if row.op == "refine_front":
-                out = pl(ops.refine_front(t(c["img"]), cl(c["t2"]), w0, s0, wd, sd))
-            elif row.op == "refine_tail":
-                out = ops.refine_tail(cl(c["x16"]), w3, s3, wr, *tail).cpu().numpy()
-            else:
-                w3a, s3a = (t(a) for a in params.pack_refine_conv3_f16s(T3["w"], T3["bn"]))
-                args = (cl(c["t2"]), w0, s0, wd, sd, w3a, s3a, wr) + tail
-                out = ops.refine_fused(mis(c["img"]) if row.misalign else t(c["img"]), *args).cpu().numpy()
-                if want_aligned:
-                    other = ops.refine_fused(t(c["img"]), *args).cpu().numpy()
+            args = g("t2", "w0", "s0", "wd", "sd", "w3a", "s3", "wr", "dnorm", "depth_min", "depth_max")
+            out = ops.refine_fused(mis(host["img"]) if row.misalign else d["img"], *args).cpu().numpy()
+            if want_aligned:
+                other = ops.refine_fused(d["img"], *args).cpu().numpy()
         torch.cuda.synchronize()
     return (out, other) if want_aligned else out
+
+
+def run_guard(row: Row, dev: str = "cuda:0") -> None:
+    """The row through the raw C ABI on ``dev`` with every buffer between guard bands (tests/guard_band.py), then guard_band.check:
+    no band touched, no input changed, every output the bytes of run_device's, the ops wrapper on ordinary tensors."""
+    import torch
+
+    import guard_band as GB
+    from patchmatchnet_amd import _lib
+    want = abi_outputs(row, run_device(row))
+    arenas = GB.build(buffers(row), payloads(row), dev)
+    fn, args = arguments(row, {k: a.ptr for k, a in arenas.items()})
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), fn)(*args)
+        torch.cuda.synchronize()
+    assert rc == 0, (fn, rc)
+    GB.check(arenas, want)

@@ -7,7 +7,8 @@ view weights at reduced resolution and costs large enough to overflow a softmax 
 
 Plain helper module (no tests here): tests/test_kernel_space.py checks the table against the library on the CPU (launch-plan
 recording and the library's own symbol table), tests/test_kernel_space_gpu.py runs every row on the device against the float64
-reference tests/ref64.py.
+reference tests/ref64.py, tests/test_guard_band_gpu.py runs every row through the raw C ABI between guard bands (buffers(),
+arguments(), run_guard() below).
 """
 from __future__ import annotations
 
@@ -17,6 +18,10 @@ from dataclasses import dataclass, replace
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
+
+from guard_band import Buf, recording_addresses
+
+MLP_FLOATS = 340  # PMN_MLP_FLOATS of include/pmn_hip.h
 
 # ---- the rows ---------------------------------------------------------------------------------------------------------------------
 
@@ -295,54 +300,108 @@ def library_instantiations(path: str, families: Optional[Dict[str, str]] = None)
     return {k: v for k, v in out.items() if any(k.startswith(f"_Z{len(f)}{f}I") for f in fams)}
 
 
-# ---- launch-plan recording (fake device addresses: recording validates arguments and dereferences nothing) -------------------------
+# ---- launch-plan recording (fake device addresses: recording validates arguments and dereferences no device pointer) ---------------
 
 _FAKE = 0x100000
 
 
-def _tab(row: Row, n: int) -> np.ndarray:
-    return np.ascontiguousarray(neighbor_table(row, n), np.int32)
+def buffers(row: Row, views: bool = False) -> List[Buf]:
+    """The pointer arguments of the row's call: name (include/pmn_hip.h's), role, dtype and element count exactly as the header
+    documents it.  ``views`` (warp rows): the call through pmn_warp_correlate_views, one buffer per source view and their table."""
+    B, N, C, G, D, h, w = row.B, row.N, row.C, row.G, row.D, row.h, row.w
+    F = lambda name, role, count, **kw: Buf(name, role, "float32", count, **kw)  # noqa: E731
+    T = lambda name, K: Buf(name, "in", "int32", 2 * K, host=True)  # noqa: E731  host int[2K]: (dy, dx) pairs
+    if row.op == "init":
+        s = row.depth_shift
+        return ([F("noise", "in", B * 48 * h * w)] if row.init == "noise" else [F("depth", "in", B * (h >> s) * (w >> s))]) + \
+            [F("depth_min", "in", B), F("depth_max", "in", B)] + \
+            ([F("propa_offsets", "in", B * 2 * row.propK * h * w), T("propa_table_host", row.propK)] if row.propK else []) + \
+            [F("depth_sample", "out", B * D * h * w), F("xnorm", "out", B * h * w * D)]
+    if row.op == "feature_weight":
+        return [F("ref_nhwc", "in", B * h * w * C), F("eval_offsets", "in", B * 2 * D * h * w), T("eval_table_host", D),
+                F("mlp", "weights", MLP_FLOATS),
+                F("out_feature_weight", "out", B * D * h * w)]
+    if row.op == "warp":
+        hs, ws = row.hs or h, row.ws or w
+        if views:
+            names = tuple(f"src_view{v}" for v in range(N))
+            src = [F(n, "in", B * hs * ws * C) for n in names] + [Buf("src_view_table", "in", "int64", N, table_of=names)]
+        else:
+            src = [F("src_nhwc", "in", N * B * hs * ws * C)]
+        s = row.vw_shift
+        return [F("ref_nhwc", "in", B * h * w * C)] + src + [F("rel_proj", "in", B * N * 16), F("depth_sample", "in", B * D * h * w)] + \
+            ([] if row.pixelwise else [F("view_weights_in", "in", B * N * (h >> s) * (w >> s))]) + [F("similarity_mlp", "weights", MLP_FLOATS)] + \
+            ([F("pixelwise_mlp", "weights", MLP_FLOATS)] if row.pixelwise else []) + [F("cost_out", "out", B * h * w * D)] + \
+            ([F("view_weights_out", "out", B * N * h * w), Buf("vw_argmax_out", "out", "int32", B * N * h * w, optional=True)]
+             if row.pixelwise else []) + [F("similarity_out", "out", B * G * D * h * w, optional=True)]
+    if row.op == "aggregate":
+        K = row.K
+        return [F("cost", "in", B * h * w * D), F("depth_sample", "in", B * D * h * w), F("xnorm", "in", B * h * w * D),
+                F("feature_weight", "in", B * K * h * w), F("eval_offsets", "in", B * 2 * K * h * w), T("eval_table_host", K),
+                F("score_out", "out", B * D * h * w), F("depth_out", "out", B * h * w)]
+    if row.op == "confidence":
+        return [F("score", "in", B * D * h * w), F("confidence_out", "out", B * row.H * row.W),
+                Buf("depth_index_out", "out", "int32", B * h * w, optional=True)]
+    if row.op == "normalize":
+        return [F("depth", "in", B * h * w), F("depth_min", "in", B), F("depth_max", "in", B), F("out", "out", B * h * w)]
+    raise ValueError(row.op)
+
+
+def arguments(row: Row, a: Dict[str, int], views: bool = False, interval_scale: float = 0.01) -> Tuple[str, list]:
+    """The row's call through the C ABI with the addresses ``a`` (buffer name -> address; an absent name is NULL) -> (entry point, its
+    full argument list).  ``interval_scale``: the one by-value argument that comes from the row's inputs (recording passes 0.01)."""
+    g = a.get
+    if row.op == "init":
+        return "pmn_init_hypotheses", [g("noise"), g("depth"), row.depth_shift, a["depth_min"], a["depth_max"], row.num_sample,
+                                       interval_scale, g("propa_offsets"), g("propa_table_host"), row.propK, row.B, row.h, row.w,
+                                       a["depth_sample"], a["xnorm"], None]
+    if row.op == "feature_weight":
+        return "pmn_feature_weight", [a["ref_nhwc"], a["eval_offsets"], a["eval_table_host"], a["mlp"], row.B, row.C, row.G, row.D, row.h,
+                                      row.w, a["out_feature_weight"], None]
+    if row.op == "warp":
+        hs, ws = row.hs or row.h, row.ws or row.w
+        return "pmn_warp_correlate_views" if views else "pmn_warp_correlate", [
+            a["ref_nhwc"], a["src_view_table" if views else "src_nhwc"], a["rel_proj"], a["depth_sample"], g("view_weights_in"), row.vw_shift,
+            a["similarity_mlp"], g("pixelwise_mlp"), row.B, row.N, row.C, row.G, row.D, row.h, row.w, hs, ws, a["cost_out"],
+            g("view_weights_out"), g("vw_argmax_out"), g("similarity_out"), None]
+    if row.op == "aggregate":
+        return "pmn_aggregate_regress", [a["cost"], a["depth_sample"], a["xnorm"], a["feature_weight"], a["eval_offsets"],
+                                         a["eval_table_host"], row.K, interval_scale, int(row.is_inverse), row.B, row.D, row.h, row.w,
+                                         a["score_out"], a["depth_out"], None]
+    if row.op == "confidence":
+        return "pmn_confidence", [a["score"], row.B, row.D, row.h, row.w, row.H, row.W, a["confidence_out"], g("depth_index_out"), None]
+    if row.op == "normalize":
+        return "pmn_normalize_depth", [a["depth"], a["depth_min"], a["depth_max"], row.B, row.h * row.w, a["out"], None]
+    raise ValueError(row.op)
+
+
+def host_tables(row: Row) -> Dict[str, np.ndarray]:
+    """The row's host neighbour table under its argument's name: int32 [K,2] = the header's int[2K]."""
+    name, K = {"init": ("propa_table_host", row.propK), "feature_weight": ("eval_table_host", row.D),
+               "aggregate": ("eval_table_host", row.K)}.get(row.op, ("", 0))
+    return {name: np.ascontiguousarray(neighbor_table(row, K), np.int32)} if K else {}
+
+
+def record_call(L, fn: str, args: list) -> Tuple[int, List[str]]:
+    """One entry-point call between pmn_plan_begin and pmn_plan_end -> (return code, recorded kernel names)."""
+    p = ctypes.c_void_p()
+    assert L.pmn_plan_create(ctypes.byref(p)) == 0
+    assert L.pmn_plan_begin(p) == 0
+    try:
+        rc = getattr(L, fn)(*args)
+    finally:
+        assert L.pmn_plan_end(p) == 0
+    names = [L.pmn_plan_kernel_name(p, i).decode() for i in range(L.pmn_plan_count(p))]
+    L.pmn_plan_destroy(p)
+    return rc, names
 
 
 def record(row: Row, L=None) -> Tuple[int, List[str]]:
     """Records the row's call through pmn_plan_begin / pmn_plan_end -> (return code, recorded kernel names)."""
     from patchmatchnet_amd import _lib
-    L = L or _lib.lib()
-    A = _FAKE
-    p = ctypes.c_void_p()
-    assert L.pmn_plan_create(ctypes.byref(p)) == 0
-    assert L.pmn_plan_begin(p) == 0
-    keep = []
-    try:
-        if row.op == "init":
-            t = _tab(row, row.propK) if row.propK else None
-            keep.append(t)
-            rc = L.pmn_init_hypotheses(A if row.init == "noise" else None, A if row.init == "depth" else None, row.depth_shift, A, A,
-                                       row.num_sample, 0.01, A if row.propK else None,
-                                       t.ctypes.data_as(ctypes.c_void_p) if t is not None else None, row.propK, row.B, row.h, row.w,
-                                       A, A, None)
-        elif row.op == "feature_weight":
-            t = _tab(row, row.D)
-            rc = L.pmn_feature_weight(A, A, t.ctypes.data_as(ctypes.c_void_p), A, row.B, row.C, row.G, row.D, row.h, row.w, A, None)
-        elif row.op == "warp":
-            hs, ws = row.hs or row.h, row.ws or row.w
-            rc = L.pmn_warp_correlate(A, A, A, A, None if row.pixelwise else A, row.vw_shift, A, A if row.pixelwise else None, row.B,
-                                      row.N, row.C, row.G, row.D, row.h, row.w, hs, ws, A, A if row.pixelwise else None, None, None,
-                                      None)
-        elif row.op == "aggregate":
-            t = _tab(row, row.K)
-            rc = L.pmn_aggregate_regress(A, A, A, A, A, t.ctypes.data_as(ctypes.c_void_p), row.K, 0.01, int(row.is_inverse), row.B,
-                                         row.D, row.h, row.w, A, A, None)
-        elif row.op == "confidence":
-            rc = L.pmn_confidence(A, row.B, row.D, row.h, row.w, row.H, row.W, A, None, None)
-        elif row.op == "normalize":
-            rc = L.pmn_normalize_depth(A, A, A, row.B, row.h * row.w, A, None)
-        else:
-            raise ValueError(row.op)
-    finally:
-        assert L.pmn_plan_end(p) == 0
-    names = [L.pmn_plan_kernel_name(p, i).decode() for i in range(L.pmn_plan_count(p))]
-    L.pmn_plan_destroy(p)
+    addr, held = recording_addresses(buffers(row), _FAKE, host_tables(row))  # (the neighbour table is read while recording)
+    rc, names = record_call(L or _lib.lib(), *arguments(row, addr))
+    del held
     return rc, names
 
 
@@ -698,3 +757,90 @@ def mistakes(row: Row, x: Dict[str, np.ndarray], ref: Dict[str, np.ndarray], mlp
         out["tail pixel unwritten"] = ("normalized", _tail(ref["normalized"]))
         out["depth range of the other sample"] = ("normalized", R.normalize_depth(x["depth"], roll(x["depth_min"]), roll(x["depth_max"])))
     return out
+
+
+# ---- the row through the raw C ABI between guard bands (tests/guard_band.py) ------------------------------------------------------------
+
+# output buffer -> the key of reference() that holds the same elements
+REF_KEY = {"depth_sample": "depth_sample", "xnorm": "xnorm", "out_feature_weight": "feature_weight", "cost_out": "cost",
+           "view_weights_out": "view_weights", "vw_argmax_out": "view_weights", "similarity_out": "similarity", "score_out": "score",
+           "depth_out": "depth", "confidence_out": "confidence", "depth_index_out": "depth_index", "out": "normalized"}
+
+
+def payloads(row: Row, x: Dict[str, np.ndarray], mlps, views: bool = False) -> Dict[str, np.ndarray]:
+    """The host array behind every input and weight buffer of buffers(row, views), in the layout the C ABI reads: inputs(row)'s
+    arrays, cost and xnorm hypothesis-last, the packed MLP blocks, the host neighbour table, the source views one by one for the
+    table entry."""
+    last = lambda a: np.ascontiguousarray(a.transpose(0, 2, 3, 1))  # noqa: E731
+    p = dict(x, **host_tables(row))
+    if row.op == "feature_weight":
+        p["mlp"] = mlps[2].packed()
+    elif row.op == "warp":
+        p.update({f"src_view{v}": s for v, s in enumerate(x["src_nhwc"])}, similarity_mlp=mlps[0].packed(), pixelwise_mlp=mlps[1].packed(),
+                 view_weights_in=x.get("view_weights"))
+    elif row.op == "aggregate":
+        p.update(cost=last(x["cost"]), xnorm=last(x["xnorm"]))
+    return {b.name: p[b.name] for b in buffers(row, views) if b.role != "out" and not b.table_of}
+
+
+def ops_outputs(row: Row, x: Dict[str, np.ndarray], mlps, views: bool = False, dev: str = "cuda:0") -> Dict[str, np.ndarray]:
+    """The row through patchmatchnet_amd.ops on ordinary tensors -> every output buffer of buffers(row) as the array its storage holds."""
+    import torch
+
+    import patchmatchnet_amd as P
+    ops = P.ops
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    n = lambda v: v.contiguous().cpu().numpy()  # noqa: E731
+    last = lambda v: n(v.permute(0, 2, 3, 1))  # noqa: E731  hypothesis-last storage behind a [B,D,h,w] view
+    with torch.no_grad():
+        if row.op == "init":
+            ds, xn = ops.init_hypotheses(t(x["noise"]) if "noise" in x else None, t(x["depth"]) if "depth" in x else None, row.depth_shift,
+                                         t(x["depth_min"]), t(x["depth_max"]), row.num_sample, float(x["interval_scale"]),
+                                         t(x["propa_offsets"]) if row.propK else None, x.get("propa_table"), row.h, row.w)
+            out = {"depth_sample": n(ds), "xnorm": last(xn)}
+        elif row.op == "feature_weight":
+            out = {"out_feature_weight": n(ops.feature_weight(t(x["ref_nhwc"]), t(x["eval_offsets"]), x["eval_table"], t(mlps[2].packed()),
+                                                              row.G))}
+        elif row.op == "warp":
+            src = t(x["src_nhwc"])
+            held = [src[v].clone() for v in range(row.N)] if views else None
+            if views:
+                src = ops.SourceTable(torch.tensor([m.data_ptr() for m in held], dtype=torch.int64, device=dev), src.shape)
+            cost, vw, am, sim = ops.warp_correlate(t(x["ref_nhwc"]), src, t(x["rel_proj"]), t(x["depth_sample"]),
+                                                   t(x["view_weights"]) if "view_weights" in x else None, row.vw_shift, t(mlps[0].packed()),
+                                                   t(mlps[1].packed()) if row.pixelwise else None, row.G, want_similarity=True,
+                                                   want_argmax=row.pixelwise)
+            out = {"cost_out": last(cost), "similarity_out": n(sim)}
+            if row.pixelwise:
+                out.update(view_weights_out=n(vw), vw_argmax_out=n(am))
+        elif row.op == "aggregate":
+            score, dep = ops.aggregate_regress(t(x["cost"]), t(x["depth_sample"]), t(x["xnorm"]), t(x["feature_weight"]), t(x["eval_offsets"]),
+                                               x["eval_table"], float(x["interval_scale"]), row.is_inverse)
+            out = {"score_out": n(score), "depth_out": n(dep)}
+        elif row.op == "confidence":
+            conf, idx = ops.confidence(t(x["score"]), row.H, row.W, want_index=True)
+            out = {"confidence_out": n(conf), "depth_index_out": n(idx)}
+        elif row.op == "normalize":
+            out = {"out": n(ops.normalize_depth(t(x["depth"]), t(x["depth_min"]), t(x["depth_max"])))}
+        else:
+            raise ValueError(row.op)
+        torch.cuda.synchronize()
+    return out
+
+
+def run_guard(row: Row, views: bool = False, dev: str = "cuda:0") -> None:
+    """The row through the raw C ABI on ``dev`` with every buffer between guard bands, then guard_band.check: no band touched, no
+    input changed, every output the bytes of the ops wrapper's."""
+    import torch
+
+    import guard_band as GB
+    from patchmatchnet_amd import _lib
+    x, mlps = inputs(row), nets(row)
+    want = ops_outputs(row, x, mlps, views, dev)
+    arenas = GB.build(buffers(row, views), payloads(row, x, mlps, views), dev)
+    fn, args = arguments(row, {k: a.ptr for k, a in arenas.items()}, views, float(x.get("interval_scale", 0.01)))
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), fn)(*args)
+        torch.cuda.synchronize()
+    assert rc == 0, (fn, rc)
+    GB.check(arenas, want)
